@@ -31,7 +31,16 @@ Two things happen before the W warm-up steps and are named in `config`: the rank
 node (`host_cpus`; --no-pin) and registers the pool for a quarter of a second (`settle`; --settle-seconds 0: the device's
 clocks have to come back from the seconds of host-side set-up).  The timed region is the K steps and nothing else.
 
-Objects in the line next to the contract's keys:
+A plain run does only that: set-up, settle, warm-up, the K timed steps and the line, whose
+`config` names the workload.  `--dump-outputs DIR` then writes, on rank 0, the record the timed entry point returned for
+the region's last step (qtr_result: T as a 4 x 4, the counts, cost, status) as float64 DIR/<field>.npy, every value
+finite: a cost of +inf (GNC-TLS stopped before computing one, as the reference does) is written as -1.  The inputs are
+seeded, so two builds compare output for output.  `--full` adds everything below (and runs the --legs, the CPU baseline
+with --cpu-seconds, the parity checks).  The timed region is the same with and without --full — every
+--nn-event-stride-th step carries the nearest-neighbour event pairs, as in the earlier rounds' lines — so a plain
+ms_per_step and a --full one time the same thing.
+
+Objects in the line next to the contract's keys (--full):
   roofline      — dominant kernel k_nn_f16: the 33-D distance matrix nb' - 2 a.b evaluated on the f16 matrix pipe with
                   every f32 operand split in two halves (3 x 33 products + 3 norm slots = 102 per matrix entry, see
                   match.hip).  `achieved` = 2 * 102 * n_query * n_base FLOP per launch (K padding to 112 not counted)
@@ -131,6 +140,28 @@ def algorithmic_work(P_s, P_t, n_s, n_t, L, M):
     return b, 66.0 * n_s * n_t
 
 
+def result_arrays(res, ql) -> dict:
+    """a copy of a qtr_result, every field as a float64 array (T as 4 x 4): the integer fields are exact in float64.
+    `cost` is Quatro::cost_, which the reference leaves at +inf when GNC-TLS stops at its first iteration (every residual
+    already far inside the noise bound, include/quatro.hpp solveForRotation2D) — as on the step's planted correspondences.
+    A cost is a sum of weighted squared residuals, never negative, so the copy holds -1 for "no cost computed": every
+    array stays finite."""
+    out = {}
+    for name, _ in ql.Result._fields_:
+        v = getattr(res, name)
+        out[name] = np.array(v[:] if isinstance(v, C.Array) else [v], dtype=np.float64)
+    out["T"] = out["T"].reshape(4, 4)
+    out["cost"][np.isposinf(out["cost"])] = -1.0
+    return out
+
+
+def dump_outputs(dirname, arrays) -> None:
+    """--dump-outputs: DIR/<name>.npy per array (a few hundred bytes in all)"""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -157,7 +188,16 @@ def main() -> None:
     ap.add_argument("--batch-pairs", type=int, default=256, help="pairs of the batch256 leg (BASELINE configs[2])")
     ap.add_argument("--sharded-pairs", type=int, default=4096, help="pair ids of the N>1 sharded leg (configs[3])")
     ap.add_argument("--batch-slots", type=int, default=32, help="stream slots of the batched legs (two lanes of half as many pairs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: roofline, stage times, repeat regions, "
+                         "the result records, the --legs, the CPU baseline and the parity against the oracle (without it a "
+                         "run sets up, warms up, times the K steps and prints the contract's line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the record the timed entry point returned for the last step "
+                         "(qtr_result: one finite float64 DIR/<field>.npy per field; cost -1 = none computed) on rank 0")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     legs = set(x for x in args.legs.split(",") if x)
     composite = args.workload == "composite"
 
@@ -241,8 +281,8 @@ def main() -> None:
     step_composite = step_composite_1 if args.composite_calls == 1 else step_composite_2
     step = step_composite if composite else step_pair
 
-    # sizes of every pool pair (one untimed registration each): needed for the per-launch FLOP accounting
-    for p in pool:
+    # sizes of every pool pair (one untimed registration each): needed for the per-launch FLOP accounting (--full)
+    for p in (pool if args.full else []):
         step_pair(p)
         p["n_src"], p["n_tgt"], p["L"], p["M"] = res.n_src, res.n_tgt, res.n_corr, res.n_clique
         p["n_hit"] = int(h.debug_fetch(ql.DBG_MATCH_STATS, np.int32)[7])  # rows the second NN direction is asked for
@@ -271,7 +311,8 @@ def main() -> None:
     # the region).  A pair costs ~5 us of queue time on either side of its launch — four such gaps, 23 us, per step —
     # so every NN_STRIDE-th step of the region carries them, not all: the region stays the product path as a caller
     # without instrumentation runs it, and the average launch duration is still measured inside it (NN_STRIDE is odd so
-    # that the timed steps rotate through the pool's pairs).
+    # that the timed steps rotate through the pool's pairs).  Only --full reads those times, but a plain run's region carries
+    # the same pairs: its ms_per_step stays like for like with --full's and with the lines of earlier rounds.
     NN_STRIDE = max(1, args.nn_event_stride)
     h.set_stage_events(False)
     h.set_nn_event_stride(NN_STRIDE)  # (also makes the region's first step a timed one)
@@ -284,8 +325,54 @@ def main() -> None:
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    last = result_arrays(res, ql)  # what the caller of the timed entry point received for the region's last step
     elapsed = qdist.max_over_ranks(elapsed, cdev)
     my_steps = max(hi - lo, 1)
+    value = world * args.steps / elapsed
+    ms_per_step = 1e3 * elapsed / args.steps
+    if composite:
+        workload = (f"composite (BASELINE configs[1]: single KITTI-64 pair, ~5k correspondences): front end + matcher of a "
+                    f"synthetic KITTI-64-shaped scan pair (quatro_amd.synth.kitti64_pair_16k, voxel 0.3 m, n ~ 16-18 k "
+                    f"per cloud) through qtr_feature_pair [voxelize x2 + FPFHManager::setFeaturePair], then "
+                    f"Quatro::computeTransformation [qtr_solve] on {LC} synthetic correspondences with 5 % planted "
+                    f"inliers (quatro_amd.synth.correspondences, SURVEY 8(d) config 2) INSTEAD of the matcher's own "
+                    f"output: FPFH on synthetic scans keeps only ~250-650 tuple-consistent correspondences for any "
+                    f"physically plausible scene (DESIGN.md section 5; tests/probe/synth_L_probe.py), so the metric's "
+                    f"'~5k corr' back end is fed from the solver-only generator; one step = " +
+                    ("ONE call, qtr_register_pair_corr (the back end is enqueued when the matcher's counters arrive and runs "
+                     "after the front end)" if args.composite_calls == 1 else "both calls, qtr_feature_pair then qtr_solve") +
+                    ", one pair at a time, inputs resident in HBM")
+    else:
+        workload = ("synthetic KITTI-64-shaped single pair (quatro_amd.synth.kitti64_pair_16k), voxel 0.3 m, whole "
+                    "path on GPU through qtr_register_pair, one registration at a time; NOTE n_corr is the matcher's "
+                    "own output (a few hundred), not the metric's ~5k")
+    brief = (f"{args.workload}: " + ("qtr_register_pair_corr" if composite and args.composite_calls == 1 else
+                                     "qtr_feature_pair + qtr_solve" if composite else "qtr_register_pair") +
+             " per step on a synthetic KITTI-64-shaped scan pair (voxel 0.3 m)" +
+             (f", back end on {LC} planted correspondences" if composite else "") +
+             ", one pair at a time, inputs resident in HBM (--full: the detailed description)")
+    out = {
+        "metric": METRIC,
+        "value": value, "unit": "registrations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 (voxel grid, FPFH, 33-D matching: f16-split MFMA filter, exact f32 decision) / f64 (consistency graph, GNC-TLS, COTE)", "data": "synthetic",
+        "config": {
+            "workload": workload if args.full else brief,  # (a plain line stays short)
+            "host_cpus": host_cpus or "unpinned",
+            "settle": {"seconds": args.settle_seconds, "untimed_registrations_before_the_warmup": k_settle},
+            "parallelism": f"pair ids [0,{world * args.steps}) block-partitioned over {world} GPU(s) ({args.steps} per rank), one "
+                           "process per GPU" + (", RCCL gather of result records" if args.full else ""),
+        },
+    }
+    if not args.full:  # the headline and nothing else: the ranks part, rank 0 writes the outputs and prints the line
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, last)
+            print(json.dumps(out), flush=True)
+        return
     nn_ms, nn_launches = h.nn_totals()
     # the contract's region is the one above; the same region four more times shows how noisy the box is (extra key)
     repeats = []
@@ -398,53 +485,23 @@ def main() -> None:
 
     p0 = pool[0]
     r0 = p0["result"]
-    value = world * args.steps / elapsed
-    ms_per_step = 1e3 * elapsed / args.steps
-    if composite:
-        workload = (f"composite (BASELINE configs[1]: single KITTI-64 pair, ~5k correspondences): front end + matcher of a "
-                    f"synthetic KITTI-64-shaped scan pair (quatro_amd.synth.kitti64_pair_16k, voxel 0.3 m, n ~ 16-18 k "
-                    f"per cloud) through qtr_feature_pair [voxelize x2 + FPFHManager::setFeaturePair], then "
-                    f"Quatro::computeTransformation [qtr_solve] on {LC} synthetic correspondences with 5 % planted "
-                    f"inliers (quatro_amd.synth.correspondences, SURVEY 8(d) config 2) INSTEAD of the matcher's own "
-                    f"output: FPFH on synthetic scans keeps only ~250-650 tuple-consistent correspondences for any "
-                    f"physically plausible scene (DESIGN.md section 5; tests/probe/synth_L_probe.py), so the metric's "
-                    f"'~5k corr' back end is fed from the solver-only generator; one step = " +
-                    ("ONE call, qtr_register_pair_corr (the back end is enqueued when the matcher's counters arrive and runs "
-                     "after the front end)" if args.composite_calls == 1 else "both calls, qtr_feature_pair then qtr_solve") +
-                    ", one pair at a time, inputs resident in HBM")
-    else:
-        workload = ("synthetic KITTI-64-shaped single pair (quatro_amd.synth.kitti64_pair_16k), voxel 0.3 m, whole "
-                    "path on GPU through qtr_register_pair, one registration at a time; NOTE n_corr is the matcher's "
-                    "own output (a few hundred), not the metric's ~5k")
-    out = {
-        "metric": METRIC,
-        "value": value, "unit": "registrations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32 (voxel grid, FPFH, 33-D matching: f16-split MFMA filter, exact f32 decision) / f64 (consistency graph, GNC-TLS, COTE)", "data": "synthetic",
-        "config": {
-            "workload": workload,
-            "raw_points": [int(p0["src_h"].shape[0]), int(p0["tgt_h"].shape[0])],
-            "n_src": int(p0["n_src"]), "n_tgt": int(p0["n_tgt"]), "n_corr": int(LC if composite else p0["L"]),
-            "n_corr_matcher": int(p0["L"]),
-            "n_clique": int(r0["clique"].size), "n_final_inliers": int(r0["final_inliers"].size),
-            "pool": [{"id": p["id"], "n_src": int(p["n_src"]), "n_tgt": int(p["n_tgt"]),
-                      "n_corr": int(LC if composite else p["L"]), "n_corr_matcher": int(p["L"]), "n_hit": int(p["n_hit"]),
-                      "n_clique": int(p["result"]["clique"].size)}
-                     for p in pool],
-            "host_cpus": host_cpus or "unpinned",
-            "settle": {"seconds": args.settle_seconds, "untimed_registrations_before_the_warmup": k_settle},
-            "records_gathered": 0 if gathered is None else int(gathered.shape[0]),
-            "parallelism": f"pair ids [0,{world * args.steps}) block-partitioned over {world} GPU(s) ({args.steps} per rank), one "
-                           "process per GPU, RCCL "
-                           "gather of result records",
-        },
-        "stage_ms": {k: round(v / max(stage_n, 1), 4) for k, v in stage_acc.items() if k not in ("nn_launches",)},
-        "repeat_regions": {"what": "the timed region run four more times after the contract's one (same steps, same barriers)",
-                           "ms_per_step": [round(1e3 * r / args.steps, 5) for r in repeats],
-                           "min": round(1e3 * min(repeats) / args.steps, 5),
-                           "median": round(1e3 * float(np.median(repeats)) / args.steps, 5),
-                           "max": round(1e3 * max(repeats) / args.steps, 5)},
-    }
+    out["config"].update({
+        "raw_points": [int(p0["src_h"].shape[0]), int(p0["tgt_h"].shape[0])],
+        "n_src": int(p0["n_src"]), "n_tgt": int(p0["n_tgt"]), "n_corr": int(LC if composite else p0["L"]),
+        "n_corr_matcher": int(p0["L"]),
+        "n_clique": int(r0["clique"].size), "n_final_inliers": int(r0["final_inliers"].size),
+        "pool": [{"id": p["id"], "n_src": int(p["n_src"]), "n_tgt": int(p["n_tgt"]),
+                  "n_corr": int(LC if composite else p["L"]), "n_corr_matcher": int(p["L"]), "n_hit": int(p["n_hit"]),
+                  "n_clique": int(p["result"]["clique"].size)}
+                 for p in pool],
+        "records_gathered": 0 if gathered is None else int(gathered.shape[0]),
+    })
+    out["stage_ms"] = {k: round(v / max(stage_n, 1), 4) for k, v in stage_acc.items() if k not in ("nn_launches",)}
+    out["repeat_regions"] = {"what": "the timed region run four more times after the contract's one (same steps, same barriers)",
+                             "ms_per_step": [round(1e3 * r / args.steps, 5) for r in repeats],
+                             "min": round(1e3 * min(repeats) / args.steps, 5),
+                             "median": round(1e3 * float(np.median(repeats)) / args.steps, 5),
+                             "max": round(1e3 * max(repeats) / args.steps, 5)}
     out.update(extra)
     if seg is not None:
         out["segment_cloud_leg"] = seg
@@ -546,6 +603,8 @@ def main() -> None:
             **brief("l5k"))
         if "l5k_dense18k" in cl:
             out["connected_l5k"]["dense18k"] = brief("l5k_dense18k")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
     print(json.dumps(out), flush=True)
     if hung:
         os._exit(0)

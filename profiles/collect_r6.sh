@@ -15,12 +15,14 @@ TAG=${1:-r6}
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG
 mkdir -p $O
-timeout 900 python -m pytest $R/tests -q -m gpu > $O/gpu_tests_full.txt 2>&1; grep -E "passed|failed" $O/gpu_tests_full.txt | tail -1 > $O/gpu_tests.txt
-python $R/bench.py --steps 40 --warmup 5 > $O/bench.json 2> $O/bench.err
+# every GPU step runs under its own time limit, and the first one that does not exit cleanly ends the script
+timeout -k 10 900 python -m pytest $R/tests -q -m gpu > $O/gpu_tests_full.txt 2>&1; rc=$?
+grep -E "passed|failed" $O/gpu_tests_full.txt | tail -1 > $O/gpu_tests.txt; [ $rc -eq 0 ] || exit $rc
+timeout -k 10 900 python $R/bench.py --full --steps 40 --warmup 5 > $O/bench.json 2> $O/bench.err || exit $?
 cd /tmp
-prof() { tag=$1; shift; timeout 300 rocprofv3 --kernel-trace --stats -d $O/prof_$tag -o $tag -- "$@" > $O/run_$tag.txt 2>&1; }
+prof() { tag=$1; shift; timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$tag -o $tag -- "$@" > $O/run_$tag.txt 2>&1 || exit $?; }
 prof seq python $R/bench.py --steps 40 --warmup 5 --legs "" --cpu-seconds 0
-prof batch python $R/bench.py --steps 2 --warmup 1 --legs batch --cpu-seconds 0
+prof batch python $R/bench.py --full --steps 2 --warmup 1 --legs batch --cpu-seconds 0
 prof s5k python $R/tests/gpu_solver_prof.py 5000 20
 prof s20k python $R/tests/gpu_solver_prof.py 20000 6
 prof dstep python $R/tests/gpu_dense_step_prof.py 6
@@ -38,11 +40,13 @@ python profiles/summarize_rocpd.py $(db conn) > $O/conn20k_kernel_stats.txt
 python profiles/summarize_rocpd.py $(db l5k) > $O/l5k_kernel_stats.txt
 grep "ms per" $O/run_l5k.txt >> $O/l5k_kernel_stats.txt
 rm -rf $O/prof_*
-bash profiles/pmc_all.sh $TAG seq > $O/pmc_seq.log 2>&1
-bash profiles/pmc_all.sh $TAG batch > $O/pmc_batch.log 2>&1
-bash profiles/pmc_all.sh $TAG dense > $O/pmc_dense.log 2>&1
+bash profiles/pmc_all.sh $TAG seq > $O/pmc_seq.log 2>&1 || exit $?
+bash profiles/pmc_all.sh $TAG batch > $O/pmc_batch.log 2>&1 || exit $?
+bash profiles/pmc_all.sh $TAG dense > $O/pmc_dense.log 2>&1 || exit $?
 bash profiles/pmc_mfma.sh $TAG > $O/mfma.log 2>&1; cp $R/gpurun_out/${TAG}_mfma.txt $O/mfma.txt 2>/dev/null
-[ -f $R/quatro_amd/libquatro_hip_timing.so ] && timeout 120 python tests/probe/nn_stamps.py > $O/kernel_stamps.txt 2>&1
-[ -f $R/quatro_amd/libquatro_hip_timing.so ] && timeout 120 python tests/probe/recheck_stamps.py > $O/recheck_stamps.txt 2>&1
+if [ -f $R/quatro_amd/libquatro_hip_timing.so ]; then
+  timeout -k 10 120 python tests/probe/nn_stamps.py > $O/kernel_stamps.txt 2>&1 || exit $?
+  timeout -k 10 120 python tests/probe/recheck_stamps.py > $O/recheck_stamps.txt 2>&1 || exit $?
+fi
 rm -f $O/run_*.txt
 ls -la $O

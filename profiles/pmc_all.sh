@@ -4,7 +4,7 @@
 # beside them.   gpurun -- 'bash profiles/pmc_all.sh TAG WORKLOAD'   ->   gpurun_out/TAG/pmc_WORKLOAD.json
 #   WORKLOAD  seq    the headline loop (bench.py --legs "")
 #             dense  BASELINE configs[4] as one registration + the dense scene's own correspondences (tests/gpu_dense_step_prof.py)
-#             batch  256 composite pairs through the batched entry points (bench.py --legs batch)
+#             batch  256 composite pairs through the batched entry points (bench.py --full --legs batch)
 #             s5k / s20k   the back end alone at L = 5000 / 20000 (tests/gpu_solver_prof.py)
 TAG=${1:-r6}
 WL=${2:-seq}
@@ -14,16 +14,17 @@ mkdir -p $O
 case $WL in
   seq)   CMD="python $R/bench.py --steps 8 --warmup 2 --legs  --cpu-seconds 0";;
   dense) CMD="python $R/tests/gpu_dense_step_prof.py 4";;
-  batch) CMD="python $R/bench.py --steps 2 --warmup 1 --legs batch --cpu-seconds 0";;
+  batch) CMD="python $R/bench.py --full --steps 2 --warmup 1 --legs batch --cpu-seconds 0";;
   s5k)   CMD="python $R/tests/gpu_solver_prof.py 5000 12";;
   s20k)  CMD="python $R/tests/gpu_solver_prof.py 20000 4";;
   *) echo "unknown workload $WL"; exit 2;;
 esac
 cd /tmp
-run() { tag=$1; shift; timeout 300 rocprofv3 --kernel-trace "$@" -d $O/prof_${WL}_$tag -o $tag -- $CMD > $O/run_${WL}_$tag.txt 2>&1; }
+# (each pass under its own time limit; the first that does not exit cleanly ends the script)
+run() { tag=$1; shift; timeout -k 10 300 rocprofv3 --kernel-trace "$@" -d $O/prof_${WL}_$tag -o $tag -- $CMD > $O/run_${WL}_$tag.txt 2>&1 || exit $?; }
 if [ "$WL" = seq ]; then
   # (an empty --legs argument has to survive word splitting)
-  run() { tag=$1; shift; timeout 300 rocprofv3 --kernel-trace "$@" -d $O/prof_${WL}_$tag -o $tag -- python $R/bench.py --steps 8 --warmup 2 --legs "" --cpu-seconds 0 > $O/run_${WL}_$tag.txt 2>&1; }
+  run() { tag=$1; shift; timeout -k 10 300 rocprofv3 --kernel-trace "$@" -d $O/prof_${WL}_$tag -o $tag -- python $R/bench.py --steps 8 --warmup 2 --legs "" --cpu-seconds 0 > $O/run_${WL}_$tag.txt 2>&1 || exit $?; }
 fi
 run clean
 run a --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS

@@ -5,6 +5,11 @@ and its other stages cannot run here — see oracle/quatro_oracle.cpp header).  
 accidental drift and give the GPU tests inputs/outputs that do not depend on the oracle being rebuilt.
 
     python tests/golden/make_golden.py
+
+ref_live_matcher.npz / ref_live_solver.npz (the compiled reference's answers to the seeded calls of the `live` tests of
+tests/test_ref_cpu.py, replayed where it cannot be compiled) are written by those tests themselves:
+
+    QTR_REF_LIVE_WRITE=1 python -m pytest tests/test_ref_cpu.py -k live
 """
 import os
 import sys

@@ -153,7 +153,7 @@ def test_bench_line_of_a_four_rank_launch_as_the_driver_starts_it(tmp_path):
                MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "4", "--warmup", "1",
-           "--legs", "batch", "--cpu-seconds", "2", "--sharded-pairs", "96", "--batch-slots", "8"]
+           "--full", "--legs", "batch", "--cpu-seconds", "2", "--sharded-pairs", "96", "--batch-slots", "8"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

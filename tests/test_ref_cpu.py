@@ -1,12 +1,15 @@
 """Anchors of the CPU oracle that the repository's own code did not produce.
 
-* the REFERENCE's teaser::Matcher, compiled from /root/reference (oracle/Makefile target `ref`): live comparison when
-  oracle/_ref/libref_matcher.so is present, and the committed outputs it generated (tests/golden/matcher_ref.npz);
+* the REFERENCE's teaser::Matcher, compiled from the reference's own text (oracle/Makefile target `ref`): live comparison
+  when oracle/_ref/libref_matcher.so is present, and the committed outputs it generated (tests/golden/matcher_ref.npz);
 * the REFERENCE's Eigen-only back-end functions (computeTIMs, solveForScale, solveForRotation2D, solveForTranslation,
   estimate of include/quatro.hpp; target `ref_solver`): live, and their committed outputs (tests/golden/solver_ref.npz);
+* the "live" tests' seeded calls replay the answers the compiled reference gave to them (tests/golden/ref_live_*.npz)
+  where it cannot be compiled, and check those stored answers against it where it can;
 * library cross-checks of the third-party semantics the oracle restates: scipy's cKDTree for the radius sets,
   numpy's eigh for pcl::eigen33, and a known answer of the published FPFH definition (Rusu 2009) on a plane.
 """
+import hashlib
 import os
 
 import numpy as np
@@ -23,6 +26,76 @@ def qo():
     o.build()
     o.set_threads(min(4, o.max_threads()))
     return o
+
+
+class _Ref:
+    """The compiled reference's functions (qo.ref_*) when it is there — each answer also checked against the one stored
+    for the same call — else the stored answers, in call order: tests/golden/ref_live_<tag>.npz, written by these tests
+    with QTR_REF_LIVE_WRITE=1 where the reference can be compiled.  Each answer is stored with a digest of the call's
+    arguments, so that inputs which changed since the recording (synth, the tests' draws) fail as such, in both modes,
+    rather than as a disagreement of oracle and reference.  `extra` adds test-local compositions of them."""
+
+    def __init__(self, qo, tag, available, **extra):
+        self.qo, self.live, self.extra, self.k = qo, available, extra, 0
+        self.path = os.path.join(G, f"ref_live_{tag}.npz")
+        self.stored = dict(np.load(self.path)) if os.path.exists(self.path) else None
+        self.new = {}
+        if not available and self.stored is None:
+            pytest.fail(f"{self.path} is missing and the reference is not compiled "
+                        "(QTR_REF_LIVE_WRITE=1: tests/golden/make_golden.py)")
+
+    def __getattr__(self, name):
+        def call(*a, **kw):
+            key = f"{name}.{self.k}"
+            self.k += 1
+            digest = _digest(a, kw)
+            if self.stored is not None and not (self.live and os.environ.get("QTR_REF_LIVE_WRITE")):
+                if str(self.stored.get(key + ":args", "")) != digest:
+                    pytest.fail(f"the arguments of call {key} are not those its stored answer in {self.path} was recorded "
+                                "for: the inputs changed, record the file again (tests/golden/make_golden.py)")
+            if not self.live:
+                return _unflat(self.stored, key)
+            r = (self.extra[name] if name in self.extra else getattr(self.qo, name))(*a, **kw)
+            self.new.update(_flat(key, r))
+            self.new[key + ":args"] = np.array(digest)
+            if self.stored is not None and not os.environ.get("QTR_REF_LIVE_WRITE"):
+                for k, v in _flat(key, r).items():
+                    assert k in self.stored and np.array_equal(self.stored[k], v), ("stored answer differs", k)
+            return r
+        return call
+
+    def save(self):
+        if self.live and os.environ.get("QTR_REF_LIVE_WRITE"):
+            np.savez_compressed(self.path, **self.new)
+
+
+def _digest(args, kw):
+    """sha256 of a call's arguments: arrays and numpy scalars by dtype, shape and bytes, Python values by repr"""
+    hh = hashlib.sha256()
+    for v in list(args) + [x for k in sorted(kw) for x in (k, kw[k])]:
+        if isinstance(v, (np.ndarray, np.generic)):
+            v = np.ascontiguousarray(v)
+            hh.update(repr((v.dtype.str, v.shape)).encode())
+            hh.update(v.tobytes())
+        else:
+            hh.update(repr(v).encode())
+        hh.update(b"|")
+    return hh.hexdigest()
+
+
+def _flat(key, r):
+    items = r.items() if isinstance(r, dict) else enumerate(r if isinstance(r, tuple) else (r,))
+    kind = "dict" if isinstance(r, dict) else "tuple" if isinstance(r, tuple) else "one"
+    return {key: np.array(kind), **{f"{key}.{k}": np.asarray(v) for k, v in items}}
+
+
+def _unflat(stored, key):
+    kind = str(stored[key])
+    vals = {k[len(key) + 1:]: (v.item() if v.ndim == 0 else v) for k, v in stored.items() if k.startswith(key + ".")}
+    if kind == "dict":
+        return vals
+    out = tuple(vals[str(i)] for i in range(len(vals)))
+    return out if kind == "tuple" else out[0]
 
 
 CASES = {"ab": ("a", "b", True, True, 11), "ba": ("b", "a", True, True, 12), "ab_nocross": ("a", "b", False, True, 13),
@@ -44,8 +117,7 @@ def test_oracle_matcher_equals_reference_generated_golden(qo, name):
 def test_oracle_matcher_equals_compiled_reference_live(qo):
     """The same comparison against the compiled reference itself, on inputs with exact ties (duplicated descriptors),
     clouds of very different size and the degenerate single-point cloud."""
-    if not (qo.build_ref() and qo.ref_available()):
-        pytest.skip("oracle/_ref/libref_matcher.so is not available (no /root/reference, no prebuilt file)")
+    ref = _Ref(qo, "matcher", bool(qo.build_ref() and qo.ref_available()))
     rng = np.random.default_rng(3)
     for trial in range(6):
         na, nb = int(rng.integers(1, 700)), int(rng.integers(1, 700))
@@ -59,15 +131,16 @@ def test_oracle_matcher_equals_compiled_reference_live(qo):
             db[nb // 2] = db[nb - 1]
         for cross in (True, False):
             for tup in (True, False):
-                ref = qo.ref_match(xa, da, xb, db, crosscheck=cross, tuple_test=tup, seed=trial)
+                want = ref.ref_match(xa, da, xb, db, crosscheck=cross, tuple_test=tup, seed=trial)
                 got = qo.match(xa, da, xb, db, crosscheck=cross, tuple_test=tup, seed=trial)
-                assert np.array_equal(ref, got), (trial, na, nb, cross, tup)
+                assert np.array_equal(want, got), (trial, na, nb, cross, tup)
     s, t, _ = synth.kitti64_pair(5)
     vs, vt = qo.voxelize(s, 0.45), qo.voxelize(t, 0.45)
     _, _, ds = qo.fpfh(vs, 0.7, 1.0)
     _, _, dt = qo.fpfh(vt, 0.7, 1.0)
     for (a, da, b, db, seed) in ((vs, ds, vt, dt, 1), (vt, dt, vs, ds, 2)):
-        assert np.array_equal(qo.ref_match(a, da, b, db, seed=seed), qo.match(a, da, b, db, seed=seed))
+        assert np.array_equal(ref.ref_match(a, da, b, db, seed=seed), qo.match(a, da, b, db, seed=seed))
+    ref.save()
 
 
 def _graph_from_reference_mask(L, mp, mask):
@@ -140,15 +213,16 @@ def test_oracle_solve_equals_reference_compute_transformation_golden(qo):
 
 def test_oracle_back_end_equals_compiled_reference_live(qo):
     """The same comparisons against the compiled reference functions themselves, on fresh random inputs."""
-    if not (qo.build_ref_solver() and qo.ref_solver_available()):
-        pytest.skip("oracle/_ref/libref_solver.so is not available (no /root/reference, no prebuilt file)")
+    def ref_graph(src, tgt, nb, cbar2):  # computeTIMs of both clouds, then solveForScale's mask: (index map, mask)
+        ts, mp = qo.ref_compute_tims(src[:, :3].astype(np.float64))
+        tt, _ = qo.ref_compute_tims(tgt[:, :3].astype(np.float64))
+        return mp, qo.ref_scale_mask(ts, tt, nb, cbar2)
+    ref = _Ref(qo, "solver", bool(qo.build_ref_solver() and qo.ref_solver_available()), ref_graph=ref_graph)
     g = np.random.default_rng(77)
     for L in (2, 3, 40, 260):
         src, tgt, _, _ = synth.correspondences(L, 0.3, seed=100 + L, noise=0.05)
         for nb, cbar2 in ((0.3, 1.0), (0.1, 2.0)):
-            ts, mp = qo.ref_compute_tims(src[:, :3].astype(np.float64))
-            tt, _ = qo.ref_compute_tims(tgt[:, :3].astype(np.float64))
-            mask = qo.ref_scale_mask(ts, tt, nb, cbar2)
+            mp, mask = ref.ref_graph(src, tgt, nb, cbar2)
             assert np.array_equal(_oracle_adjacency(qo, src, tgt, nb, cbar2), _graph_from_reference_mask(L, mp, mask)), (L, nb)
     for trial in range(12):
         M = int(g.integers(3, 500))
@@ -158,7 +232,7 @@ def test_oracle_back_end_equals_compiled_reference_live(qo):
         b = a @ Rt.T + g.normal(0, g.choice([0.0, 0.02, 0.2]), (M, 2))
         bad = g.random(M) > g.choice([0.2, 0.6, 1.0])
         b[bad] = g.normal(0, 5, (int(bad.sum()), 2))
-        Rr, cr, ir = qo.ref_gnc_rotation2d(a, b)
+        Rr, cr, ir = ref.ref_gnc_rotation2d(a, b)
         Ro, co, _, io = qo.gnc_rotation2d(a, b, qo.REF_GNC_NOISE_BOUND)
         assert np.array_equal(io, ir), trial
         assert np.abs(Ro - Rr).max() < 1e-11, trial
@@ -170,7 +244,7 @@ def test_oracle_back_end_equals_compiled_reference_live(qo):
             X[:max(2, N // 2)] = g.normal(0.5, 0.05, max(2, N // 2))
         ranges = g.uniform(0.05, 0.6, N) if trial % 2 else np.full(N, float(g.choice([0.1, 0.3, 0.6])))
         for median in (True, False):
-            er, mr = qo.ref_cote_estimate(X, ranges, median)
+            er, mr = ref.ref_cote_estimate(X, ranges, median)
             eo, mo, nc = qo.cote_estimate_ranges(X, ranges, median)
             if median and nc < 2:
                 continue  # the reference reads past its candidate list for a consensus set of one (declared divergence D4)
@@ -181,9 +255,9 @@ def test_oracle_back_end_equals_compiled_reference_live(qo):
                                                noise=float(g.choice([0.0, 0.05, 0.2])))
         kw = [{}, {"cote_median": 0}, {"using_rot_inliers_when_estimating_cote": 1}, {"inlier_selection_mode": 2}][trial % 4]
         o = qo.solve(src, tgt, qo.default_params(**kw))
-        r = qo.ref_compute_transformation(src, tgt, cote_median=bool(kw.get("cote_median", 1)),
-                                          use_rot_inliers=bool(kw.get("using_rot_inliers_when_estimating_cote", 0)),
-                                          inlier_selection_mode=kw.get("inlier_selection_mode", 1))
+        r = ref.ref_compute_transformation(src, tgt, cote_median=bool(kw.get("cote_median", 1)),
+                                           use_rot_inliers=bool(kw.get("using_rot_inliers_when_estimating_cote", 0)),
+                                           inlier_selection_mode=kw.get("inlier_selection_mode", 1))
         assert o["valid"] == r["valid"], (trial, L)
         if o["valid"] and kw.get("cote_median", 1) and min(o["n_card"]) < 2:
             continue  # a consensus set of one: the reference reads candidates[-1] (declared divergence D4)
@@ -203,7 +277,8 @@ def test_oracle_back_end_equals_compiled_reference_live(qo):
         V = Vt.T
         if np.linalg.det(U) * np.linalg.det(V) < 0:
             V[:, -1] *= -1
-        assert np.abs(qo.ref_svd_rot(X, Y, W) - V @ U.T).max() < 1e-12
+        assert np.abs(ref.ref_svd_rot(X, Y, W) - V @ U.T).max() < 1e-12
+    ref.save()
 
 
 def test_radius_sets_against_scipy_ckdtree(qo):
