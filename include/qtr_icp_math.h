@@ -1,0 +1,294 @@
+// qtr_icp_math.h — the arithmetic of one ICP iteration, shared by the gfx950 kernel (quatro_amd/csrc/icp.hip) and the
+// host restatement of the tests (g++), in the style of qtr_math.h: binary64 + - * / sqrt only, evaluated in the order
+// written (both sides compile with -ffp-contract=off), so host and device agree bit for bit.
+//
+// One iteration, given the current transform T (row-major 4x4, maps source into target):
+//   q = R p + t                       per source point, binary64 from the float32 input (qtr_icp_transform)
+//   nearest target point, d^2 <= max_d^2 in binary64 (qtr_icp_d2), ties to the lowest target index
+//   per-correspondence terms          qtr_icp_terms: QTR_ICP_NT doubles (zero for a point without correspondence)
+//   fixed-shape sum                   qtr_icp_fold64 inside every 64-point wave, (w0 + w1) + (w2 + w3) inside every
+//                                     256-point chunk, then the chunks in ascending order (qtr_icp_chunk_sum)
+//   update and stopping               qtr_icp_step
+#pragma once
+#include "qtr_math.h"
+
+#define QTR_ICP_CHUNK 256  // source points per workgroup / partial sum
+#define QTR_ICP_NT 32      // terms per point (30 used, padded)
+
+// term layout.  Point-to-plane: 21 upper entries of J^T J (row-major upper triangle), 6 of J^T r, sum r^2.
+// Point-to-point: sum q t^T (9, row-major: [3a+b] = q_a t_b), sum q (3), sum t (3).  Both: sum d^2, count.
+#define QTR_ICP_T_JTR 21
+#define QTR_ICP_T_R2 27
+#define QTR_ICP_T_QT 0
+#define QTR_ICP_T_SQ 9
+#define QTR_ICP_T_ST 12
+#define QTR_ICP_T_D2 28
+#define QTR_ICP_T_CNT 29
+
+// stop reasons (qtr_icp_result.stop_reason; the same values as include/quatro_hip.h)
+#define QTR_ICP_RUNNING 0
+#define QTR_ICP_STOP_MAX_ITERATIONS 1
+#define QTR_ICP_STOP_TRANSFORMATION 2
+#define QTR_ICP_STOP_FITNESS 3
+#define QTR_ICP_STOP_TOO_FEW 4
+#define QTR_ICP_STOP_DEGENERATE 5
+
+// a pivot of the 6x6 LDL^T at or below this fraction of its own diagonal entry is a rank deficiency (a plane leaves
+// three of the six directions unconstrained: their pivots are rounding noise, ~1e-16 of the diagonal)
+#define QTR_ICP_PIVOT_REL 1e-12
+
+typedef struct QtrIcpCfg {
+  double max_d2;        // max_correspondence_distance^2
+  double trans_eps;     // transformation_epsilon
+  double fit_eps;       // euclidean_fitness_epsilon
+  int max_iterations;
+  int method;           // 0 point-to-plane, 1 point-to-point
+  int min_corr;
+  int pad;
+} QtrIcpCfg;
+
+typedef struct QtrIcpState {
+  double T[16];         // current transform (the last good one once stopped)
+  double prev_mse;      // MSE of the previous iteration's correspondences (< 0: none yet)
+  double fitness;       // MSE (mean d^2) of the last evaluated correspondence set
+  double rmse;          // sqrt(mean of the minimised residual^2) of that set
+  int iterations;       // updates applied
+  int stop;             // 1: stopped (later launches return at once)
+  int reason;           // QTR_ICP_STOP_*
+  int n_corr;           // correspondences of the last evaluated set
+  int valid, converged;
+  int pad[2];
+} QtrIcpState;
+
+QM_HD void qtr_icp_transform(const double* T, float px, float py, float pz, double* q) {
+  const double x = (double)px, y = (double)py, z = (double)pz;
+  q[0] = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+  q[1] = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+  q[2] = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+}
+
+QM_HD double qtr_icp_d2(const double* q, float tx, float ty, float tz) {
+  const double dx = q[0] - (double)tx, dy = q[1] - (double)ty, dz = q[2] - (double)tz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+QM_HD bool qtr_icp_finite3(float x, float y, float z) {
+  // (x - x is NaN for inf and NaN alike; no library call)
+  return (x - x) == 0.0f && (y - y) == 0.0f && (z - z) == 0.0f;
+}
+
+// the terms of one correspondence q <-> (t, n); d2 = qtr_icp_d2(q, t)
+QM_HD void qtr_icp_terms(int method, const double* q, float tx, float ty, float tz, float nx, float ny, float nz, double d2,
+                         double* o /* [QTR_ICP_NT] */) {
+  for (int k = 0; k < QTR_ICP_NT; ++k) o[k] = 0.0;
+  const double t0 = (double)tx, t1 = (double)ty, t2 = (double)tz;
+  if (method == 0) {
+    const double n0 = (double)nx, n1 = (double)ny, n2 = (double)nz;
+    const double r = ((q[0] - t0) * n0 + (q[1] - t1) * n1) + (q[2] - t2) * n2;
+    double J[6];
+    J[0] = q[1] * n2 - q[2] * n1;  // q x n
+    J[1] = q[2] * n0 - q[0] * n2;
+    J[2] = q[0] * n1 - q[1] * n0;
+    J[3] = n0;
+    J[4] = n1;
+    J[5] = n2;
+    int k = 0;
+    for (int a = 0; a < 6; ++a)
+      for (int b = a; b < 6; ++b) o[k++] = J[a] * J[b];
+    for (int a = 0; a < 6; ++a) o[QTR_ICP_T_JTR + a] = J[a] * r;
+    o[QTR_ICP_T_R2] = r * r;
+  } else {
+    const double t[3] = {t0, t1, t2};
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) o[QTR_ICP_T_QT + 3 * a + b] = q[a] * t[b];
+    for (int a = 0; a < 3; ++a) {
+      o[QTR_ICP_T_SQ + a] = q[a];
+      o[QTR_ICP_T_ST + a] = t[a];
+    }
+  }
+  o[QTR_ICP_T_D2] = d2;
+  o[QTR_ICP_T_CNT] = 1.0;
+}
+
+// the in-wave fold of 64 values: for off = 32, 16, ..., 1: p[l] += p[l + off] (l < off) — what __shfl_down does
+QM_HD double qtr_icp_fold64(double* p /* [64], clobbered */) {
+  for (int off = 32; off >= 1; off >>= 1)
+    for (int l = 0; l < off; ++l) p[l] = p[l] + p[l + off];
+  return p[0];
+}
+QM_HD double qtr_icp_chunk_sum(const double* w /* [4] wave sums */) { return (w[0] + w[1]) + (w[2] + w[3]); }
+
+// Solves A x = b for the symmetric 6x6 A given by its 21 upper entries (row-major upper triangle), LDL^T with a fixed
+// loop order.  Returns false on a pivot that is not clearly positive (degenerate scene).
+QM_HD bool qtr_icp_solve6(const double* U21, const double* b, double* x) {
+  double A[6][6];
+  int k = 0;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) {
+      A[i][j] = U21[k];
+      A[j][i] = U21[k];
+      ++k;
+    }
+  double L[6][6], D[6];
+  for (int i = 0; i < 6; ++i)
+    for (int j = 0; j < 6; ++j) L[i][j] = (i == j) ? 1.0 : 0.0;
+  for (int j = 0; j < 6; ++j) {
+    double d = A[j][j];
+    for (int m = 0; m < j; ++m) d = d - (L[j][m] * L[j][m]) * D[m];
+    if (!(d > QTR_ICP_PIVOT_REL * A[j][j])) return false;  // (also false for NaN)
+    D[j] = d;
+    for (int i = j + 1; i < 6; ++i) {
+      double s = A[i][j];
+      for (int m = 0; m < j; ++m) s = s - (L[i][m] * L[j][m]) * D[m];
+      L[i][j] = s / d;
+    }
+  }
+  double y[6];
+  for (int i = 0; i < 6; ++i) {
+    double s = b[i];
+    for (int m = 0; m < i; ++m) s = s - L[i][m] * y[m];
+    y[i] = s;
+  }
+  for (int i = 5; i >= 0; --i) {
+    double s = y[i] / D[i];
+    for (int m = i + 1; m < 6; ++m) s = s - L[m][i] * x[m];
+    x[i] = s;
+  }
+  return true;
+}
+
+// rotation of the unit quaternion (1, w/2) / |(1, w/2)|: the small-angle increment without sin / cos
+QM_HD void qtr_icp_rot_from_omega(const double* w, double* R /* row-major 3x3 */) {
+  double q0 = 1.0, q1 = 0.5 * w[0], q2 = 0.5 * w[1], q3 = 0.5 * w[2];
+  const double nq = sqrt((q0 * q0 + q1 * q1) + (q2 * q2 + q3 * q3));
+  q0 = q0 / nq;
+  q1 = q1 / nq;
+  q2 = q2 / nq;
+  q3 = q3 / nq;
+  R[0] = ((q0 * q0 + q1 * q1) - q2 * q2) - q3 * q3;
+  R[1] = 2.0 * (q1 * q2 - q0 * q3);
+  R[2] = 2.0 * (q1 * q3 + q0 * q2);
+  R[3] = 2.0 * (q1 * q2 + q0 * q3);
+  R[4] = ((q0 * q0 - q1 * q1) + q2 * q2) - q3 * q3;
+  R[5] = 2.0 * (q2 * q3 - q0 * q1);
+  R[6] = 2.0 * (q1 * q3 - q0 * q2);
+  R[7] = 2.0 * (q2 * q3 + q0 * q1);
+  R[8] = ((q0 * q0 - q1 * q1) - q2 * q2) + q3 * q3;
+}
+
+// T <- [dR dt; 0 1] T
+QM_HD void qtr_icp_compose(const double* dR, const double* dt, double* T) {
+  double N[12];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 4; ++c) N[4 * r + c] = (dR[3 * r] * T[c] + dR[3 * r + 1] * T[4 + c]) + dR[3 * r + 2] * T[8 + c];
+    N[4 * r + 3] = N[4 * r + 3] + dt[r];
+  }
+  for (int k = 0; k < 12; ++k) T[k] = N[k];
+  T[12] = 0.0;
+  T[13] = 0.0;
+  T[14] = 0.0;
+  T[15] = 1.0;
+}
+
+QM_HD void qtr_icp_init(QtrIcpState* st, const double* guess) {
+  for (int k = 0; k < 16; ++k) st->T[k] = guess[k];
+  st->prev_mse = -1.0;
+  st->fitness = 1.7976931348623157e308;  // (pcl getFitnessScore without correspondences: DBL_MAX)
+  st->rmse = 0.0;
+  st->iterations = 0;
+  st->stop = 0;
+  st->reason = QTR_ICP_RUNNING;
+  st->n_corr = 0;
+  st->valid = 0;
+  st->converged = 0;
+  st->pad[0] = st->pad[1] = 0;
+}
+
+// The update of one iteration from the summed terms S: solve, compose, decide whether to stop.  trace (may be null)
+// receives [T after the update (16), MSE, count] when an update was applied.
+QM_HD void qtr_icp_step(const QtrIcpCfg* cfg, const double* S, QtrIcpState* st, double* trace /* [18] or null */) {
+  const double n = S[QTR_ICP_T_CNT];
+  st->n_corr = (int)n;
+  if (n < (double)cfg->min_corr || !(n > 0.0)) {  // too few correspondences: T stays at the last good value
+    if (n > 0.0) st->fitness = S[QTR_ICP_T_D2] / n;
+    st->stop = 1;
+    st->reason = QTR_ICP_STOP_TOO_FEW;
+    st->valid = 0;
+    st->converged = 0;
+    return;
+  }
+  const double mse = S[QTR_ICP_T_D2] / n;
+  st->fitness = mse;
+  double dR[9], dt[3];
+  if (cfg->method == 0) {
+    st->rmse = sqrt(S[QTR_ICP_T_R2] / n);
+    double b[6], x[6];
+    for (int a = 0; a < 6; ++a) b[a] = -S[QTR_ICP_T_JTR + a];
+    if (!qtr_icp_solve6(S, b, x)) {
+      st->stop = 1;
+      st->reason = QTR_ICP_STOP_DEGENERATE;
+      st->valid = 0;
+      st->converged = 0;
+      return;
+    }
+    qtr_icp_rot_from_omega(x, dR);
+    dt[0] = x[3];
+    dt[1] = x[4];
+    dt[2] = x[5];
+  } else {
+    st->rmse = sqrt(mse);
+    double ms[3], mt[3], H[9];
+    for (int a = 0; a < 3; ++a) {
+      ms[a] = S[QTR_ICP_T_SQ + a] / n;
+      mt[a] = S[QTR_ICP_T_ST + a] / n;
+    }
+    for (int a = 0; a < 3; ++a)
+      for (int c = 0; c < 3; ++c) H[3 * a + c] = S[QTR_ICP_T_QT + 3 * a + c] - (S[QTR_ICP_T_SQ + a] * mt[c]);
+    // a cross-covariance of rank < 2 leaves the rotation undetermined (collinear points): degenerate like a plane is
+    // for point-to-plane.  H's scale: its trace of squares against the spread of the source points
+    double spread = 0.0;
+    for (int a = 0; a < 9; ++a) spread = spread + H[a] * H[a];
+    if (!(spread > 0.0)) {
+      st->stop = 1;
+      st->reason = QTR_ICP_STOP_DEGENERATE;
+      st->valid = 0;
+      st->converged = 0;
+      return;
+    }
+    qm_rot3_from_h(H, dR);
+    for (int a = 0; a < 3; ++a) dt[a] = mt[a] - ((dR[3 * a] * ms[0] + dR[3 * a + 1] * ms[1]) + dR[3 * a + 2] * ms[2]);
+  }
+  qtr_icp_compose(dR, dt, st->T);
+  st->iterations = st->iterations + 1;
+  st->valid = 1;
+  if (trace) {
+    for (int k = 0; k < 16; ++k) trace[k] = st->T[k];
+    trace[16] = mse;
+    trace[17] = n;
+  }
+  // max |dT - I| over the 3x4 block
+  double dmax = 0.0;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) {
+      const double e = dR[3 * r + c] - (r == c ? 1.0 : 0.0);
+      const double ae = e < 0 ? -e : e;
+      dmax = ae > dmax ? ae : dmax;
+    }
+    const double ae = dt[r] < 0 ? -dt[r] : dt[r];
+    dmax = ae > dmax ? ae : dmax;
+  }
+  const double prev = st->prev_mse;
+  st->prev_mse = mse;
+  if (st->iterations >= cfg->max_iterations) {
+    st->reason = QTR_ICP_STOP_MAX_ITERATIONS;
+  } else if (dmax <= cfg->trans_eps) {
+    st->reason = QTR_ICP_STOP_TRANSFORMATION;
+  } else if (prev >= 0.0) {
+    const double ch = mse - prev;
+    if ((ch < 0 ? -ch : ch) <= cfg->fit_eps * prev) st->reason = QTR_ICP_STOP_FITNESS;
+  }
+  if (st->reason != QTR_ICP_RUNNING) {
+    st->stop = 1;
+    st->converged = 1;
+  }
+}

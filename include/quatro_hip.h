@@ -25,6 +25,8 @@
  *                                                          include/imageProjection.hpp:244-258,273-581
  *   qtr_submit_batch / qtr_wait <- the demo's loop over scan pairs (one Quatro object, reset() between
  *                         registrations)                   examples/run_global_registration.cpp:97-108
+ *   qtr_icp / qtr_refine_pair <- pcl::IterativeClosestPoint(WithNormals)::align after the registration (the
+ *                         reference class derives from pcl::Registration, include/quatro.hpp:131,151)
  *   qtr_register_pair  <- the demo's whole path        examples/run_global_registration.cpp:206-246
  *                         (voxelize x2, FPFHManager::setFeaturePair include/fpfh_manager.hpp:98-153,
  *                          setInputSource/setInputTarget/computeTransformation)
@@ -398,6 +400,56 @@ QTR_API int qtr_get_nn_totals(qtr_handle* h, int slot, double* total_ms, long lo
  * call of its own rather than two more fields: qtr_stage_times keeps its size for callers built against earlier headers. */
 QTR_API int qtr_get_nn_dir_times(qtr_handle* h, int slot, float* dir1_ms, float* dir2_ms);
 
+/* 6-DoF ICP refinement of a registration (the step after a global registration: Quatro recovers yaw and translation only,
+ * roll / pitch come from the caller's estimated_RyRx_).  pcl::IterativeClosestPoint's knobs (pcl::Registration /
+ * DefaultConvergenceCriteria); the whole loop runs on the device, one launch per iteration and no host read-back inside it.
+ *   correspondence: the NEAREST target point within max_correspondence_distance of R p + t (binary64 distances, ties
+ *                   to the lowest target index); non-finite points of either cloud are ignored; point-to-plane also drops
+ *                   a correspondence whose target normal is not finite
+ *   point-to-plane: one Gauss-Newton step of sum ((q - t) . n)^2 per iteration (6x6 LDL^T; rotation increment from the
+ *                   normalised quaternion (1, w/2)); point-to-point: the closed-form rotation of the cross-covariance
+ *   stopping:       max_iterations updates; max |dT - I| <= transformation_epsilon; |mse - mse_prev| <=
+ *                   euclidean_fitness_epsilon * mse_prev; fewer than min_correspondences correspondences (valid = 0, T the
+ *                   last good transform); a rank-deficient system, e.g. a single plane (valid = 0, T the last good one)
+ * Sizes above qtr_limits.max_voxels per cloud: QTR_ERR_CAPACITY.  Empty clouds: QTR_OK with valid = 0 and T = guess.
+ * The arena is allocated on a slot's first ICP call. */
+#define QTR_ICP_POINT_TO_PLANE 0
+#define QTR_ICP_POINT_TO_POINT 1
+#define QTR_ICP_MAX_ITERATIONS 1000 /* largest max_iterations accepted */
+/* qtr_icp_result.stop_reason */
+#define QTR_ICP_STOP_NONE 0
+#define QTR_ICP_STOP_MAX_ITERATIONS 1
+#define QTR_ICP_STOP_TRANSFORMATION 2
+#define QTR_ICP_STOP_FITNESS 3
+#define QTR_ICP_STOP_TOO_FEW 4
+#define QTR_ICP_STOP_DEGENERATE 5
+typedef struct qtr_icp_params {
+  double max_correspondence_distance; /* 1.0 m (setMaxCorrespondenceDistance) */
+  double transformation_epsilon;      /* 1e-7: max |dT - I| of an update (setTransformationEpsilon) */
+  double euclidean_fitness_epsilon;   /* 1e-6: relative change of the correspondences' MSE (setEuclideanFitnessEpsilon) */
+  int max_iterations;                 /* 30 (setMaximumIterations), 1 .. QTR_ICP_MAX_ITERATIONS */
+  int method;                         /* QTR_ICP_POINT_TO_PLANE */
+  int min_correspondences;            /* 0 = the method's minimum: 6 point-to-plane, 3 point-to-point */
+  float normal_radius;                /* 0.5 m: target normals of qtr_icp when the caller passes none (the FPFH stage's
+                                         normal estimation); qtr_refine_pair uses the registration's normals */
+} qtr_icp_params;
+typedef struct qtr_icp_result {
+  int status, valid, converged, stop_reason, iterations, n_corr;
+  double T[16];   /* row-major, maps source into target */
+  double fitness; /* mean squared distance of the last evaluated correspondences (pcl getFitnessScore) */
+  double rmse;    /* sqrt of the mean squared residual the method minimises (point-to-plane distance / point distance) */
+} qtr_icp_result;
+QTR_API void qtr_default_icp_params(qtr_icp_params* p);
+/* src4 (n_s) / tgt4 (n_t): 16-byte records; tgt_normals4: n_t records nx,ny,nz,* (point-to-plane; NULL: computed at
+ * normal_radius).  guess: row-major 4x4 (NULL = identity).  mem: where the clouds live. */
+QTR_API int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const float* tgt4, int n_t, const float* tgt_normals4,
+                    const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res, int mem);
+/* Refines the slot's last qtr_register_pair / qtr_register_pair_corr on its voxelised clouds (the CALLER's source and
+ * target) and the target normals its FPFH stage left in the slot: no copy, no recomputation.  guess NULL = that call's T.
+ * QTR_ERR_BAD_ARG when the slot's last call was not a registration.  Leaves the registration's state untouched (it may be
+ * refined again, with other parameters). */
+QTR_API int qtr_refine_pair(qtr_handle* h, int slot, const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res);
+
 /* Inspection of intermediates of the LAST call on a slot (tests / parity debugging).  Copies up to
  * `bytes` bytes to host memory `dst`; returns the number of bytes the item holds, or <0 on error. */
 #define QTR_DBG_GRAPH_BITMAP 1   /* uint64[L][ceil(L/64)] adjacency, original labels */
@@ -420,6 +472,9 @@ QTR_API int qtr_get_nn_dir_times(qtr_handle* h, int slot, float* dir1_ms, float*
 #define QTR_DBG_SOLVER_STATE 14  /* int32[32]: mc, best_r, pos, done, t0, ub, batch, max_core, n_edges2, clique rounds,
                                     [10] k-core peeling rounds / iterations, [22] 1: the clique stage ran twice (second
                                     time with exact core numbers), [29] floor of the core numbers (0: all exact) */
+#define QTR_DBG_ICP_CORR 15      /* int32[n_s] target index of every source point in the last ICP iteration (-1: none) */
+#define QTR_DBG_ICP_TRACE 16     /* double[iterations][18] per update of the last ICP call: T after it (16), MSE, count */
+#define QTR_DBG_ICP_TIMES 17     /* float[2] last ICP call: grid build, iterations (device milliseconds) */
 QTR_API long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t bytes);
 
 /* Evaluates the shared deterministic math (include/qtr_math.h) ON THE DEVICE, for the test that pins

@@ -412,3 +412,94 @@ class Quatro:
 
     def getNumMaxCliqueInliers(self) -> int:
         return self.num_maxclique_
+
+
+class IterativeClosestPoint:
+    """pcl::IterativeClosestPoint's surface (setInputSource / setInputTarget / the convergence knobs / align) over
+    qtr_icp: the 6-DoF refinement that normally follows a global registration.  Point-to-plane by default
+    (pcl::IterativeClosestPointWithNormals; target normals at normal_radius unless setTargetNormals gives them),
+    point-to-point with method="point_to_point".  Everything numerical runs on the device."""
+
+    def __init__(self, handle=None, method: str = "point_to_plane", normal_radius: float = 0.5):
+        if method not in ("point_to_plane", "point_to_point"):
+            raise ValueError("method must be 'point_to_plane' or 'point_to_point'")
+        self._h = handle
+        self.params_ = _ql.default_icp_params(
+            method=_ql.ICP_POINT_TO_PLANE if method == "point_to_plane" else _ql.ICP_POINT_TO_POINT,
+            normal_radius=float(normal_radius))
+        self.input_ = None
+        self.target_ = None
+        self.target_normals_ = None
+        self.final_transformation_ = np.eye(4)
+        self.converged_ = False
+        self.result_ = None
+
+    def setInputSource(self, cloud):
+        self.input_ = _as_cloud(cloud)
+
+    def setInputTarget(self, cloud):
+        self.target_ = _as_cloud(cloud)
+        self.target_normals_ = None
+
+    def setTargetNormals(self, normals):
+        self.target_normals_ = None if normals is None else _as_cloud(normals)
+
+    def setMaxCorrespondenceDistance(self, distance: float):
+        self.params_.max_correspondence_distance = float(distance)
+
+    def setMaximumIterations(self, nr_iterations: int):
+        self.params_.max_iterations = int(nr_iterations)
+
+    def setTransformationEpsilon(self, epsilon: float):
+        self.params_.transformation_epsilon = float(epsilon)
+
+    def setEuclideanFitnessEpsilon(self, epsilon: float):
+        self.params_.euclidean_fitness_epsilon = float(epsilon)
+
+    def getMaxCorrespondenceDistance(self) -> float:
+        return self.params_.max_correspondence_distance
+
+    def getMaximumIterations(self) -> int:
+        return self.params_.max_iterations
+
+    def align(self, guess=None):
+        """Runs the loop from `guess` (4x4, default identity) and returns the source transformed by the final
+        transformation, like pcl::Registration::align(output, guess)."""
+        if self.input_ is None or self.target_ is None:
+            raise ValueError("input clouds not set")
+        h = self._h or _handle()
+        r = h.icp(self.input_, self.target_, self.target_normals_, np.eye(4) if guess is None else guess, self.params_)
+        self.result_ = r
+        self.final_transformation_ = r["T"]
+        self.converged_ = r["converged"]
+        T = r["T"]
+        out = self.input_.copy()
+        out[:, :3] = (self.input_[:, :3].astype(np.float64) @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
+        return out
+
+    def hasConverged(self) -> bool:
+        return bool(self.converged_)
+
+    def getFitnessScore(self) -> float:
+        """Mean squared distance of the last iteration's correspondences (DBL_MAX without any)."""
+        return float(self.result_["fitness"]) if self.result_ else float(np.finfo(np.float64).max)
+
+    def getFinalTransformation(self) -> np.ndarray:
+        return self.final_transformation_.copy()
+
+
+def refine_quatro(quatro: "Quatro", source_cloud, target_cloud, icp: IterativeClosestPoint | None = None):
+    """Refines a Quatro result on the clouds themselves (the scans, typically voxelised): an IterativeClosestPoint on the
+    same handle as `quatro`, started from its solution.  Returns the refined 4x4 (and leaves the ICP object's state
+    readable: hasConverged, getFitnessScore)."""
+    icp = icp or IterativeClosestPoint(handle=quatro._h)
+    if icp._h is None:
+        icp._h = quatro._h
+    guess = np.eye(4)
+    if quatro.solution_.valid:
+        guess[:3, :3] = quatro.solution_.rotation
+        guess[:3, 3] = quatro.solution_.translation
+    icp.setInputSource(source_cloud)
+    icp.setInputTarget(target_cloud)
+    icp.align(guess)
+    return icp.getFinalTransformation()

@@ -19,7 +19,8 @@ LIB = os.path.join(HERE, "libquatro_hip.so")
 # live in a second build with -DQTR_TEST_ENGINES that only tests load (quatro_amd.lib.Handle(lib_path=...))
 TEST_LIB = os.path.join(HERE, "libquatro_hip_testengines.so")
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))) + [
-    os.path.join("..", "..", "include", "qtr_math.h"), os.path.join("..", "..", "include", "quatro_hip.h")]
+    os.path.join("..", "..", "include", "qtr_math.h"), os.path.join("..", "..", "include", "qtr_icp_math.h"),
+    os.path.join("..", "..", "include", "quatro_hip.h")]
 
 
 def is_stale(lib: str = LIB) -> bool:

@@ -56,6 +56,11 @@ struct Slot {
   int last_Wb = 0; // row stride (words) of the bit matrix it left behind (solver.h SolverView::Wb)
   int last_n = 0;  // points of the last qtr_fpfh
   int last_ns = 0, last_nt = 0;
+  IcpBufs icp;                   // ICP arena (allocated on first use: icp.hip)
+  int reg_ready = 0;             // 1: the last call on this slot was a registration (qtr_refine_pair may use its clouds)
+  double reg_T[16] = {};         // ... and its transform
+  int icp_ns = 0, icp_iters = 0; // source points and updates of the last ICP call (debug ids)
+  float icp_ms[2] = {0, 0};      // its grid build and its iterations, milliseconds
 };
 
 // One lane of the batch driver (qtr_submit_batch): a contiguous group of slots stepped through the three launch
@@ -114,6 +119,7 @@ struct qtr_handle {
   unsigned long long uid = 0;     // process-unique id of this handle (a thread remembers the handle it registered with)
   int stage_events = 1;  // QTR_STAGE_EVENTS=0: only the first/last event of a call are recorded (stage times read 0)
   int nn_event_stride = 1;  // every n-th match of a slot carries the nearest-neighbour event pairs (0: none)
+  int icp_block = 0;  // QTR_ICP_BLOCK=n: ICP launches enqueued between two read-backs of the stop flag (0: all at once)
   char err[512];
 };
 
@@ -396,6 +402,7 @@ void qtr_destroy(qtr_handle* h) {
     if (s.seg_arena) (void)hipFree(s.seg_arena);
     if (s.pw_arena) (void)hipFree(s.pw_arena);
     if (s.ex_arena) (void)hipFree(s.ex_arena);
+    icp_free(s.icp);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.stream2) (void)hipStreamDestroy(s.stream2);
   }
@@ -507,6 +514,8 @@ int qtr_create(int device, const qtr_limits* limits, qtr_handle** out) {
     const char* se = getenv("QTR_STAGE_EVENTS");
     h->stage_events = (se && atoi(se) == 0) ? 0 : 1;
     h->nn_event_stride = h->stage_events ? 1 : 0;
+    const char* ib = getenv("QTR_ICP_BLOCK");
+    h->icp_block = ib ? std::max(0, atoi(ib)) : 0;
   }
   if (limits)
     h->lim = *limits;
@@ -679,13 +688,20 @@ static int ensure_long_arenas(qtr_handle* h, Slot& s) {
   return QTR_OK;
 }
 
-static Slot* get_slot(qtr_handle* h, int slot) {
+// inspection calls (qtr_debug_fetch, timings) look at a slot without ending what its last call left behind
+static Slot* peek_slot(qtr_handle* h, int slot) {
   if (!h) return nullptr;
   if (slot < 0 || slot >= (int)h->slots.size()) {
     snprintf(h->err, sizeof(h->err), "slot %d out of range", slot);
     return nullptr;
   }
   return &h->slots[slot];
+}
+// every working call: the slot's clouds are no longer those of a registration (qtr_refine_pair refuses them)
+static Slot* get_slot(qtr_handle* h, int slot) {
+  Slot* s = peek_slot(h, slot);
+  if (s) s->reg_ready = 0;
+  return s;
 }
 
 static int check_params(qtr_handle* h, const qtr_params* prm) {
@@ -1415,7 +1431,7 @@ int qtr_set_nn_event_stride(qtr_handle* h, int every) {
 }
 
 int qtr_get_nn_dir_times(qtr_handle* h, int slot, float* dir1_ms, float* dir2_ms) {
-  Slot* sp = get_slot(h, slot);
+  Slot* sp = peek_slot(h, slot);
   if (!sp) return QTR_ERR_BAD_ARG;
   if (sp->times_pending) {  // (the events of the last call are read on demand, like qtr_get_stage_times does)
     qtr_stage_times t;
@@ -1427,7 +1443,7 @@ int qtr_get_nn_dir_times(qtr_handle* h, int slot, float* dir1_ms, float* dir2_ms
 }
 
 int qtr_get_nn_totals(qtr_handle* h, int slot, double* total_ms, long long* launches, int reset) {
-  Slot* sp = get_slot(h, slot);
+  Slot* sp = peek_slot(h, slot);
   if (!sp) return QTR_ERR_BAD_ARG;
   (void)hipStreamSynchronize(sp->stream);
   flush_nn_totals(*sp);
@@ -1441,7 +1457,7 @@ int qtr_get_nn_totals(qtr_handle* h, int slot, double* total_ms, long long* laun
 }
 
 int qtr_get_stage_times(qtr_handle* h, int slot, qtr_stage_times* out) {
-  Slot* sp = get_slot(h, slot);
+  Slot* sp = peek_slot(h, slot);
   if (!sp || !out) return QTR_ERR_BAD_ARG;
   compute_times(*sp);
   *out = sp->times;
@@ -1801,6 +1817,13 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
   return QTR_OK;
 }
 
+// a registration that got through its front end leaves its voxel clouds, the target normals and T for qtr_refine_pair
+static void mark_registration(Slot& s, int rc, const qtr_result* res) {
+  if (rc != QTR_OK && rc != QTR_ERR_CLIQUE_TOO_SMALL) return;
+  s.reg_ready = 1;
+  for (int k = 0; k < 16; ++k) s.reg_T[k] = res->T[k];
+}
+
 // The whole path on one slot.  mem_in: where the scans live; mem_out: where the index lists go.  corr_src / corr_tgt
 // (device pointers, n_corr >= 0): the back end runs on THESE matched clouds instead of the matcher's output (the batched
 // entry's "scans + pre-matched correspondences" pairs); n_corr < 0: the matcher's own correspondences.
@@ -1833,8 +1856,10 @@ int qtr_register_pair(qtr_handle* h, int slot, const float* src_raw4, int Ps, co
   memset(res, 0, sizeof(*res));
   const int rc = check_params(h, prm);
   if (rc != QTR_OK) return res->status = rc;
-  return register_pair_impl(h, *sp, src_raw4, Ps, tgt_raw4, Pt, fp, prm, res, clique, final_inliers, cap, mem, mem, nullptr,
-                            nullptr, -1);
+  const int rc2 = register_pair_impl(h, *sp, src_raw4, Ps, tgt_raw4, Pt, fp, prm, res, clique, final_inliers, cap, mem, mem,
+                                     nullptr, nullptr, -1);
+  mark_registration(*sp, rc2, res);
+  return rc2;
 }
 
 int qtr_register_pair_corr(qtr_handle* h, int slot, const float* src_raw4, int Ps, const float* tgt_raw4, int Pt,
@@ -1873,6 +1898,7 @@ int qtr_register_pair_corr(qtr_handle* h, int slot, const float* src_raw4, int P
   s.times_pending = h->stage_events ? 2 : 4;
   const int rc2 = copy_out_lists(h, s, res, clique, nullptr, final_inliers, cap, mem);
   if (rc2 != QTR_OK) return res->status = rc2;
+  mark_registration(s, rc, res);
   return rc;
 }
 
@@ -2450,6 +2476,7 @@ int qtr_submit_batch(qtr_handle* h, const qtr_pair_desc* pairs, int B, const qtr
   }
   const int rc = check_params(h, prm);
   if (rc != QTR_OK) return rc;
+  for (auto& sl : h->slots) sl.reg_ready = 0;  // (every slot's clouds are the batch's from here on)
   if (fp->normal_radius > fp->fpfh_radius) {
     snprintf(h->err, sizeof(h->err), "[FPFHManager]: Normal should be lower than fpfh_radius!!!!");
     return QTR_ERR_BAD_ARG;
@@ -2532,8 +2559,231 @@ int qtr_wait(qtr_handle* h) {
 }
 
 // ------------------------------------------------------------------------------------------------
-long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t bytes) {
+// ---- ICP refinement (icp.hip) -----------------------------------------------------------------------------------------
+void qtr_default_icp_params(qtr_icp_params* p) {
+  memset(p, 0, sizeof(*p));
+  p->max_correspondence_distance = 1.0;
+  p->transformation_epsilon = 1e-7;
+  p->euclidean_fitness_epsilon = 1e-6;
+  p->max_iterations = 30;
+  p->method = QTR_ICP_POINT_TO_PLANE;
+  p->min_correspondences = 0;
+  p->normal_radius = 0.5f;
+}
+
+static bool icp_finite(double x) { return x - x == 0.0; }
+
+static int check_icp_params(qtr_handle* h, const qtr_icp_params* p) {
+  if (!p || !icp_finite(p->max_correspondence_distance) || !(p->max_correspondence_distance > 0) ||
+      !icp_finite(p->transformation_epsilon) || p->transformation_epsilon < 0 || !icp_finite(p->euclidean_fitness_epsilon) ||
+      p->euclidean_fitness_epsilon < 0 || p->max_iterations < 1 || p->max_iterations > QTR_ICP_MAX_ITERATIONS ||
+      (p->method != QTR_ICP_POINT_TO_PLANE && p->method != QTR_ICP_POINT_TO_POINT) || p->min_correspondences < 0 ||
+      !icp_finite((double)p->normal_radius) || !(p->normal_radius > 0)) {
+    snprintf(h->err, sizeof(h->err), "invalid ICP parameter");
+    return QTR_ERR_BAD_ARG;
+  }
+  return QTR_OK;
+}
+
+static void icp_result_from(qtr_icp_result* res, const QtrIcpState& st) {
+  res->valid = st.valid;
+  res->converged = st.converged;
+  res->stop_reason = st.reason;
+  res->iterations = st.iterations;
+  res->n_corr = st.n_corr;
+  for (int k = 0; k < 16; ++k) res->T[k] = st.T[k];
+  res->fitness = st.fitness;
+  res->rmse = st.rmse;
+}
+
+// The loop on device-resident clouds: grid over the target, then the iterations, one launch each, with no host read-back
+// inside a block of h->icp_block launches (0: all max_iterations of them in one go).
+static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const float4* d_tgt, int nt, const float4* d_nrm,
+                      const double* guess, const qtr_icp_params* prm, qtr_icp_result* res) {
+  QtrIcpState init;
+  qtr_icp_init(&init, guess);
+  init.reason = QTR_ICP_STOP_TOO_FEW;  // (what an empty cloud reports; the device state starts RUNNING)
+  icp_result_from(res, init);
+  res->status = QTR_OK;
+  s.icp_ns = 0;
+  s.icp_iters = 0;
+  s.icp_ms[0] = s.icp_ms[1] = 0.f;
+  if (ns == 0 || nt == 0) return QTR_OK;
+  IcpBufs& B = s.icp;
+  QTR_HIP_TRY(h, icp_reserve(B, h->lim.max_voxels, QTR_ICP_MAX_ITERATIONS));
+  IcpView& v = B.v;
+  v.src = d_src;
+  v.tgt = d_tgt;
+  v.nrm = prm->method == QTR_ICP_POINT_TO_PLANE ? d_nrm : nullptr;
+  v.ns = ns;
+  v.nt = nt;
+  v.cfg.max_d2 = prm->max_correspondence_distance * prm->max_correspondence_distance;
+  v.cfg.trans_eps = prm->transformation_epsilon;
+  v.cfg.fit_eps = prm->euclidean_fitness_epsilon;
+  v.cfg.max_iterations = prm->max_iterations;
+  v.cfg.method = prm->method;
+  v.cfg.min_corr = prm->min_correspondences > 0 ? prm->min_correspondences : (prm->method == QTR_ICP_POINT_TO_PLANE ? 6 : 3);
+  v.cfg.pad = 0;
+  const hipStream_t st = s.stream;
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[0], st));
+  // bounding box of the finite target points (one read-back per call: it sizes the cell table)
+  for (int a = 0; a < 3; ++a) {
+    B.h_bbox[a] = 0x7fffffff;
+    B.h_bbox[3 + a] = (int)0x80000000;
+  }
+  QTR_HIP_TRY(h, hipMemcpyAsync(v.bbox, B.h_bbox, 24, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_icp_bbox, dim3(qtr_div_up(nt, 256)), dim3(256), 0, st, v);
+  QTR_HIP_TRY(h, hipGetLastError());
+  QTR_HIP_TRY(h, hipMemcpyAsync(B.h_bbox, v.bbox, 24, hipMemcpyDeviceToHost, st));
+  QTR_HIP_TRY(h, hipStreamSynchronize(st));
+  if (B.h_bbox[0] > B.h_bbox[3]) return QTR_OK;  // no finite target point
+  double mx[3];
+  for (int a = 0; a < 3; ++a) {
+    v.mn[a] = (double)icp_dec(B.h_bbox[a]);
+    mx[a] = (double)icp_dec(B.h_bbox[3 + a]);
+  }
+  // cells a little larger than the correspondence distance (a rounding of the cell index cannot hide a point in reach);
+  // a grid of more than QTR_ICP_CELL_CAP cells takes larger ones
+  double cell = prm->max_correspondence_distance * 1.001;
+  double nc = 0;
+  for (;;) {
+    nc = 1;
+    for (int a = 0; a < 3; ++a) nc *= floor((mx[a] - v.mn[a]) / cell) + 1.0;
+    if (nc <= (double)QTR_ICP_CELL_CAP) break;
+    cell *= 1.25;
+  }
+  v.cell = cell;
+  for (int a = 0; a < 3; ++a) v.dims[a] = (int)(floor((mx[a] - v.mn[a]) / cell) + 1.0);
+  v.ncell = v.dims[0] * v.dims[1] * v.dims[2];
+  QTR_HIP_TRY(h, icp_reserve_cells(B, v.ncell));
+  v.cell_cnt = B.cells;
+  v.cell_start = B.cells + B.cap_cells + 1;
+  QTR_HIP_TRY(h, hipMemsetAsync(v.cell_cnt, 0, (size_t)(v.ncell + 1) * 4, st));
+  hipLaunchKernelGGL(k_icp_count, dim3(qtr_div_up(nt, 256)), dim3(256), 0, st, v);
+  QTR_HIP_TRY(h, hipGetLastError());
+  QTR_HIP_TRY(h, exclusive_scan_i32(v.cell_cnt, v.cell_start, v.ncell, st));
+  hipLaunchKernelGGL(k_icp_place, dim3(qtr_div_up(nt, 256)), dim3(256), 0, st, v);
+  QTR_HIP_TRY(h, hipGetLastError());
+  QtrIcpState st0;
+  qtr_icp_init(&st0, guess);
+  hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, v, st0);
+  QTR_HIP_TRY(h, hipGetLastError());
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[1], st));
+  const int nchunk = qtr_div_up(ns, QTR_ICP_CHUNK);
+  const int block = h->icp_block > 0 ? h->icp_block : prm->max_iterations;
+  for (int it = 0; it < prm->max_iterations;) {
+    const int m = std::min(block, prm->max_iterations - it);
+    for (int k = 0; k < m; ++k) hipLaunchKernelGGL(k_icp_iter, dim3(nchunk), dim3(256), 0, st, v);
+    QTR_HIP_TRY(h, hipGetLastError());
+    it += m;
+    if (it >= prm->max_iterations) break;
+    QTR_HIP_TRY(h, hipMemcpyAsync(B.h_state, v.st, sizeof(QtrIcpState), hipMemcpyDeviceToHost, st));
+    QTR_HIP_TRY(h, hipStreamSynchronize(st));
+    if (B.h_state->stop) break;
+  }
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[2], st));
+  QTR_HIP_TRY(h, hipMemcpyAsync(B.h_state, v.st, sizeof(QtrIcpState), hipMemcpyDeviceToHost, st));
+  QTR_HIP_TRY(h, hipStreamSynchronize(st));
+  icp_result_from(res, *B.h_state);
+  s.icp_ns = ns;
+  s.icp_iters = B.h_state->iterations;
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.icp_ms[0] = ms;
+  if (hipEventElapsedTime(&ms, s.ev[1], s.ev[2]) == hipSuccess) s.icp_ms[1] = ms;
+  s.times_pending = 0;
+  s.times = qtr_stage_times{};
+  s.times.total = s.icp_ms[0] + s.icp_ms[1];
+  return QTR_OK;
+}
+
+static const double kIcpIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+
+static bool icp_guess_ok(const double* g) {
+  for (int k = 0; k < 16; ++k)
+    if (!icp_finite(g[k])) return false;
+  return true;
+}
+
+int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const float* tgt4, int n_t, const float* tgt_normals4,
+            const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res, int mem) {
   Slot* sp = get_slot(h, slot);
+  if (!sp || !res) return QTR_ERR_BAD_ARG;
+  memset(res, 0, sizeof(*res));
+  Slot& s = *sp;
+  int rc = check_icp_params(h, prm);
+  if (rc != QTR_OK) return res->status = rc;
+  if (n_s < 0 || n_t < 0 || (n_s > 0 && !src4) || (n_t > 0 && !tgt4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE) ||
+      (guess && !icp_guess_ok(guess))) {
+    snprintf(h->err, sizeof(h->err), "bad ICP arguments");
+    return res->status = QTR_ERR_BAD_ARG;
+  }
+  if (n_s > h->lim.max_voxels || n_t > h->lim.max_voxels) {
+    snprintf(h->err, sizeof(h->err), "ICP cloud exceeds max_voxels=%d", h->lim.max_voxels);
+    return res->status = QTR_ERR_CAPACITY;
+  }
+  const double* g = guess ? guess : kIcpIdentity;
+  if (n_s == 0 || n_t == 0) return icp_device(h, s, nullptr, n_s, nullptr, n_t, nullptr, g, prm, res);
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  const float4 *d_s = (const float4*)src4, *d_t = (const float4*)tgt4, *d_n = (const float4*)tgt_normals4;
+  const bool plane = prm->method == QTR_ICP_POINT_TO_PLANE;
+  if (mem == QTR_MEM_HOST) {  // (staging: the raw-scan buffers, max_points >= max_voxels points each)
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, src4, (size_t)n_s * 16, hipMemcpyHostToDevice, s.stream));
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_tgt, tgt4, (size_t)n_t * 16, hipMemcpyHostToDevice, s.stream));
+    d_s = s.in_src;
+    d_t = s.in_tgt;
+    if (plane && tgt_normals4) {
+      QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[1].normals, tgt_normals4, (size_t)n_t * 16, hipMemcpyHostToDevice, s.stream));
+      d_n = s.fb.cloud[1].normals;
+    }
+  }
+  if (plane && !tgt_normals4) {
+    // the target's normals at normal_radius: the normal stage of the FPFH chain (qtr_fpfh's dense mode) on a copy of the
+    // target in the first cloud's arena
+    CloudBufs& cb = s.fb.cloud[0];
+    QTR_HIP_TRY(h, hipMemcpyAsync(cb.vox, d_t, (size_t)n_t * 16, hipMemcpyDeviceToDevice, s.stream));
+    QTR_HIP_TRY(h, hipMemsetAsync(cb.counts, 0, 16 * sizeof(int), s.stream));
+    QTR_HIP_TRY(h, set_count_enqueue(cb, CNT_NVOX, n_t, s.stream));
+    QTR_TRY(ensure_long_arenas(h, s));
+    const int n1[1] = {n_t};
+    QTR_HIP_TRY(h, fpfh_enqueue(s.fb, 0, 1, n1, prm->normal_radius, prm->normal_radius, s.stream, false, false, true));
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32, cb.counts, 16 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
+    QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
+    if (s.pinned_i32[CNT_NBR_CAPACITY]) {
+      snprintf(h->err, sizeof(h->err), "normals at normal_radius: radius-neighbour lists exceed the long-list arena "
+               "(qtr_limits.max_long_neighbors is %d)", h->lim.max_long_neighbors);
+      return res->status = QTR_ERR_CAPACITY;
+    }
+    d_n = cb.normals;
+  }
+  rc = icp_device(h, s, d_s, n_s, d_t, n_t, d_n, g, prm, res);
+  return res->status = rc;
+}
+
+int qtr_refine_pair(qtr_handle* h, int slot, const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res) {
+  Slot* sp = peek_slot(h, slot);  // (a refinement leaves the registration's clouds as they are: it may be repeated)
+  if (!sp || !res) return QTR_ERR_BAD_ARG;
+  memset(res, 0, sizeof(*res));
+  Slot& s = *sp;
+  int rc = check_icp_params(h, prm);
+  if (rc != QTR_OK) return res->status = rc;
+  if (!s.reg_ready) {
+    snprintf(h->err, sizeof(h->err), "qtr_refine_pair: the slot's last call was not a registration");
+    return res->status = QTR_ERR_BAD_ARG;
+  }
+  if (guess && !icp_guess_ok(guess)) {
+    snprintf(h->err, sizeof(h->err), "bad ICP guess");
+    return res->status = QTR_ERR_BAD_ARG;
+  }
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  // cloud[0] / cloud[1] hold the caller's source / target whatever roles the matcher gave them (it swaps views, not
+  // arenas); the target's normals are the FPFH stage's, at the registration's normal_radius
+  rc = icp_device(h, s, s.fb.cloud[0].vox, s.last_ns, s.fb.cloud[1].vox, s.last_nt, s.fb.cloud[1].normals,
+                  guess ? guess : s.reg_T, prm, res);
+  return res->status = rc;
+}
+
+long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t bytes) {
+  Slot* sp = peek_slot(h, slot);
   if (!sp) return -1;
   Slot& s = *sp;
   if (hipSetDevice(h->device) != hipSuccess) return -1;
@@ -2569,6 +2819,9 @@ long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t b
     case QTR_DBG_CORR: src = s.fb.corr; have = (size_t)s.last_L * 8; break;
     case QTR_DBG_MATCH_STATS: src = s.fb.mcounts; have = 16 * 4; break;
     case QTR_DBG_SOLVER_STATE: src = s.sb.st; have = sizeof(SolverState); break;
+    case QTR_DBG_ICP_CORR: src = s.icp.v.corr; have = s.icp.v.corr ? (size_t)s.icp_ns * 4 : 0; break;
+    case QTR_DBG_ICP_TRACE: src = s.icp.v.trace; have = s.icp.v.trace ? (size_t)s.icp_iters * 18 * 8 : 0; break;
+    case QTR_DBG_ICP_TIMES: src = s.icp_ms; have = sizeof(s.icp_ms); break;
     default: return -1;
   }
   const size_t n = have < bytes ? have : bytes;
@@ -2579,6 +2832,8 @@ long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t b
       if (rows > 0 && hipMemcpy2D(dst, (size_t)W * 8, src, (size_t)s.last_Wb * 8, (size_t)W * 8, rows, hipMemcpyDeviceToHost) !=
                           hipSuccess)
         return -1;
+    } else if (what == QTR_DBG_ICP_TIMES) {
+      memcpy(dst, src, n);
     } else if (hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) {
       return -1;
     }

@@ -1,0 +1,289 @@
+// icp.hip — 6-DoF ICP refinement on the device (qtr_icp / qtr_refine_pair): point-to-plane (default) and point-to-point.
+//
+// Per call: a uniform cell grid over the finite target points (cell side >= max_correspondence_distance, so the
+// nearest target within reach of any query lies in its 27 neighbouring cells), built by a counting sort into the
+// handle's own ICP arena (k_icp_bbox, k_icp_count, exclusive_scan_i32, k_icp_place).  The FPFH chain's cell table is not
+// used: its cells are the FPFH radius over the RAW scan's box and its counters must stay zero between registrations;
+// the ICP table has its own counters, cleared by the call that uses them.
+//
+// Per iteration: ONE launch of k_icp_iter (one workgroup per 256 source points).  Every thread transforms its point
+// with the current T, finds the nearest target (binary64 d^2, ties to the lowest target index, so the order inside a
+// cell does not matter) and forms its terms; the terms are summed in a fixed shape (include/qtr_icp_math.h) into one
+// partial per workgroup; the LAST workgroup to finish (atomic ticket) adds the partials in workgroup order, solves,
+// updates T and decides whether to stop.  Nobody waits for anybody, so no co-residency is assumed.  A launch that finds
+// the stop flag set returns at once, so the host can enqueue iterations without reading anything back.
+#include "common.h"
+#include "frontend.h"
+#include "../../include/qtr_icp_math.h"
+
+struct IcpView {
+  const float4* src;      // [ns] source points (x, y, z, *)
+  const float4* tgt;      // [nt] target points
+  const float4* nrm;      // [nt] target normals (point-to-plane) or null
+  int ns, nt;
+  float4* spts;           // [nt] finite target points in cell order, w = original index
+  float4* snrm;           // [nt] their normals in the same order
+  int* cell_cnt;          // [ncell + 1] counters (zeroed by the call)
+  int* cell_start;        // [ncell + 1] exclusive scan of cell_cnt
+  int* place;             // [nt][2] cell and rank in the cell of every target point (-1: not finite)
+  int* bbox;              // 6 order-preserving encodings: min x, y, z, max x, y, z
+  double mn[3];           // grid origin and cell side (host-computed from bbox)
+  double cell;
+  int dims[3];
+  int ncell;
+  QtrIcpCfg cfg;
+  QtrIcpState* st;        // device state
+  double* partials;       // [nchunk][QTR_ICP_NT]
+  unsigned* ticket;       // workgroups done in the current launch (reset by the last one)
+  int* corr;              // [ns] target index of every source point in the last evaluated iteration (-1: none)
+  double* trace;          // [max_iterations][18]
+};
+
+__device__ __forceinline__ int icp_enc(float f) {  // order-preserving int of a finite float (for atomicMin / Max)
+  const int b = __float_as_int(f);
+  return b >= 0 ? b : (b ^ 0x7fffffff);
+}
+static inline float icp_dec(int e) {  // (host)
+  const int b = e >= 0 ? e : (e ^ 0x7fffffff);
+  float f;
+  memcpy(&f, &b, 4);
+  return f;
+}
+
+__global__ __launch_bounds__(256) void k_icp_bbox(IcpView v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= v.nt) return;
+  const float4 p = v.tgt[i];
+  if (!qtr_icp_finite3(p.x, p.y, p.z)) return;
+  atomicMin(v.bbox + 0, icp_enc(p.x));
+  atomicMin(v.bbox + 1, icp_enc(p.y));
+  atomicMin(v.bbox + 2, icp_enc(p.z));
+  atomicMax(v.bbox + 3, icp_enc(p.x));
+  atomicMax(v.bbox + 4, icp_enc(p.y));
+  atomicMax(v.bbox + 5, icp_enc(p.z));
+}
+
+// cell index of a coordinate (binary64), the same expression on both sides of the grid
+__device__ __forceinline__ double icp_cellf(double x, double mn, double cell) { return floor((x - mn) / cell); }
+
+__device__ __forceinline__ int icp_cell_of(const IcpView& v, float4 p) {
+  int c[3];
+  const double x[3] = {(double)p.x, (double)p.y, (double)p.z};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double f = icp_cellf(x[a], v.mn[a], v.cell);
+    c[a] = f < 0 ? 0 : (f > (double)(v.dims[a] - 1) ? v.dims[a] - 1 : (int)f);
+  }
+  return c[0] + v.dims[0] * (c[1] + v.dims[1] * c[2]);
+}
+
+__global__ __launch_bounds__(256) void k_icp_count(IcpView v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= v.nt) return;
+  const float4 p = v.tgt[i];
+  if (!qtr_icp_finite3(p.x, p.y, p.z)) {
+    v.place[2 * i] = -1;
+    return;
+  }
+  const int lin = icp_cell_of(v, p);
+  v.place[2 * i] = lin;
+  v.place[2 * i + 1] = atomicAdd(v.cell_cnt + lin, 1);
+}
+
+__global__ __launch_bounds__(256) void k_icp_place(IcpView v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= v.nt) return;
+  const int lin = v.place[2 * i];
+  if (lin < 0) return;
+  const int at = v.cell_start[lin] + v.place[2 * i + 1];
+  float4 p = v.tgt[i];
+  p.w = __int_as_float(i);
+  v.spts[at] = p;
+  if (v.nrm) v.snrm[at] = v.nrm[i];
+}
+
+__global__ __launch_bounds__(256) void k_icp_init(IcpView v, QtrIcpState init) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    *v.st = init;
+    *v.ticket = 0u;
+  }
+}
+
+__device__ __forceinline__ double icp_shfl_down(double x, int off) { return __shfl_down(x, off, 64); }
+
+__global__ __launch_bounds__(256) void k_icp_iter(IcpView v) {
+  __shared__ double s_w[4][QTR_ICP_NT];
+  __shared__ double s_S[QTR_ICP_NT];
+  __shared__ int s_last;
+  const QtrIcpState* st = v.st;
+  if (st->stop) return;  // (uniform: written by an earlier launch)
+  double T[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) T[k] = st->T[k];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = blockIdx.x * QTR_ICP_CHUNK + tid;
+  double o[QTR_ICP_NT];
+#pragma unroll
+  for (int k = 0; k < QTR_ICP_NT; ++k) o[k] = 0.0;
+  if (i < v.ns) {
+    const float4 p = v.src[i];
+    int best = -1, bat = -1;
+    double bd = 0.0, q[3];
+    if (qtr_icp_finite3(p.x, p.y, p.z) && v.ncell > 0) {
+      qtr_icp_transform(T, p.x, p.y, p.z, q);
+      int lo[3], hi[3];
+      bool any = true;
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const double f = icp_cellf(q[a], v.mn[a], v.cell);  // (NaN / huge: compared as double before any int cast)
+        if (!(f >= -1.0 && f <= (double)v.dims[a])) {
+          any = false;
+          lo[a] = 0;
+          hi[a] = -1;
+        } else {
+          const int c = (int)f;
+          lo[a] = c - 1 < 0 ? 0 : c - 1;
+          hi[a] = c + 1 > v.dims[a] - 1 ? v.dims[a] - 1 : c + 1;
+        }
+      }
+      if (any) {
+        for (int cz = lo[2]; cz <= hi[2]; ++cz)
+          for (int cy = lo[1]; cy <= hi[1]; ++cy) {
+            const int row = v.dims[0] * (cy + v.dims[1] * cz);
+            const int s = v.cell_start[row + lo[0]], e = v.cell_start[row + hi[0] + 1];  // (cells of a row are contiguous)
+            for (int j = s; j < e; ++j) {
+              const float4 t = v.spts[j];
+              const double d2 = qtr_icp_d2(q, t.x, t.y, t.z);
+              const int idx = __float_as_int(t.w);
+              if (d2 <= v.cfg.max_d2 && (best < 0 || d2 < bd || (d2 == bd && idx < best))) {
+                best = idx;
+                bat = j;
+                bd = d2;
+              }
+            }
+          }
+      }
+    }
+    if (best >= 0 && v.cfg.method == 0) {
+      const float4 n = v.snrm[bat];
+      if (!qtr_icp_finite3(n.x, n.y, n.z)) best = -1;
+    }
+    v.corr[i] = best;
+    if (best >= 0) {
+      const float4 t = v.spts[bat];
+      const float4 n = v.cfg.method == 0 ? v.snrm[bat] : make_float4(0.f, 0.f, 0.f, 0.f);
+      qtr_icp_terms(v.cfg.method, q, t.x, t.y, t.z, n.x, n.y, n.z, bd, o);
+    }
+  }
+  // fixed-shape sum: the shfl_down fold inside each wave (qtr_icp_fold64), then (w0 + w1) + (w2 + w3)
+#pragma unroll
+  for (int k = 0; k < QTR_ICP_T_CNT + 1; ++k) {
+    double x = o[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) x = x + icp_shfl_down(x, off);
+    if (lane == 0) s_w[wave][k] = x;
+  }
+  __syncthreads();
+  if (tid < QTR_ICP_T_CNT + 1) {
+    const double w4[4] = {s_w[0][tid], s_w[1][tid], s_w[2][tid], s_w[3][tid]};
+    const double c = qtr_icp_chunk_sum(w4);
+    __hip_atomic_store((unsigned long long*)(v.partials + (size_t)blockIdx.x * QTR_ICP_NT + tid),
+                       (unsigned long long)__double_as_longlong(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned done = __hip_atomic_fetch_add(v.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = (done == gridDim.x - 1) ? 1 : 0;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  __threadfence();
+  if (tid < QTR_ICP_NT) {
+    double acc = 0.0;
+    if (tid < QTR_ICP_T_CNT + 1) {
+      acc = __longlong_as_double((long long)__hip_atomic_load((unsigned long long*)(v.partials + tid), __ATOMIC_RELAXED,
+                                                              __HIP_MEMORY_SCOPE_AGENT));
+      for (int c = 1; c < (int)gridDim.x; ++c)
+        acc = acc + __longlong_as_double((long long)__hip_atomic_load(
+                        (unsigned long long*)(v.partials + (size_t)c * QTR_ICP_NT + tid), __ATOMIC_RELAXED,
+                        __HIP_MEMORY_SCOPE_AGENT));
+    }
+    s_S[tid] = acc;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    QtrIcpState s = *v.st;
+    double* tr = (s.iterations < v.cfg.max_iterations) ? v.trace + (size_t)s.iterations * 18 : nullptr;
+    qtr_icp_step(&v.cfg, s_S, &s, tr);
+    *v.st = s;
+    __hip_atomic_store(v.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------
+struct IcpBufs {
+  int cap_pts = 0;        // points per cloud the arena holds
+  int cap_cells = 0;
+  void* arena = nullptr;  // everything but the cell table
+  int* cells = nullptr;   // [2][cap_cells + 1]: counters, starts
+  IcpView v{};
+  QtrIcpState* h_state = nullptr;  // pinned read-back
+  int* h_bbox = nullptr;
+};
+
+// the largest cell table of a call: a grid that would need more cells takes larger cells (still >= the correspondence
+// distance, so the result is the same; only the candidate lists get longer)
+#define QTR_ICP_CELL_CAP (1 << 22)
+
+static hipError_t icp_reserve(IcpBufs& B, int cap_pts, int max_iter_cap) {
+  if (B.arena && B.cap_pts >= cap_pts) return hipSuccess;
+  if (B.arena) (void)hipFree(B.arena);
+  if (B.h_state) (void)hipHostFree(B.h_state);
+  B.arena = nullptr;
+  B.h_state = nullptr;
+  const size_t nchunk = (size_t)(cap_pts + QTR_ICP_CHUNK - 1) / QTR_ICP_CHUNK;
+  const size_t bytes = (size_t)cap_pts * (16 + 16 + 8 + 4) + nchunk * QTR_ICP_NT * 8 + (size_t)max_iter_cap * 18 * 8 +
+                       sizeof(QtrIcpState) + 4096;
+  hipError_t e = hipMalloc(&B.arena, bytes);
+  if (e != hipSuccess) return e;
+  char* p = (char*)B.arena;
+  auto take = [&](size_t n) {
+    char* r = p;
+    p += (n + 255) & ~(size_t)255;
+    return r;
+  };
+  B.v.st = (QtrIcpState*)take(sizeof(QtrIcpState));
+  B.v.ticket = (unsigned*)take(64);
+  B.v.bbox = (int*)take(64);
+  B.v.partials = (double*)take(nchunk * QTR_ICP_NT * 8);
+  B.v.trace = (double*)take((size_t)max_iter_cap * 18 * 8);
+  B.v.spts = (float4*)take((size_t)cap_pts * 16);
+  B.v.snrm = (float4*)take((size_t)cap_pts * 16);
+  B.v.place = (int*)take((size_t)cap_pts * 8);
+  B.v.corr = (int*)take((size_t)cap_pts * 4);
+  e = hipHostMalloc((void**)&B.h_state, sizeof(QtrIcpState) + 64);
+  if (e != hipSuccess) return e;
+  B.h_bbox = (int*)(B.h_state + 1);
+  B.cap_pts = cap_pts;
+  return hipSuccess;
+}
+
+static hipError_t icp_reserve_cells(IcpBufs& B, int ncell) {
+  if (B.cells && B.cap_cells >= ncell) return hipSuccess;
+  if (B.cells) (void)hipFree(B.cells);
+  B.cells = nullptr;
+  int cap = 1 << 16;
+  while (cap < ncell) cap <<= 1;
+  hipError_t e = hipMalloc((void**)&B.cells, (size_t)2 * (cap + 1) * 4 + 512);
+  if (e != hipSuccess) return e;
+  B.cap_cells = cap;
+  return hipSuccess;
+}
+
+static void icp_free(IcpBufs& B) {
+  if (B.arena) (void)hipFree(B.arena);
+  if (B.cells) (void)hipFree(B.cells);
+  if (B.h_state) (void)hipHostFree(B.h_state);
+  B = IcpBufs{};
+}

@@ -22,6 +22,9 @@ REG_QUATRO, REG_TEASER = 0, 1
 DBG_GRAPH_BITMAP, DBG_CORE, DBG_PERM, DBG_NBR_OFFSETS, DBG_NBR_INDEX, DBG_NBR_DIST2, DBG_SPFH = 1, 2, 3, 4, 5, 6, 7
 DBG_NN_LARGE_OF_SMALL, DBG_NN_SMALL_OF_LARGE, DBG_VOX_SRC, DBG_VOX_TGT, DBG_CORR, DBG_MATCH_STATS = 8, 9, 10, 11, 12, 13
 DBG_SOLVER_STATE = 14
+DBG_ICP_CORR, DBG_ICP_TRACE, DBG_ICP_TIMES = 15, 16, 17
+ICP_POINT_TO_PLANE, ICP_POINT_TO_POINT = 0, 1
+ICP_STOP_NONE, ICP_STOP_MAX_ITERATIONS, ICP_STOP_TRANSFORMATION, ICP_STOP_FITNESS, ICP_STOP_TOO_FEW, ICP_STOP_DEGENERATE = range(6)
 
 
 class Limits(C.Structure):
@@ -82,11 +85,24 @@ class IpParams(C.Structure):
                 ("segment_theta", C.c_float), ("valid_point_num", C.c_int), ("valid_line_num", C.c_int)]
 
 
+class IcpParams(C.Structure):
+    _fields_ = [("max_correspondence_distance", C.c_double), ("transformation_epsilon", C.c_double),
+                ("euclidean_fitness_epsilon", C.c_double), ("max_iterations", C.c_int), ("method", C.c_int),
+                ("min_correspondences", C.c_int), ("normal_radius", C.c_float)]
+
+
+class IcpResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("valid", C.c_int), ("converged", C.c_int), ("stop_reason", C.c_int),
+                ("iterations", C.c_int), ("n_corr", C.c_int), ("T", C.c_double * 16), ("fitness", C.c_double),
+                ("rmse", C.c_double)]
+
+
 EXPORTS = [
     "qtr_create", "qtr_destroy", "qtr_last_error", "qtr_default_limits", "qtr_default_params", "qtr_demo_params",
     "qtr_default_frontend_params", "qtr_num_slots", "qtr_slot_stream", "qtr_voxelize", "qtr_fpfh", "qtr_match",
     "qtr_solve", "qtr_max_clique", "qtr_compute_tims", "qtr_scale_mask", "qtr_gnc_rotation2d",
     "qtr_cote_estimate", "qtr_cote_estimate_ranges", "qtr_ip_default_params", "qtr_segment_cloud", "qtr_pw_default_params", "qtr_patchwork", "qtr_gnc_rotation3d", "qtr_exact_stats", "qtr_read_kitti_bin", "qtr_write_pcd_xyz", "qtr_read_pcd_xyz", "qtr_register_pair", "qtr_register_pair_corr", "qtr_feature_pair", "qtr_get_stage_times", "qtr_get_nn_dir_times", "qtr_set_stage_events", "qtr_set_nn_event_stride", "qtr_get_nn_totals", "qtr_debug_fetch", "qtr_debug_math", "qtr_submit_batch", "qtr_wait", "qtr_set_batch_preprocess", "qtr_comm_unique_id", "qtr_comm_init", "qtr_gather_results", "qtr_gather_results_v", "qtr_comm_destroy",
+    "qtr_default_icp_params", "qtr_icp", "qtr_refine_pair",
 ]
 
 _lib = None
@@ -236,6 +252,10 @@ def load(path: str | None = None):
     lib.qtr_gather_results_v.argtypes = [C.c_void_p, C.POINTER(Result), C.c_int, C.POINTER(Result), C.c_int,
                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.qtr_comm_destroy.argtypes = [C.c_void_p]
+    lib.qtr_default_icp_params.argtypes = [C.POINTER(IcpParams)]
+    lib.qtr_icp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                            C.POINTER(IcpParams), C.POINTER(IcpResult), C.c_int]
+    lib.qtr_refine_pair.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(IcpParams), C.POINTER(IcpResult)]
     lib.qtr_comm_destroy.restype = None
     _libs[LIB_PATH] = lib
     if path is None:
@@ -276,6 +296,28 @@ def default_frontend_params(**kw) -> FrontendParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_icp_params(**kw) -> IcpParams:
+    """pcl::IterativeClosestPoint-style knobs (qtr_default_icp_params), fields overridden by keyword."""
+    p = IcpParams()
+    load().qtr_default_icp_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _guess16(guess):
+    if guess is None:
+        return None
+    g = np.ascontiguousarray(np.asarray(guess, dtype=np.float64).reshape(16))
+    return g
+
+
+def _icp_dict(res: IcpResult) -> dict:
+    return {"status": res.status, "valid": bool(res.valid), "converged": bool(res.converged),
+            "stop_reason": res.stop_reason, "iterations": res.iterations, "n_corr": res.n_corr,
+            "T": np.array(res.T[:]).reshape(4, 4), "fitness": res.fitness, "rmse": res.rmse}
 
 
 def _ptr(a):
@@ -688,6 +730,39 @@ class Handle:
             self._lib.qtr_get_nn_dir_times(self._h, slot, C.byref(d1), C.byref(d2))
         out["nn_dir1"], out["nn_dir2"] = d1.value, d2.value  # the two nearest-neighbour launches behind nn_kernel apart
         return out
+
+    def icp(self, src4, tgt4, tgt_normals4=None, guess=None, params: IcpParams | None = None, slot: int = 0) -> dict:
+        """6-DoF ICP of src4 onto tgt4 (qtr_icp).  numpy arrays (host) or contiguous [N,4] float32 torch device tensors
+        (all on the device: mem = QTR_MEM_DEVICE).  tgt_normals4 None: the target normals are computed at
+        params.normal_radius (point-to-plane).  Returns the result record as a dict (T row-major 4x4)."""
+        prm = params or default_icp_params()
+        if isinstance(src4, np.ndarray) or isinstance(tgt4, np.ndarray):
+            src4, tgt4 = _f4(src4), _f4(tgt4)
+            tgt_normals4 = None if tgt_normals4 is None else _f4(tgt_normals4)
+            ps, pt, pn, mem = src4.ctypes.data, tgt4.ctypes.data, (None if tgt_normals4 is None else
+                                                                   tgt_normals4.ctypes.data), MEM_HOST
+        else:
+            (ps, m1), (pt, m2) = _ptr(src4), _ptr(tgt4)
+            pn, m3 = _ptr(tgt_normals4)
+            assert m1 == m2 == MEM_DEVICE and m3 in (None, MEM_DEVICE), "torch tensors must all be on the device"
+            assert src4.dtype == tgt4.dtype and src4.shape[-1] == 4 and tgt4.shape[-1] == 4
+            mem = MEM_DEVICE
+        g = _guess16(guess)
+        res = IcpResult()
+        rc = self._lib.qtr_icp(self._h, slot, ps, int(src4.shape[0]), pt, int(tgt4.shape[0]), pn,
+                               None if g is None else g.ctypes.data, C.byref(prm), C.byref(res), mem)
+        self._check(rc)
+        return _icp_dict(res)
+
+    def refine_pair(self, guess=None, params: IcpParams | None = None, slot: int = 0) -> dict:
+        """Refines the slot's last register_pair / register_pair_corr on its voxelised clouds (qtr_refine_pair); guess
+        None = that registration's T."""
+        prm = params or default_icp_params()
+        g = _guess16(guess)
+        res = IcpResult()
+        rc = self._lib.qtr_refine_pair(self._h, slot, None if g is None else g.ctypes.data, C.byref(prm), C.byref(res))
+        self._check(rc)
+        return _icp_dict(res)
 
     def debug_fetch(self, what: int, dtype, slot: int = 0) -> np.ndarray:
         nbytes = self._lib.qtr_debug_fetch(self._h, slot, what, None, 0)
