@@ -317,7 +317,9 @@ QTR_API int qtr_feature_pair(qtr_handle* h, int slot, const float* src_raw4, int
  *                     record (its own status: QTR_OK, QTR_ERR_CLIQUE_TOO_SMALL, QTR_ERR_CAPACITY ...); the return
  *                     value is QTR_OK unless the job itself failed (HIP error, bad argument) — then every pair that
  *                     had finished keeps its record, pairs that were in flight read QTR_ERR_HIP, pairs never started
- *                     QTR_ERR_NOT_RUN, and the handle is drained and usable.
+ *                     QTR_ERR_NOT_RUN, and the handle is drained and usable.  A job of qtr_submit_batch_refine
+ *                     (below) also fills refined[i]; on a job failure a pair's refined record reads the same status
+ *                     as its result, or QTR_ERR_HIP when its registration finished and its refinement did not.
  * pairs / results must stay valid until qtr_wait returns; one job at a time per handle; every slot of the handle is
  * used (do not run slot calls concurrently).  mem as elsewhere (raw scans and the optional index lists). */
 typedef struct qtr_pair_desc {
@@ -449,6 +451,21 @@ QTR_API int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const f
  * QTR_ERR_BAD_ARG when the slot's last call was not a registration.  Leaves the registration's state untouched (it may be
  * refined again, with other parameters). */
 QTR_API int qtr_refine_pair(qtr_handle* h, int slot, const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res);
+/* Batched registration AND refinement: qtr_submit_batch's contract (validation, one job per handle, qtr_wait drives it),
+ * and refined[i] receives pair i's ICP refinement with `icp`.  results[i] are bit-identical to qtr_submit_batch's;
+ * refined[i] is bit-identical (T, iterations, stop_reason, n_corr, fitness, rmse, valid, converged) to what
+ * qtr_refine_pair(h, slot, NULL, icp, ...) returns right after a qtr_register_pair of that pair: ICP on the pair's voxelised
+ * clouds (the pre-processed sweeps' with qtr_set_batch_preprocess on) and the target normals of its FPFH stage, from the
+ * registration's T.  A pair with scans AND correspondences is refined on the scans' clouds from the T of the given
+ * correspondences.  Refined: pairs that ran the front end and whose result status is QTR_OK or QTR_ERR_CLIQUE_TOO_SMALL
+ * (refined[i].status = QTR_OK).  Every other pair — correspondences only, or a failed registration — gets
+ * refined[i].status = QTR_ERR_NOT_RUN, valid = 0 and T = results[i].T.  A NULL or invalid icp, or refined = NULL with
+ * B > 0: QTR_ERR_BAD_ARG with nothing enqueued.  pairs / results / refined must stay valid until qtr_wait returns; the
+ * records are host structs whatever `mem` says.  Each slot's ICP arena is allocated on the first refining batch.  After
+ * the job, qtr_refine_pair on any slot returns QTR_ERR_BAD_ARG, as after qtr_submit_batch. */
+QTR_API int qtr_submit_batch_refine(qtr_handle* h, const qtr_pair_desc* pairs, int B, const qtr_frontend_params* fp,
+                                    const qtr_params* prm, const qtr_icp_params* icp, qtr_result* results,
+                                    qtr_icp_result* refined, int mem);
 
 /* Inspection of intermediates of the LAST call on a slot (tests / parity debugging).  Copies up to
  * `bytes` bytes to host memory `dst`; returns the number of bytes the item holds, or <0 on error. */

@@ -68,7 +68,7 @@ struct Slot {
 struct Lane {
   int first_slot = 0, cap = 0;  // slots [first_slot, first_slot + cap)
   ViewStage stage;              // views of the group (pinned host + device)
-  int phase = 0;                // 0 idle, 1 voxelise pending, 2 matching pending, 3 solver pending
+  int phase = 0;                // 0 idle, 1 voxelise pending, 2 matching pending, 3 solver pending, 4-5 refine pending
   int first_pair = 0, count = 0;  // pairs [first_pair, first_pair + count) of the job are on this lane
   std::vector<int> active;      // indices g (0..count) of the pairs still alive after each chain's checks
   std::vector<int> ns, nt, L;   // per g
@@ -77,6 +77,10 @@ struct Lane {
   std::vector<const float4*> raw_s, raw_t;  // per g: the clouds the voxel grid read (device pointers) and their sizes
   std::vector<int> Ps, Pt;
   bool long_lists = false;      // the chunk's FPFH chain included k2_neighbors_big
+  // refine phase (qtr_submit_batch_refine): 4 target boxes pending, 5 iterations pending; ln.active = the refining pairs
+  std::vector<IcpView> iv;      // per position in ln.active: the pair's ICP view (its slot's arena, its clouds, its grid)
+  const IcpView* ref_views = nullptr;  // the same views in the stage (device)
+  int ref_it = 0, ref_nchunk = 1;      // iterations enqueued so far; the group's widest iteration launch
 };
 struct BatchJob {
   const qtr_pair_desc* pairs = nullptr;
@@ -87,6 +91,10 @@ struct BatchJob {
   int mem = QTR_MEM_HOST;
   bool active = false;
   std::vector<unsigned char> finished;  // per pair: its record is final (result or per-pair failure)
+  bool refine = false;                  // qtr_submit_batch_refine: the lanes refine their pairs after the solver chain
+  qtr_icp_params icp;
+  qtr_icp_result* refined = nullptr;
+  std::vector<unsigned char> ref_state; // per pair: 0 not refined, 1 refinement under way, 2 refined record final
 };
 
 struct qtr_handle {
@@ -588,6 +596,8 @@ static bool mail_payload_ok(const Slot& s, int idx, int seq) {
     case MAIL_SEQ_VOX1: return line_ok(MAIL_VOX1);
     case MAIL_SEQ_MATCH: return line_ok(MAIL_MATCH) && line_ok(MAIL_CNT0) && line_ok(MAIL_CNT1);
     case MAIL_SEQ_SOLVE: return solver_ok();
+    case MAIL_SEQ_ICP_BOX: return line_ok(MAIL_ICP_BOX);
+    case MAIL_SEQ_ICP: return line_ok(MAIL_ICP) && line_ok(MAIL_ICP + 16) && line_ok(MAIL_ICP + 32);
     default: return true;
   }
 }
@@ -1942,6 +1952,32 @@ static void batch_fail_pair(qtr_handle* h, int pair, int status) {
   ++h->job.done;
 }
 
+// ICP pieces the refine phase shares with qtr_icp / qtr_refine_pair (defined with them, below)
+static int check_icp_params(qtr_handle* h, const qtr_icp_params* p);
+static void icp_result_from(qtr_icp_result* res, const QtrIcpState& st);
+static QtrIcpCfg icp_cfg_of(const qtr_icp_params* prm);
+static bool icp_grid_of(IcpView& v, const int* bbox, double max_d, int cap_cells);
+static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const float4* d_tgt, int nt, const float4* d_nrm,
+                      const double* guess, const qtr_icp_params* prm, qtr_icp_result* res);
+
+// The refined records the job has not produced: QTR_ERR_NOT_RUN, valid = 0, T = the registration's T.  After a job
+// failure (failed), a pair whose registration did not finish takes its result's status, a pair whose refinement was under
+// way QTR_ERR_HIP.
+static void refine_fill_rest(qtr_handle* h, bool failed) {
+  BatchJob& J = h->job;
+  if (!J.refine) return;
+  for (int i = 0; i < J.B; ++i) {
+    if (J.ref_state[i] == 2) continue;
+    qtr_icp_result& q = J.refined[i];
+    memset(&q, 0, sizeof(q));
+    q.status = QTR_ERR_NOT_RUN;
+    if (failed && !J.finished[i]) q.status = J.results[i].status;
+    else if (failed && J.ref_state[i] == 1) q.status = QTR_ERR_HIP;
+    for (int k = 0; k < 16; ++k) q.T[k] = J.results[i].T[k];
+    J.ref_state[i] = 2;
+  }
+}
+
 // The job failed (HIP error, a lane that never published): drain what is in flight so the handle stays usable, and make
 // every record say what happened to its pair — pairs that had been started but did not finish get QTR_ERR_HIP, pairs
 // that were never started QTR_ERR_NOT_RUN; finished pairs keep their records.
@@ -1959,6 +1995,7 @@ static void batch_abort(qtr_handle* h) {
     memset(&J.results[i], 0, sizeof(qtr_result));
     J.results[i].status = i < J.next ? QTR_ERR_HIP : QTR_ERR_NOT_RUN;
   }
+  refine_fill_rest(h, true);
   J.active = false;
 }
 
@@ -1971,6 +2008,7 @@ static inline bool pair_has_corr(const qtr_pair_desc& pd) {
 }
 
 static int lane_start_chunk(qtr_handle* h, Lane& ln);
+static int lane_enqueue_refine(qtr_handle* h, Lane& ln);
 
 // Solver chain of the chunk: the pairs of `from_match` (survivors of the matching chain, ln.L / ln.csrc / ln.ctgt set)
 // plus the chunk's correspondence-only pairs.
@@ -2197,11 +2235,162 @@ static int lane_start_chunk(qtr_handle* h, Lane& ln) {
   return QTR_OK;
 }
 
+// Refine phase of the chunk (qtr_submit_batch_refine), while the chunk's slots still hold its clouds: the pairs of the
+// solver chain that ran the front end and registered (QTR_OK / QTR_ERR_CLIQUE_TOO_SMALL, mark_registration's rule) go
+// through the grouped ICP kernels (icp.hip), blockIdx.y = pair.  Three chains, each ending in the slots' mailboxes:
+//   target boxes (phase 4)  ->  host: every pair's cell grid  ->  grid build + iterations + states (phase 5)
+// With QTR_ICP_BLOCK = n the iterations go n launches per chain, and the lane stops enqueuing once every pair has stopped.
+static int lane_enqueue_refine(qtr_handle* h, Lane& ln) {
+  BatchJob& J = h->job;
+  Slot& lead = h->slots[ln.first_slot];
+  std::vector<int> ref;
+  for (int g : ln.active) {
+    const int pair = ln.first_pair + g;
+    const int st = J.results[pair].status;
+    if (pair_has_scans(J.pairs[pair]) && (st == QTR_OK || st == QTR_ERR_CLIQUE_TOO_SMALL)) {
+      ref.push_back(g);
+      J.ref_state[pair] = 1;
+    }
+  }
+  ln.active.swap(ref);
+  if (ln.active.empty()) return lane_start_chunk(h, ln);
+  const QtrIcpCfg cfg = icp_cfg_of(&J.icp);
+  const bool plane = J.icp.method == QTR_ICP_POINT_TO_PLANE;
+  ln.iv.clear();
+  std::vector<int> seqs;
+  int max_nt = 1;
+  for (int g : ln.active) {
+    Slot& s = h->slots[ln.first_slot + g];
+    IcpView v = s.icp.v;  // (the slot's arena; the single-pair calls' own view is left as it is)
+    // cloud[0] / cloud[1] hold the caller's source / target (as qtr_refine_pair reads them)
+    v.src = s.fb.cloud[0].vox;
+    v.tgt = s.fb.cloud[1].vox;
+    v.nrm = plane ? s.fb.cloud[1].normals : nullptr;
+    v.ns = ln.ns[g];
+    v.nt = ln.nt[g];
+    v.cfg = cfg;
+    v.cell_cnt = s.icp.cells;
+    v.cell_start = s.icp.cells + s.icp.cap_cells + 1;
+    v.mail = s.fb.mail;
+    ln.iv.push_back(v);
+    seqs.push_back(++s.seq);
+    max_nt = std::max(max_nt, v.nt);
+  }
+  const int G = (int)ln.iv.size();
+  const IcpView* dv = (const IcpView*)stage_push(&ln.stage, ln.iv.data(), sizeof(IcpView) * (size_t)G, lead.stream);
+  const int* ds = (const int*)stage_push(&ln.stage, seqs.data(), sizeof(int) * (size_t)G, lead.stream);
+  if (!dv || !ds) {
+    snprintf(h->err, sizeof(h->err), "batch refine: the lane's view stage is full");
+    return QTR_ERR_HIP;
+  }
+  QTR_HIP_TRY(h, icp_box_enqueue_group(dv, G, max_nt, ds, lead.stream));
+  ln.phase = 4;
+  return QTR_OK;
+}
+
+// the next block of iterations of the lane's refining pairs, ending in their states' mails
+static int lane_enqueue_icp_block(qtr_handle* h, Lane& ln) {
+  BatchJob& J = h->job;
+  Slot& lead = h->slots[ln.first_slot];
+  std::vector<int> seqs;
+  for (int g : ln.active) seqs.push_back(++h->slots[ln.first_slot + g].seq);
+  const int* ds = (const int*)stage_push(&ln.stage, seqs.data(), sizeof(int) * seqs.size(), lead.stream);
+  if (!ds) {
+    snprintf(h->err, sizeof(h->err), "batch refine: the lane's view stage is full");
+    return QTR_ERR_HIP;
+  }
+  const int block = h->icp_block > 0 ? h->icp_block : J.icp.max_iterations;
+  const int m = std::min(block, J.icp.max_iterations - ln.ref_it);
+  QTR_HIP_TRY(h, icp_iter_enqueue_group(ln.ref_views, (int)seqs.size(), ln.ref_nchunk, m, ds, lead.stream));
+  ln.ref_it += m;
+  ln.phase = 5;
+  return QTR_OK;
+}
+
+// phase 4: the boxes are in; every pair's grid (a pair without a finite target point is done: icp_device's early return)
+static int lane_refine_grids(qtr_handle* h, Lane& ln) {
+  BatchJob& J = h->job;
+  Slot& lead = h->slots[ln.first_slot];
+  std::vector<int> keep;
+  std::vector<IcpView> V;
+  std::vector<QtrIcpState> init;
+  int max_nt = 1, max_ncell = 1, max_nchunk = 1;
+  for (size_t k = 0; k < ln.active.size(); ++k) {
+    const int g = ln.active[k], pair = ln.first_pair + g;
+    Slot& s = h->slots[ln.first_slot + g];
+    IcpView v = ln.iv[k];
+    QtrIcpState st0;
+    qtr_icp_init(&st0, J.results[pair].T);
+    if (!icp_grid_of(v, s.mail + MAIL_ICP_BOX, J.icp.max_correspondence_distance, s.icp.cap_cells)) {
+      st0.reason = QTR_ICP_STOP_TOO_FEW;
+      icp_result_from(&J.refined[pair], st0);
+      J.refined[pair].status = QTR_OK;
+      J.ref_state[pair] = 2;
+      continue;
+    }
+    keep.push_back(g);
+    V.push_back(v);
+    init.push_back(st0);
+    max_nt = std::max(max_nt, v.nt);
+    max_ncell = std::max(max_ncell, v.ncell);
+    max_nchunk = std::max(max_nchunk, qtr_div_up(v.ns, QTR_ICP_CHUNK));
+  }
+  ln.active.swap(keep);
+  ln.iv.swap(V);
+  if (ln.active.empty()) return lane_start_chunk(h, ln);
+  const int G = (int)ln.iv.size();
+  const IcpView* dv = (const IcpView*)stage_push(&ln.stage, ln.iv.data(), sizeof(IcpView) * (size_t)G, lead.stream);
+  const QtrIcpState* di = (const QtrIcpState*)stage_push(&ln.stage, init.data(), sizeof(QtrIcpState) * (size_t)G, lead.stream);
+  if (!dv || !di) {
+    snprintf(h->err, sizeof(h->err), "batch refine: the lane's view stage is full");
+    return QTR_ERR_HIP;
+  }
+  QTR_HIP_TRY(h, icp_grid_enqueue_group(dv, di, G, max_nt, max_ncell, lead.stream));
+  ln.ref_views = dv;
+  ln.ref_nchunk = max_nchunk;
+  ln.ref_it = 0;
+  return lane_enqueue_icp_block(h, ln);
+}
+
+// phase 5: the states are in; another block, or the refined records and the next chunk
+static int lane_refine_done(qtr_handle* h, Lane& ln) {
+  BatchJob& J = h->job;
+  std::vector<QtrIcpState> st(ln.active.size());
+  bool all_stopped = true;
+  for (size_t k = 0; k < ln.active.size(); ++k) {
+    const Slot& s = h->slots[ln.first_slot + ln.active[k]];
+    int w[QTR_ICP_MAIL_WORDS];
+    for (int i = 0; i < QTR_ICP_MAIL_WORDS; ++i) w[i] = s.mail[MAIL_ICP + 16 * (i / 15) + i % 15];
+    memset(&st[k], 0, sizeof(QtrIcpState));
+    memcpy(&st[k], w, sizeof(w));
+    all_stopped = all_stopped && st[k].stop;
+  }
+  if (!all_stopped && ln.ref_it < J.icp.max_iterations) return lane_enqueue_icp_block(h, ln);
+  for (size_t k = 0; k < ln.active.size(); ++k) {
+    const int g = ln.active[k], pair = ln.first_pair + g;
+    Slot& s = h->slots[ln.first_slot + g];
+    icp_result_from(&J.refined[pair], st[k]);
+    J.refined[pair].status = QTR_OK;
+    J.ref_state[pair] = 2;
+    s.icp_ns = ln.iv[k].ns;  // (QTR_DBG_ICP_CORR / _TRACE of the slot: its last refinement)
+    s.icp_iters = st[k].iterations;
+  }
+  return lane_start_chunk(h, ln);
+}
+
 // advances the lane by at most one chain; *progress is set when it did
 static int lane_poll(qtr_handle* h, Lane& ln, bool* progress) {
   BatchJob& J = h->job;
   if (ln.phase == 0) return QTR_OK;
   Slot& lead = h->slots[ln.first_slot];
+  if (ln.phase == 4 || ln.phase == 5) {
+    for (int g : ln.active) {
+      Slot& s = h->slots[ln.first_slot + g];
+      if (!mail_ready(s, ln.phase == 4 ? MAIL_SEQ_ICP_BOX : MAIL_SEQ_ICP, s.seq)) return QTR_OK;
+    }
+    *progress = true;
+    return ln.phase == 4 ? lane_refine_grids(h, ln) : lane_refine_done(h, ln);
+  }
   if (ln.phase == 1) {
     for (int g : ln.active) {
       Slot& s = h->slots[ln.first_slot + g];
@@ -2355,6 +2544,14 @@ static int lane_poll(qtr_handle* h, Lane& ln, bool* progress) {
         if (rc1 == QTR_ERR_HIP) return rc1;
         J.finished[ln.first_pair + g] = 1;
         ++J.done;
+        if (J.refine && (r.status == QTR_OK || r.status == QTR_ERR_CLIQUE_TOO_SMALL)) {
+          // (the slot holds this pair's clouds as after qtr_register_pair: qtr_refine_pair's own path, on the slot's stream)
+          J.ref_state[ln.first_pair + g] = 1;
+          if (icp_device(h, s, s.fb.cloud[0].vox, s.last_ns, s.fb.cloud[1].vox, s.last_nt, s.fb.cloud[1].normals, r.T, &J.icp,
+                         &J.refined[ln.first_pair + g]) != QTR_OK)
+            return QTR_ERR_HIP;
+          J.ref_state[ln.first_pair + g] = 2;
+        }
         continue;
       }
       if (!given) QTR_HIP_TRY(h, gather_matched_enqueue(s.fb, Lm, s.m_src, s.m_tgt, lead.stream));  // no-op after the fused tail
@@ -2446,6 +2643,7 @@ static int lane_poll(qtr_handle* h, Lane& ln, bool* progress) {
     ++J.done;
   }
   if (copies) QTR_HIP_TRY(h, hipStreamSynchronize(lead.stream));
+  if (J.refine) return lane_enqueue_refine(h, ln);
   return lane_start_chunk(h, ln);
 }
 
@@ -2463,9 +2661,10 @@ int qtr_set_batch_preprocess(qtr_handle* h, const qtr_pw_params* pw, const qtr_i
   return QTR_OK;
 }
 
-int qtr_submit_batch(qtr_handle* h, const qtr_pair_desc* pairs, int B, const qtr_frontend_params* fp,
-                     const qtr_params* prm, qtr_result* results, int mem) {
-  if (!h) return QTR_ERR_BAD_ARG;
+// icp = NULL: plain qtr_submit_batch (no refine phase, no ICP arena, no extra launch)
+static int submit_batch_impl(qtr_handle* h, const qtr_pair_desc* pairs, int B, const qtr_frontend_params* fp,
+                             const qtr_params* prm, const qtr_icp_params* icp, qtr_result* results, qtr_icp_result* refined,
+                             int mem) {
   if (h->job.active) {
     snprintf(h->err, sizeof(h->err), "a batch is already in flight on this handle (call qtr_wait first)");
     return QTR_ERR_BAD_ARG;
@@ -2482,6 +2681,11 @@ int qtr_submit_batch(qtr_handle* h, const qtr_pair_desc* pairs, int B, const qtr
     return QTR_ERR_BAD_ARG;
   }
   QTR_HIP_TRY(h, hipSetDevice(h->device));
+  if (icp)  // every slot's ICP arena, and a cell table no grid of the refine phase outgrows (no allocation in the lanes)
+    for (auto& sl : h->slots) {
+      QTR_HIP_TRY(h, icp_reserve(sl.icp, h->lim.max_voxels, QTR_ICP_MAX_ITERATIONS));
+      QTR_HIP_TRY(h, icp_reserve_cells(sl.icp, QTR_ICP_BATCH_CELLS));
+    }
   BatchJob& J = h->job;
   J.pairs = pairs;
   J.B = B;
@@ -2497,6 +2701,16 @@ int qtr_submit_batch(qtr_handle* h, const qtr_pair_desc* pairs, int B, const qtr
     memset(&results[i], 0, sizeof(qtr_result));  // per-pair status can tell "never ran" from "ran, no solution")
     results[i].status = QTR_ERR_NOT_RUN;
   }
+  J.refine = icp != nullptr;
+  J.refined = refined;
+  J.ref_state.assign(J.refine ? (size_t)B : 0, 0);
+  if (J.refine) {
+    J.icp = *icp;
+    for (int i = 0; i < B; ++i) {
+      memset(&refined[i], 0, sizeof(qtr_icp_result));
+      refined[i].status = QTR_ERR_NOT_RUN;
+    }
+  }
   for (auto& ln : h->lanes) {
     const int r = lane_start_chunk(h, ln);
     if (r != QTR_OK) {
@@ -2505,6 +2719,29 @@ int qtr_submit_batch(qtr_handle* h, const qtr_pair_desc* pairs, int B, const qtr
     }
   }
   return QTR_OK;
+}
+
+int qtr_submit_batch(qtr_handle* h, const qtr_pair_desc* pairs, int B, const qtr_frontend_params* fp,
+                     const qtr_params* prm, qtr_result* results, int mem) {
+  if (!h) return QTR_ERR_BAD_ARG;
+  return submit_batch_impl(h, pairs, B, fp, prm, nullptr, results, nullptr, mem);
+}
+
+int qtr_submit_batch_refine(qtr_handle* h, const qtr_pair_desc* pairs, int B, const qtr_frontend_params* fp,
+                            const qtr_params* prm, const qtr_icp_params* icp, qtr_result* results, qtr_icp_result* refined,
+                            int mem) {
+  if (!h) return QTR_ERR_BAD_ARG;
+  if (h->job.active) {
+    snprintf(h->err, sizeof(h->err), "a batch is already in flight on this handle (call qtr_wait first)");
+    return QTR_ERR_BAD_ARG;
+  }
+  const int rc = check_icp_params(h, icp);
+  if (rc != QTR_OK) return rc;
+  if (B > 0 && !refined) {
+    snprintf(h->err, sizeof(h->err), "bad batch arguments (refined is NULL)");
+    return QTR_ERR_BAD_ARG;
+  }
+  return submit_batch_impl(h, pairs, B, fp, prm, icp, results, refined, mem);
 }
 
 int qtr_wait(qtr_handle* h) {
@@ -2537,7 +2774,11 @@ int qtr_wait(qtr_handle* h) {
           bool all = true;
           for (int g : ln.active) {
             Slot& s = h->slots[ln.first_slot + g];
-            const int idx = ln.phase == 1 ? MAIL_SEQ_VOX1 : ln.phase == 2 ? MAIL_SEQ_MATCH : MAIL_SEQ_SOLVE;
+            const int idx = ln.phase == 1   ? MAIL_SEQ_VOX1
+                            : ln.phase == 2 ? MAIL_SEQ_MATCH
+                            : ln.phase == 3 ? MAIL_SEQ_SOLVE
+                            : ln.phase == 4 ? MAIL_SEQ_ICP_BOX
+                                            : MAIL_SEQ_ICP;
             all = all && mail_ready(s, idx, s.seq);
           }
           if (!all) {
@@ -2554,6 +2795,7 @@ int qtr_wait(qtr_handle* h) {
     }
   }
   if (rc != QTR_OK) batch_abort(h);  // leave the handle usable, every record says what happened to its pair
+  else refine_fill_rest(h, false);
   J.active = false;
   return rc;
 }
@@ -2583,6 +2825,43 @@ static int check_icp_params(qtr_handle* h, const qtr_icp_params* p) {
     return QTR_ERR_BAD_ARG;
   }
   return QTR_OK;
+}
+
+static QtrIcpCfg icp_cfg_of(const qtr_icp_params* prm) {
+  QtrIcpCfg c;
+  c.max_d2 = prm->max_correspondence_distance * prm->max_correspondence_distance;
+  c.trans_eps = prm->transformation_epsilon;
+  c.fit_eps = prm->euclidean_fitness_epsilon;
+  c.max_iterations = prm->max_iterations;
+  c.method = prm->method;
+  c.min_corr = prm->min_correspondences > 0 ? prm->min_correspondences : (prm->method == QTR_ICP_POINT_TO_PLANE ? 6 : 3);
+  c.pad = 0;
+  return c;
+}
+
+// The cell grid of a target box (6 order-preserving encodings, k_icp_bbox): cells a little larger than the correspondence
+// distance (a rounding of the cell index cannot hide a point in reach); a grid of more than cap_cells cells takes larger
+// ones.  Any cell >= the distance finds the same nearest neighbour (ties go to the lowest index), so the grid's shape does
+// not change a result.  false: no finite target point.
+static bool icp_grid_of(IcpView& v, const int* bbox, double max_d, int cap_cells) {
+  if (bbox[0] > bbox[3]) return false;
+  double mx[3];
+  for (int a = 0; a < 3; ++a) {
+    v.mn[a] = (double)icp_dec(bbox[a]);
+    mx[a] = (double)icp_dec(bbox[3 + a]);
+  }
+  double cell = max_d * 1.001;
+  double nc = 0;
+  for (;;) {
+    nc = 1;
+    for (int a = 0; a < 3; ++a) nc *= floor((mx[a] - v.mn[a]) / cell) + 1.0;
+    if (nc <= (double)cap_cells) break;
+    cell *= 1.25;
+  }
+  v.cell = cell;
+  for (int a = 0; a < 3; ++a) v.dims[a] = (int)(floor((mx[a] - v.mn[a]) / cell) + 1.0);
+  v.ncell = v.dims[0] * v.dims[1] * v.dims[2];
+  return true;
 }
 
 static void icp_result_from(qtr_icp_result* res, const QtrIcpState& st) {
@@ -2617,13 +2896,7 @@ static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const
   v.nrm = prm->method == QTR_ICP_POINT_TO_PLANE ? d_nrm : nullptr;
   v.ns = ns;
   v.nt = nt;
-  v.cfg.max_d2 = prm->max_correspondence_distance * prm->max_correspondence_distance;
-  v.cfg.trans_eps = prm->transformation_epsilon;
-  v.cfg.fit_eps = prm->euclidean_fitness_epsilon;
-  v.cfg.max_iterations = prm->max_iterations;
-  v.cfg.method = prm->method;
-  v.cfg.min_corr = prm->min_correspondences > 0 ? prm->min_correspondences : (prm->method == QTR_ICP_POINT_TO_PLANE ? 6 : 3);
-  v.cfg.pad = 0;
+  v.cfg = icp_cfg_of(prm);
   const hipStream_t st = s.stream;
   QTR_HIP_TRY(h, hipEventRecord(s.ev[0], st));
   // bounding box of the finite target points (one read-back per call: it sizes the cell table)
@@ -2636,25 +2909,7 @@ static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const
   QTR_HIP_TRY(h, hipGetLastError());
   QTR_HIP_TRY(h, hipMemcpyAsync(B.h_bbox, v.bbox, 24, hipMemcpyDeviceToHost, st));
   QTR_HIP_TRY(h, hipStreamSynchronize(st));
-  if (B.h_bbox[0] > B.h_bbox[3]) return QTR_OK;  // no finite target point
-  double mx[3];
-  for (int a = 0; a < 3; ++a) {
-    v.mn[a] = (double)icp_dec(B.h_bbox[a]);
-    mx[a] = (double)icp_dec(B.h_bbox[3 + a]);
-  }
-  // cells a little larger than the correspondence distance (a rounding of the cell index cannot hide a point in reach);
-  // a grid of more than QTR_ICP_CELL_CAP cells takes larger ones
-  double cell = prm->max_correspondence_distance * 1.001;
-  double nc = 0;
-  for (;;) {
-    nc = 1;
-    for (int a = 0; a < 3; ++a) nc *= floor((mx[a] - v.mn[a]) / cell) + 1.0;
-    if (nc <= (double)QTR_ICP_CELL_CAP) break;
-    cell *= 1.25;
-  }
-  v.cell = cell;
-  for (int a = 0; a < 3; ++a) v.dims[a] = (int)(floor((mx[a] - v.mn[a]) / cell) + 1.0);
-  v.ncell = v.dims[0] * v.dims[1] * v.dims[2];
+  if (!icp_grid_of(v, B.h_bbox, prm->max_correspondence_distance, QTR_ICP_CELL_CAP)) return QTR_OK;  // no finite target point
   QTR_HIP_TRY(h, icp_reserve_cells(B, v.ncell));
   v.cell_cnt = B.cells;
   v.cell_start = B.cells + B.cap_cells + 1;

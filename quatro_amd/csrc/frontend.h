@@ -37,8 +37,10 @@ enum { MC_NCORR = 0, MC_HIDDEN_I = 1, MC_HIDDEN_J = 2, MC_NCROSS = 3, MC_NTUPLE 
 // pinned host memory, so a phase boundary costs one stream synchronisation and no copy launches.
 // MAIL_SEQ_*: written LAST (after a system-scope fence) with the sequence number the host passed to the phase, so
 // the host can simply watch that word instead of going through the runtime's stream wait.
+// MAIL_ICP_BOX / MAIL_ICP: the batched refinement's target box (one line) and ICP state (three lines, icp.hip).
 enum { MAIL_VOX0 = 0, MAIL_VOX1 = 16, MAIL_MATCH = 32, MAIL_CNT0 = 48, MAIL_CNT1 = 64, MAIL_SEQ_VOX0 = 96, MAIL_SEQ_VOX1 = 97,
-       MAIL_SEQ_MATCH = 98, MAIL_SEQ_SOLVE = 99, MAIL_SOLVER = 128, MAIL_INTS = 512 };
+       MAIL_SEQ_MATCH = 98, MAIL_SEQ_SOLVE = 99, MAIL_SEQ_ICP_BOX = 100, MAIL_SEQ_ICP = 101, MAIL_SOLVER = 128,
+       MAIL_ICP_BOX = 256, MAIL_ICP = 272, MAIL_INTS = 512 };
 
 struct CloudBufs {
   int* counts = nullptr;       // 16

@@ -12,6 +12,11 @@
 // partial per workgroup; the LAST workgroup to finish (atomic ticket) adds the partials in workgroup order, solves,
 // updates T and decides whether to stop.  Nobody waits for anybody, so no co-residency is assumed.  A launch that finds
 // the stop flag set returns at once, so the host can enqueue iterations without reading anything back.
+//
+// Batched refinement (qtr_submit_batch_refine): the same kernels in grouped form, blockIdx.y = pair of the lane's group,
+// the per-pair IcpViews in device memory (ViewExt).  Every pair runs the per-pair body the single-pair kernel runs
+// (d_icp_*), with its own chunk count in place of gridDim.x, so its arithmetic — partials, fold, ticket, solve — is the
+// single-pair call's bit for bit.  Workgroups past a pair's own end return before they take a ticket.
 #include "common.h"
 #include "frontend.h"
 #include "../../include/qtr_icp_math.h"
@@ -37,6 +42,8 @@ struct IcpView {
   unsigned* ticket;       // workgroups done in the current launch (reset by the last one)
   int* corr;              // [ns] target index of every source point in the last evaluated iteration (-1: none)
   double* trace;          // [max_iterations][18]
+  int* mail;              // grouped launches: device view of the slot's host mailbox (frontend.h MAIL_ICP*), else null
+  int pad_[2];
 };
 
 __device__ __forceinline__ int icp_enc(float f) {  // order-preserving int of a finite float (for atomicMin / Max)
@@ -77,8 +84,7 @@ __device__ __forceinline__ int icp_cell_of(const IcpView& v, float4 p) {
   return c[0] + v.dims[0] * (c[1] + v.dims[1] * c[2]);
 }
 
-__global__ __launch_bounds__(256) void k_icp_count(IcpView v) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void d_icp_count(const IcpView& v, int i) {
   if (i >= v.nt) return;
   const float4 p = v.tgt[i];
   if (!qtr_icp_finite3(p.x, p.y, p.z)) {
@@ -90,8 +96,9 @@ __global__ __launch_bounds__(256) void k_icp_count(IcpView v) {
   v.place[2 * i + 1] = atomicAdd(v.cell_cnt + lin, 1);
 }
 
-__global__ __launch_bounds__(256) void k_icp_place(IcpView v) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+__global__ __launch_bounds__(256) void k_icp_count(IcpView v) { d_icp_count(v, blockIdx.x * blockDim.x + threadIdx.x); }
+
+__device__ __forceinline__ void d_icp_place(const IcpView& v, int i) {
   if (i >= v.nt) return;
   const int lin = v.place[2 * i];
   if (lin < 0) return;
@@ -102,6 +109,8 @@ __global__ __launch_bounds__(256) void k_icp_place(IcpView v) {
   if (v.nrm) v.snrm[at] = v.nrm[i];
 }
 
+__global__ __launch_bounds__(256) void k_icp_place(IcpView v) { d_icp_place(v, blockIdx.x * blockDim.x + threadIdx.x); }
+
 __global__ __launch_bounds__(256) void k_icp_init(IcpView v, QtrIcpState init) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     *v.st = init;
@@ -111,7 +120,8 @@ __global__ __launch_bounds__(256) void k_icp_init(IcpView v, QtrIcpState init) {
 
 __device__ __forceinline__ double icp_shfl_down(double x, int off) { return __shfl_down(x, off, 64); }
 
-__global__ __launch_bounds__(256) void k_icp_iter(IcpView v) {
+// One workgroup (chunk `blk` of `nblk`) of one iteration of one pair.
+__device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) {
   __shared__ double s_w[4][QTR_ICP_NT];
   __shared__ double s_S[QTR_ICP_NT];
   __shared__ int s_last;
@@ -121,7 +131,7 @@ __global__ __launch_bounds__(256) void k_icp_iter(IcpView v) {
 #pragma unroll
   for (int k = 0; k < 16; ++k) T[k] = st->T[k];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i = blockIdx.x * QTR_ICP_CHUNK + tid;
+  const int i = blk * QTR_ICP_CHUNK + tid;
   double o[QTR_ICP_NT];
 #pragma unroll
   for (int k = 0; k < QTR_ICP_NT; ++k) o[k] = 0.0;
@@ -187,14 +197,14 @@ __global__ __launch_bounds__(256) void k_icp_iter(IcpView v) {
   if (tid < QTR_ICP_T_CNT + 1) {
     const double w4[4] = {s_w[0][tid], s_w[1][tid], s_w[2][tid], s_w[3][tid]};
     const double c = qtr_icp_chunk_sum(w4);
-    __hip_atomic_store((unsigned long long*)(v.partials + (size_t)blockIdx.x * QTR_ICP_NT + tid),
+    __hip_atomic_store((unsigned long long*)(v.partials + (size_t)blk * QTR_ICP_NT + tid),
                        (unsigned long long)__double_as_longlong(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __threadfence();
   __syncthreads();
   if (tid == 0) {
     const unsigned done = __hip_atomic_fetch_add(v.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = (done == gridDim.x - 1) ? 1 : 0;
+    s_last = (done == (unsigned)nblk - 1) ? 1 : 0;
   }
   __syncthreads();
   if (!s_last) return;
@@ -204,7 +214,7 @@ __global__ __launch_bounds__(256) void k_icp_iter(IcpView v) {
     if (tid < QTR_ICP_T_CNT + 1) {
       acc = __longlong_as_double((long long)__hip_atomic_load((unsigned long long*)(v.partials + tid), __ATOMIC_RELAXED,
                                                               __HIP_MEMORY_SCOPE_AGENT));
-      for (int c = 1; c < (int)gridDim.x; ++c)
+      for (int c = 1; c < nblk; ++c)
         acc = acc + __longlong_as_double((long long)__hip_atomic_load(
                         (unsigned long long*)(v.partials + (size_t)c * QTR_ICP_NT + tid), __ATOMIC_RELAXED,
                         __HIP_MEMORY_SCOPE_AGENT));
@@ -221,6 +231,114 @@ __global__ __launch_bounds__(256) void k_icp_iter(IcpView v) {
   }
 }
 
+__global__ __launch_bounds__(256) void k_icp_iter(IcpView v) { d_icp_iter(v, (int)blockIdx.x, (int)gridDim.x); }
+
+// ---- grouped forms (the lane's refine phase of qtr_submit_batch_refine): blockIdx.y = pair of the group ----------------
+// A launch is as wide as the group's largest pair; workgroups past the pair's own end return first.
+
+// bbox = the identity of min / max, ticket = 0 (the arena is not cleared on allocation; a single-pair call leaves its box)
+__global__ __launch_bounds__(64) void k_icp_box_init_group(ViewExt<IcpView> x) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  if (threadIdx.x < 6) v.bbox[threadIdx.x] = threadIdx.x < 3 ? 0x7fffffff : (int)0x80000000;
+  if (threadIdx.x == 0) __hip_atomic_store(v.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// k_icp_bbox per pair, folded in LDS first; the pair's last workgroup (ticket) mails the box to the host
+// (MAIL_ICP_BOX, then MAIL_SEQ_ICP_BOX = seqs[pair]) and leaves the ticket at zero
+__global__ __launch_bounds__(256) void k_icp_bbox_group(ViewExt<IcpView> x, const int* __restrict__ seqs) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  const int nblk = (v.nt + 255) / 256;
+  if ((int)blockIdx.x >= nblk) return;
+  __shared__ int s_bb[6];
+  __shared__ int s_last;
+  if (threadIdx.x < 6) s_bb[threadIdx.x] = threadIdx.x < 3 ? 0x7fffffff : (int)0x80000000;
+  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < v.nt) {
+    const float4 p = v.tgt[i];
+    if (qtr_icp_finite3(p.x, p.y, p.z)) {
+      atomicMin(s_bb + 0, icp_enc(p.x));
+      atomicMin(s_bb + 1, icp_enc(p.y));
+      atomicMin(s_bb + 2, icp_enc(p.z));
+      atomicMax(s_bb + 3, icp_enc(p.x));
+      atomicMax(s_bb + 4, icp_enc(p.y));
+      atomicMax(s_bb + 5, icp_enc(p.z));
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) atomicMin(v.bbox + threadIdx.x, s_bb[threadIdx.x]);
+  else if (threadIdx.x < 6) atomicMax(v.bbox + threadIdx.x, s_bb[threadIdx.x]);
+  __threadfence();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned done = __hip_atomic_fetch_add(v.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = (done == (unsigned)nblk - 1) ? 1 : 0;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  __threadfence();
+  if (threadIdx.x < 16) {
+    const int seq = seqs[blockIdx.y];
+    const int b = threadIdx.x < 6 ? __hip_atomic_load(v.bbox + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+    mail_store_line(v.mail + MAIL_ICP_BOX, threadIdx.x, b, seq);
+    __threadfence_system();
+    if (threadIdx.x == 0) {
+      __hip_atomic_store(v.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      v.mail[MAIL_SEQ_ICP_BOX] = seq;
+    }
+  }
+}
+
+// clean cell counters (what icp_device's memset does), then k_icp_init's state and ticket
+__global__ __launch_bounds__(256) void k_icp_prep_group(ViewExt<IcpView> x, const QtrIcpState* __restrict__ init) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e <= v.ncell; e += gridDim.x * blockDim.x) v.cell_cnt[e] = 0;
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    *v.st = init[blockIdx.y];
+    *v.ticket = 0u;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_icp_count_group(ViewExt<IcpView> x) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  d_icp_count(v, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+__global__ __launch_bounds__(1024) void k_icp_scan_group(ViewExt<IcpView> x) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  d_scan_i32_copy(v.cell_cnt, v.cell_start, v.ncell);
+}
+
+__global__ __launch_bounds__(256) void k_icp_place_group(ViewExt<IcpView> x) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  d_icp_place(v, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// one iteration of every pair of the group: the pair's chunk count stands where k_icp_iter has gridDim.x
+__global__ __launch_bounds__(256) void k_icp_iter_group(ViewExt<IcpView> x) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  const int nblk = (v.ns + QTR_ICP_CHUNK - 1) / QTR_ICP_CHUNK;
+  if ((int)blockIdx.x >= nblk) return;  // (before the stop flag and the ticket)
+  d_icp_iter(v, (int)blockIdx.x, nblk);
+}
+
+// the first QTR_ICP_MAIL_WORDS words of every pair's state into its mailbox (three tagged lines from MAIL_ICP), then
+// MAIL_SEQ_ICP = seqs[pair]; one wave per pair
+#define QTR_ICP_MAIL_WORDS 44  // T, prev_mse, fitness, rmse, iterations, stop, reason, n_corr, valid, converged
+static_assert(offsetof(QtrIcpState, pad) == QTR_ICP_MAIL_WORDS * 4, "the mailed words end where QtrIcpState's pad begins");
+static_assert(QTR_ICP_MAIL_WORDS <= 45 && MAIL_ICP + 48 <= MAIL_INTS, "three mailbox lines");
+__global__ __launch_bounds__(64) void k_icp_publish_group(ViewExt<IcpView> x, const int* __restrict__ seqs) {
+  const IcpView& v = x.ext[blockIdx.x];  // (inline on purpose: see ViewExt)
+  const int t = threadIdx.x;
+  if (t >= 48) return;  // (whole 16-lane groups stay together for the tag's shuffles)
+  const int seq = seqs[blockIdx.x];
+  const int w = (t >> 4) * 15 + (t & 15);  // state word carried by this lane (lane 15 of a line: the tag)
+  const int val = ((t & 15) < 15 && w < QTR_ICP_MAIL_WORDS) ? ((const int*)v.st)[w] : 0;
+  mail_store_line(v.mail + MAIL_ICP + 16 * (t >> 4), t & 15, val, seq);
+  __threadfence_system();
+  if (t == 0) v.mail[MAIL_SEQ_ICP] = seq;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------
 struct IcpBufs {
   int cap_pts = 0;        // points per cloud the arena holds
@@ -235,6 +353,9 @@ struct IcpBufs {
 // the largest cell table of a call: a grid that would need more cells takes larger cells (still >= the correspondence
 // distance, so the result is the same; only the candidate lists get longer)
 #define QTR_ICP_CELL_CAP (1 << 22)
+// the cell table every slot reserves for the batched refinement (qtr_submit_batch_refine), so that the lanes never allocate:
+// a larger grid takes larger cells (icp_grid_of).  2^20 cells of 1 m cover a 100 m x 100 m x 100 m box.
+#define QTR_ICP_BATCH_CELLS (1 << 20)
 
 static hipError_t icp_reserve(IcpBufs& B, int cap_pts, int max_iter_cap) {
   if (B.arena && B.cap_pts >= cap_pts) return hipSuccess;
@@ -286,4 +407,34 @@ static void icp_free(IcpBufs& B) {
   if (B.cells) (void)hipFree(B.cells);
   if (B.h_state) (void)hipHostFree(B.h_state);
   B = IcpBufs{};
+}
+
+// ---- grouped launches (the lane's refine phase, capi.hip) ---------------------------------------------------------------
+// dv: the group's views in device memory (the lane's ViewStage); dseqs: one mailbox sequence number per pair.
+static hipError_t icp_box_enqueue_group(const IcpView* dv, int G, int max_nt, const int* dseqs, hipStream_t st) {
+  const ViewExt<IcpView> x{dv, {0, 0, 0}};
+  hipLaunchKernelGGL(k_icp_box_init_group, dim3(1, G), dim3(64), 0, st, x);
+  hipLaunchKernelGGL(k_icp_bbox_group, dim3(qtr_div_up(max_nt, 256), G), dim3(256), 0, st, x, dseqs);
+  return hipGetLastError();
+}
+
+// the cell grids of the group (views carry their grids now) and the initial states
+static hipError_t icp_grid_enqueue_group(const IcpView* dv, const QtrIcpState* dinit, int G, int max_nt, int max_ncell,
+                                         hipStream_t st) {
+  const ViewExt<IcpView> x{dv, {0, 0, 0}};
+  hipLaunchKernelGGL(k_icp_prep_group, dim3(std::min(qtr_div_up((long long)max_ncell + 1, 256), 1024), G), dim3(256), 0, st,
+                     x, dinit);
+  hipLaunchKernelGGL(k_icp_count_group, dim3(qtr_div_up(max_nt, 256), G), dim3(256), 0, st, x);
+  hipLaunchKernelGGL(k_icp_scan_group, dim3(1, G), dim3(1024), 0, st, x);
+  hipLaunchKernelGGL(k_icp_place_group, dim3(qtr_div_up(max_nt, 256), G), dim3(256), 0, st, x);
+  return hipGetLastError();
+}
+
+// `launches` iterations of the group, then every pair's state into its mailbox
+static hipError_t icp_iter_enqueue_group(const IcpView* dv, int G, int max_nchunk, int launches, const int* dseqs,
+                                         hipStream_t st) {
+  const ViewExt<IcpView> x{dv, {0, 0, 0}};
+  for (int k = 0; k < launches; ++k) hipLaunchKernelGGL(k_icp_iter_group, dim3(max_nchunk, G), dim3(256), 0, st, x);
+  hipLaunchKernelGGL(k_icp_publish_group, dim3(G), dim3(64), 0, st, x, dseqs);
+  return hipGetLastError();
 }

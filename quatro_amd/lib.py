@@ -102,7 +102,7 @@ EXPORTS = [
     "qtr_default_frontend_params", "qtr_num_slots", "qtr_slot_stream", "qtr_voxelize", "qtr_fpfh", "qtr_match",
     "qtr_solve", "qtr_max_clique", "qtr_compute_tims", "qtr_scale_mask", "qtr_gnc_rotation2d",
     "qtr_cote_estimate", "qtr_cote_estimate_ranges", "qtr_ip_default_params", "qtr_segment_cloud", "qtr_pw_default_params", "qtr_patchwork", "qtr_gnc_rotation3d", "qtr_exact_stats", "qtr_read_kitti_bin", "qtr_write_pcd_xyz", "qtr_read_pcd_xyz", "qtr_register_pair", "qtr_register_pair_corr", "qtr_feature_pair", "qtr_get_stage_times", "qtr_get_nn_dir_times", "qtr_set_stage_events", "qtr_set_nn_event_stride", "qtr_get_nn_totals", "qtr_debug_fetch", "qtr_debug_math", "qtr_submit_batch", "qtr_wait", "qtr_set_batch_preprocess", "qtr_comm_unique_id", "qtr_comm_init", "qtr_gather_results", "qtr_gather_results_v", "qtr_comm_destroy",
-    "qtr_default_icp_params", "qtr_icp", "qtr_refine_pair",
+    "qtr_default_icp_params", "qtr_icp", "qtr_refine_pair", "qtr_submit_batch_refine",
 ]
 
 _lib = None
@@ -256,6 +256,9 @@ def load(path: str | None = None):
     lib.qtr_icp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                             C.POINTER(IcpParams), C.POINTER(IcpResult), C.c_int]
     lib.qtr_refine_pair.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(IcpParams), C.POINTER(IcpResult)]
+    lib.qtr_submit_batch_refine.argtypes = [C.c_void_p, C.POINTER(PairDesc), C.c_int, C.POINTER(FrontendParams),
+                                            C.POINTER(Params), C.POINTER(IcpParams), C.POINTER(Result),
+                                            C.POINTER(IcpResult), C.c_int]
     lib.qtr_comm_destroy.restype = None
     _libs[LIB_PATH] = lib
     if path is None:
@@ -620,6 +623,16 @@ class Handle:
         [L,4]) for a pair that brings pre-matched correspondences (qtr_pair_desc.src_corr4 / tgt_corr4): src = tgt = None
         runs the back end alone on them, scans AND correspondences run the scans' front end and the back end on the given
         correspondences.  Returns one result dict per pair, in order — the same dicts register_pair returns."""
+        return self._batch_host(pairs, fp, params, None, want_lists)
+
+    def register_batch_refine(self, pairs, fp: FrontendParams | None = None, params: Params | None = None,
+                              icp: IcpParams | None = None, want_lists=True):
+        """register_batch, and every registered pair refined by ICP on its voxelised clouds (qtr_submit_batch_refine).
+        Returns (results, refined): register_batch's result dicts and one ICP dict per pair — refine_pair's dict; a pair
+        that was not refined (no scans, failed registration) has status QTR_ERR_NOT_RUN and the registration's T."""
+        return self._batch_host(pairs, fp, params, icp or default_icp_params(), want_lists)
+
+    def _batch_host(self, pairs, fp, params, icp, want_lists):
         fp = fp or default_frontend_params()
         prm = params or demo_params()
         B = len(pairs)
@@ -642,7 +655,12 @@ class Handle:
                                 None if t_ is None else t_.ctypes.data, 0 if t_ is None else t_.shape[0], int(seed),
                                 cl.ctypes.data if want_lists else None, fin.ctypes.data if want_lists else None, cap,
                                 None if cs_ is None else cs_.ctypes.data, None if ct_ is None else ct_.ctypes.data, n_c)
-        self._check(self._lib.qtr_submit_batch(self._h, descs, B, C.byref(fp), C.byref(prm), results, MEM_HOST))
+        if icp is None:
+            self._check(self._lib.qtr_submit_batch(self._h, descs, B, C.byref(fp), C.byref(prm), results, MEM_HOST))
+        else:
+            refined = (IcpResult * max(B, 1))()
+            self._check(self._lib.qtr_submit_batch_refine(self._h, descs, B, C.byref(fp), C.byref(prm), C.byref(icp),
+                                                          results, refined, MEM_HOST))
         self._check(self._lib.qtr_wait(self._h))
         out = []
         for i in range(B):
@@ -654,7 +672,9 @@ class Handle:
                 out.append({"status": r.status, "valid": bool(r.valid), "T": np.array(r.T[:]).reshape(4, 4),
                             "cost": r.cost, "n_src": r.n_src, "n_tgt": r.n_tgt, "L": r.n_corr,
                             "n_clique": r.n_clique, "n_final": r.n_final, "n_rot_inliers": r.n_rot_inliers})
-        return out
+        if icp is None:
+            return out
+        return out, [_icp_dict(refined[i]) for i in range(B)]
 
     def set_batch_preprocess(self, pw: "PwParams | None" = None, ip: "IpParams | None" = None, on: bool = True):
         """Raw sweeps through register_batch: Patchwork ground removal + range-image segmentation in front of the voxel
@@ -671,6 +691,15 @@ class Handle:
         with corr=True — the pre-matched correspondences "cs" / "ct" the back end runs on (scans=False: the back end
         alone).  Inputs stay in HBM; only the result records come back.  Returns a list of dicts (status, valid, T,
         sizes)."""
+        return self._batch_dev(items, prm, fp, scans, corr, None)
+
+    def register_batch_dev_refine(self, items, prm: Params, icp: IcpParams | None = None, fp: FrontendParams | None = None,
+                                  scans: bool = True, corr: bool = False):
+        """register_batch_dev with the refinement of qtr_submit_batch_refine: returns (results, refined), the result dicts
+        of register_batch_dev and one ICP dict per pair (refine_pair's)."""
+        return self._batch_dev(items, prm, fp, scans, corr, icp or default_icp_params())
+
+    def _batch_dev(self, items, prm, fp, scans, corr, icp):
         fp = fp or default_frontend_params()
         B = len(items)
         descs = (PairDesc * max(B, 1))()
@@ -681,12 +710,20 @@ class Handle:
                                 int(it["fp"].seed), None, None, 0,
                                 it["cs"].data_ptr() if corr else None, it["ct"].data_ptr() if corr else None,
                                 it["cs"].shape[0] if corr else 0)
-        self._check(self._lib.qtr_submit_batch(self._h, descs, B, C.byref(fp), C.byref(prm), results, MEM_DEVICE))
+        if icp is None:
+            self._check(self._lib.qtr_submit_batch(self._h, descs, B, C.byref(fp), C.byref(prm), results, MEM_DEVICE))
+        else:
+            refined = (IcpResult * max(B, 1))()
+            self._check(self._lib.qtr_submit_batch_refine(self._h, descs, B, C.byref(fp), C.byref(prm), C.byref(icp),
+                                                          results, refined, MEM_DEVICE))
         self._check(self._lib.qtr_wait(self._h))
-        return [{"status": r.status, "valid": bool(r.valid), "T": np.array(r.T[:]).reshape(4, 4), "cost": r.cost,
-                 "n_src": r.n_src, "n_tgt": r.n_tgt, "L": r.n_corr, "n_clique": r.n_clique, "n_final": r.n_final,
-                 "n_rot_inliers": r.n_rot_inliers, "gnc_iters": r.gnc_iters}
-                for r in results[:B]]
+        out = [{"status": r.status, "valid": bool(r.valid), "T": np.array(r.T[:]).reshape(4, 4), "cost": r.cost,
+                "n_src": r.n_src, "n_tgt": r.n_tgt, "L": r.n_corr, "n_clique": r.n_clique, "n_final": r.n_final,
+                "n_rot_inliers": r.n_rot_inliers, "gnc_iters": r.gnc_iters}
+               for r in results[:B]]
+        if icp is None:
+            return out
+        return out, [_icp_dict(refined[i]) for i in range(B)]
 
     # ---- multi-GPU: RCCL all-gather of the result records through the C ABI (one handle = one rank)
     def comm_init(self, unique_id: bytes, rank: int, world: int):
