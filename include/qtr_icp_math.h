@@ -9,13 +9,28 @@
 //   fixed-shape sum                   qtr_icp_fold64 inside every 64-point wave, (w0 + w1) + (w2 + w3) inside every
 //                                     256-point chunk, then the chunks in ascending order (qtr_icp_chunk_sum)
 //   update and stopping               qtr_icp_step
+//
+// Plane-to-plane (method 2, Generalized ICP): every point's covariance is the plane-regularised one of
+// pcl::GeneralizedIterativeClosestPoint / fast_gicp, eigenvalues (1, 1, eps) with the normal as the eps direction, which
+// is a function of the unit normal alone: C = I - (1 - eps) n n^T.  eps is the constant QTR_ICP_GICP_EPSILON: it is fixed
+// because qtr_icp_params may not grow (C++ callers are built against its layout).  Per correspondence p <-> b with the
+// source normal a (source frame), the target normal nb and T = [R t] (qtr_icp_gicp_terms):
+//   Sigma = C_b + R C_a R^T = 2 I - (1 - eps)(n n^T + m m^T),  n = nb / |nb|,  m = R (a / |a|)
+//   M = Sigma^-1 by adjugate / determinant (det >= 8 eps for unit normals: no pivoting), held fixed inside the iteration
+//   d = q - b,  J = [ -[q]x | I ]  (the left-multiplied increment T <- [dR dt] T of qtr_icp_compose)
+//   terms: J^T M J (21), J^T M d (6), d^T M d, d^2, 1 - solved and stepped exactly like point-to-plane.
+// A source point whose normal is not finite or has zero length takes no part (skipped before the search); a
+// correspondence whose target normal is not finite or has zero length is dropped (qtr_icp_normal_ok).
 #pragma once
 #include "qtr_math.h"
 
 #define QTR_ICP_CHUNK 256  // source points per workgroup / partial sum
 #define QTR_ICP_NT 32      // terms per point (30 used, padded)
 
+#define QTR_ICP_GICP_EPSILON 1e-3  // plane regularisation of method 2 (pcl's gicp_epsilon); fixed, see above
+
 // term layout.  Point-to-plane: 21 upper entries of J^T J (row-major upper triangle), 6 of J^T r, sum r^2.
+// Plane-to-plane: the same places with J^T M J, J^T M d, d^T M d.
 // Point-to-point: sum q t^T (9, row-major: [3a+b] = q_a t_b), sum q (3), sum t (3).  Both: sum d^2, count.
 #define QTR_ICP_T_JTR 21
 #define QTR_ICP_T_R2 27
@@ -42,7 +57,7 @@ typedef struct QtrIcpCfg {
   double trans_eps;     // transformation_epsilon
   double fit_eps;       // euclidean_fitness_epsilon
   int max_iterations;
-  int method;           // 0 point-to-plane, 1 point-to-point
+  int method;           // 0 point-to-plane, 1 point-to-point, 2 plane-to-plane
   int min_corr;
   int pad;
 } QtrIcpCfg;
@@ -108,6 +123,93 @@ QM_HD void qtr_icp_terms(int method, const double* q, float tx, float ty, float 
   }
   o[QTR_ICP_T_D2] = d2;
   o[QTR_ICP_T_CNT] = 1.0;
+}
+
+// a normal plane-to-plane can use: finite and of non-zero length
+QM_HD bool qtr_icp_normal_ok(float x, float y, float z) {
+  if (!qtr_icp_finite3(x, y, z)) return false;
+  const double a = (double)x, b = (double)y, c = (double)z;
+  return ((a * a + b * b) + c * c) > 0.0;
+}
+
+// the plane-to-plane terms of one correspondence: q = T p, source normal a (source frame), target point t with normal
+// nb; d2 = qtr_icp_d2(q, t).  Both normals pass qtr_icp_normal_ok.  With K = [q]x and J = [-K | I]:
+//   J^T M J = [[-K M K, K M], [(K M)^T, M]],  J^T M d = (q x (M d), M d)
+// B = K M is formed column by column (B[:, j] = q x M[:, j]), then -K M K = B K^T row by row (row i = q x B[i, :]).
+QM_HD void qtr_icp_gicp_terms(const double* T, const double* q, float ax, float ay, float az, float tx, float ty, float tz,
+                              float bx, float by, float bz, double d2, double* o /* [QTR_ICP_NT] */) {
+  const double k = 1.0 - QTR_ICP_GICP_EPSILON;
+  double a0 = (double)ax, a1 = (double)ay, a2 = (double)az;
+  const double la = sqrt((a0 * a0 + a1 * a1) + a2 * a2);
+  a0 = a0 / la;
+  a1 = a1 / la;
+  a2 = a2 / la;
+  double n0 = (double)bx, n1 = (double)by, n2 = (double)bz;
+  const double ln = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+  n0 = n0 / ln;
+  n1 = n1 / ln;
+  n2 = n2 / ln;
+  const double m0 = (T[0] * a0 + T[1] * a1) + T[2] * a2;
+  const double m1 = (T[4] * a0 + T[5] * a1) + T[6] * a2;
+  const double m2 = (T[8] * a0 + T[9] * a1) + T[10] * a2;
+  // Sigma (symmetric): s00 s01 s02 s11 s12 s22
+  const double s00 = 2.0 - k * (n0 * n0 + m0 * m0);
+  const double s01 = -(k * (n0 * n1 + m0 * m1));
+  const double s02 = -(k * (n0 * n2 + m0 * m2));
+  const double s11 = 2.0 - k * (n1 * n1 + m1 * m1);
+  const double s12 = -(k * (n1 * n2 + m1 * m2));
+  const double s22 = 2.0 - k * (n2 * n2 + m2 * m2);
+  // M = adj(Sigma) / det(Sigma)
+  const double c00 = s11 * s22 - s12 * s12;
+  const double c01 = s02 * s12 - s01 * s22;
+  const double c02 = s01 * s12 - s02 * s11;
+  const double c11 = s00 * s22 - s02 * s02;
+  const double c12 = s01 * s02 - s00 * s12;
+  const double c22 = s00 * s11 - s01 * s01;
+  const double det = (s00 * c00 + s01 * c01) + s02 * c02;
+  const double M00 = c00 / det, M01 = c01 / det, M02 = c02 / det, M11 = c11 / det, M12 = c12 / det, M22 = c22 / det;
+  const double q0 = q[0], q1 = q[1], q2 = q[2];
+  const double d0 = q0 - (double)tx, d1 = q1 - (double)ty, dz = q2 - (double)tz;
+  const double e0 = (M00 * d0 + M01 * d1) + M02 * dz;  // M d
+  const double e1 = (M01 * d0 + M11 * d1) + M12 * dz;
+  const double e2 = (M02 * d0 + M12 * d1) + M22 * dz;
+  // B = K M
+  const double B00 = q1 * M02 - q2 * M01, B01 = q1 * M12 - q2 * M11, B02 = q1 * M22 - q2 * M12;
+  const double B10 = q2 * M00 - q0 * M02, B11 = q2 * M01 - q0 * M12, B12 = q2 * M02 - q0 * M22;
+  const double B20 = q0 * M01 - q1 * M00, B21 = q0 * M11 - q1 * M01, B22 = q0 * M12 - q1 * M02;
+  // -K M K = B K^T (symmetric; the upper triangle)
+  o[0] = q1 * B02 - q2 * B01;
+  o[1] = q2 * B00 - q0 * B02;
+  o[2] = q0 * B01 - q1 * B00;
+  o[3] = B00;
+  o[4] = B01;
+  o[5] = B02;
+  o[6] = q2 * B10 - q0 * B12;
+  o[7] = q0 * B11 - q1 * B10;
+  o[8] = B10;
+  o[9] = B11;
+  o[10] = B12;
+  o[11] = q0 * B21 - q1 * B20;
+  o[12] = B20;
+  o[13] = B21;
+  o[14] = B22;
+  o[15] = M00;
+  o[16] = M01;
+  o[17] = M02;
+  o[18] = M11;
+  o[19] = M12;
+  o[20] = M22;
+  o[QTR_ICP_T_JTR + 0] = q1 * e2 - q2 * e1;
+  o[QTR_ICP_T_JTR + 1] = q2 * e0 - q0 * e2;
+  o[QTR_ICP_T_JTR + 2] = q0 * e1 - q1 * e0;
+  o[QTR_ICP_T_JTR + 3] = e0;
+  o[QTR_ICP_T_JTR + 4] = e1;
+  o[QTR_ICP_T_JTR + 5] = e2;
+  o[QTR_ICP_T_R2] = (d0 * e0 + d1 * e1) + dz * e2;
+  o[QTR_ICP_T_D2] = d2;
+  o[QTR_ICP_T_CNT] = 1.0;
+  o[30] = 0.0;
+  o[31] = 0.0;
 }
 
 // the in-wave fold of 64 values: for off = 32, 16, ..., 1: p[l] += p[l + off] (l < off) — what __shfl_down does
@@ -220,7 +322,7 @@ QM_HD void qtr_icp_step(const QtrIcpCfg* cfg, const double* S, QtrIcpState* st, 
   const double mse = S[QTR_ICP_T_D2] / n;
   st->fitness = mse;
   double dR[9], dt[3];
-  if (cfg->method == 0) {
+  if (cfg->method != 1) {  // (plane-to-plane: the same solve over J^T M J, J^T M d, d^T M d)
     st->rmse = sqrt(S[QTR_ICP_T_R2] / n);
     double b[6], x[6];
     for (int a = 0; a < 6; ++a) b[a] = -S[QTR_ICP_T_JTR + a];

@@ -27,6 +27,8 @@
  *                         registrations)                   examples/run_global_registration.cpp:97-108
  *   qtr_icp / qtr_refine_pair <- pcl::IterativeClosestPoint(WithNormals)::align after the registration (the
  *                         reference class derives from pcl::Registration, include/quatro.hpp:131,151)
+ *   qtr_gicp          <- pcl::GeneralizedIterativeClosestPoint::align, the plane-to-plane refinement usually paired
+ *                         with Quatro (same pcl::Registration surface; covariances from the normals of both clouds)
  *   qtr_register_pair  <- the demo's whole path        examples/run_global_registration.cpp:206-246
  *                         (voxelize x2, FPFHManager::setFeaturePair include/fpfh_manager.hpp:98-153,
  *                          setInputSource/setInputTarget/computeTransformation)
@@ -410,6 +412,12 @@ QTR_API int qtr_get_nn_dir_times(qtr_handle* h, int slot, float* dir1_ms, float*
  *                   a correspondence whose target normal is not finite
  *   point-to-plane: one Gauss-Newton step of sum ((q - t) . n)^2 per iteration (6x6 LDL^T; rotation increment from the
  *                   normalised quaternion (1, w/2)); point-to-point: the closed-form rotation of the cross-covariance
+ *   plane-to-plane: Generalized ICP (pcl::GeneralizedIterativeClosestPoint / fast_gicp) with the plane-regularised
+ *                   covariances C = I - (1 - eps) n n^T of BOTH clouds' normals, eps = QTR_ICP_GICP_EPSILON = 1e-3
+ *                   (include/qtr_icp_math.h; a constant, because this struct may not grow): one Gauss-Newton step of
+ *                   sum d^T (C_b + R C_a R^T)^-1 d per iteration, d = q - t, the same 6x6 solve and increment.  A source
+ *                   point whose normal is not finite or has zero length is skipped; a correspondence whose target normal
+ *                   is not finite or has zero length is dropped.  rmse = sqrt(mean d^T M d), fitness = mean d^2
  *   stopping:       max_iterations updates; max |dT - I| <= transformation_epsilon; |mse - mse_prev| <=
  *                   euclidean_fitness_epsilon * mse_prev; fewer than min_correspondences correspondences (valid = 0, T the
  *                   last good transform); a rank-deficient system, e.g. a single plane (valid = 0, T the last good one)
@@ -417,6 +425,7 @@ QTR_API int qtr_get_nn_dir_times(qtr_handle* h, int slot, float* dir1_ms, float*
  * The arena is allocated on a slot's first ICP call. */
 #define QTR_ICP_POINT_TO_PLANE 0
 #define QTR_ICP_POINT_TO_POINT 1
+#define QTR_ICP_PLANE_TO_PLANE 2
 #define QTR_ICP_MAX_ITERATIONS 1000 /* largest max_iterations accepted */
 /* qtr_icp_result.stop_reason */
 #define QTR_ICP_STOP_NONE 0
@@ -430,10 +439,11 @@ typedef struct qtr_icp_params {
   double transformation_epsilon;      /* 1e-7: max |dT - I| of an update (setTransformationEpsilon) */
   double euclidean_fitness_epsilon;   /* 1e-6: relative change of the correspondences' MSE (setEuclideanFitnessEpsilon) */
   int max_iterations;                 /* 30 (setMaximumIterations), 1 .. QTR_ICP_MAX_ITERATIONS */
-  int method;                         /* QTR_ICP_POINT_TO_PLANE */
-  int min_correspondences;            /* 0 = the method's minimum: 6 point-to-plane, 3 point-to-point */
-  float normal_radius;                /* 0.5 m: target normals of qtr_icp when the caller passes none (the FPFH stage's
-                                         normal estimation); qtr_refine_pair uses the registration's normals */
+  int method;                         /* QTR_ICP_POINT_TO_PLANE (default), _POINT_TO_POINT, _PLANE_TO_PLANE */
+  int min_correspondences;            /* 0 = the method's minimum: 6 point-to-plane, 3 point-to-point,
+                                         4 plane-to-plane */
+  float normal_radius;                /* 0.5 m: normals of qtr_icp / qtr_gicp that the caller does not pass (the FPFH
+                                         stage's normal estimation); qtr_refine_pair uses the registration's normals */
 } qtr_icp_params;
 typedef struct qtr_icp_result {
   int status, valid, converged, stop_reason, iterations, n_corr;
@@ -442,12 +452,19 @@ typedef struct qtr_icp_result {
   double rmse;    /* sqrt of the mean squared residual the method minimises (point-to-plane distance / point distance) */
 } qtr_icp_result;
 QTR_API void qtr_default_icp_params(qtr_icp_params* p);
-/* src4 (n_s) / tgt4 (n_t): 16-byte records; tgt_normals4: n_t records nx,ny,nz,* (point-to-plane; NULL: computed at
- * normal_radius).  guess: row-major 4x4 (NULL = identity).  mem: where the clouds live. */
+/* src4 (n_s) / tgt4 (n_t): 16-byte records; tgt_normals4: n_t records nx,ny,nz,* (point-to-plane and plane-to-plane; NULL:
+ * computed at normal_radius).  guess: row-major 4x4 (NULL = identity).  mem: where the clouds live.  Plane-to-plane
+ * computes the source normals at normal_radius: qtr_icp(method 2) is qtr_gicp with src_normals4 = NULL. */
 QTR_API int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const float* tgt4, int n_t, const float* tgt_normals4,
                     const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res, int mem);
+/* Plane-to-plane for callers who bring both normal sets: src_normals4 (n_s records, source frame) / tgt_normals4 (n_t
+ * records); either may be NULL (computed at normal_radius).  prm->method must be QTR_ICP_PLANE_TO_PLANE (QTR_ERR_BAD_ARG
+ * otherwise).  Validation, capacity, empty clouds, mem and the QTR_DBG_ICP_* items as qtr_icp. */
+QTR_API int qtr_gicp(qtr_handle* h, int slot, const float* src4, int n_s, const float* src_normals4, const float* tgt4, int n_t,
+                     const float* tgt_normals4, const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res, int mem);
 /* Refines the slot's last qtr_register_pair / qtr_register_pair_corr on its voxelised clouds (the CALLER's source and
- * target) and the target normals its FPFH stage left in the slot: no copy, no recomputation.  guess NULL = that call's T.
+ * target) and the normals its FPFH stage left in the slot (the target's; plane-to-plane: the source's too): no copy, no
+ * recomputation.  guess NULL = that call's T.
  * QTR_ERR_BAD_ARG when the slot's last call was not a registration.  Leaves the registration's state untouched (it may be
  * refined again, with other parameters). */
 QTR_API int qtr_refine_pair(qtr_handle* h, int slot, const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res);

@@ -2,7 +2,9 @@
 // align / hasConverged / getFitnessScore / getFinalTransformation) over qtr_icp: the 6-DoF refinement that normally
 // follows a Quatro registration (Quatro recovers yaw and translation; roll and pitch come only from estimated_RyRx_).
 // Point-to-plane by default (pcl::IterativeClosestPointWithNormals; target normals at normal_radius unless
-// setTargetNormals gives them), point-to-point on request.  Host code only; link with -lquatro_hip.  Compiles with the
+// setTargetNormals gives them), point-to-point or plane-to-plane (Generalized ICP: qtr_gicp with the normals of both
+// clouds, given by setSourceNormals / setTargetNormals or computed at normal_radius) on request.  Host code only; link
+// with -lquatro_hip.  Compiles with the
 // built-in stand-ins of quatro.hpp and against PCL / Eigen (QUATRO_HAVE_PCL).
 #ifndef QUATRO_ICP_H
 #define QUATRO_ICP_H
@@ -20,7 +22,11 @@ class IterativeClosestPoint {
   using PointCloudTarget = pcl::PointCloud<PointTarget>;
   using PointCloudSourceConstPtr = typename PointCloudSource::ConstPtr;
   using PointCloudTargetConstPtr = typename PointCloudTarget::ConstPtr;
-  enum class Method { POINT_TO_PLANE = QTR_ICP_POINT_TO_PLANE, POINT_TO_POINT = QTR_ICP_POINT_TO_POINT };
+  enum class Method {
+    POINT_TO_PLANE = QTR_ICP_POINT_TO_PLANE,
+    POINT_TO_POINT = QTR_ICP_POINT_TO_POINT,
+    PLANE_TO_PLANE = QTR_ICP_PLANE_TO_PLANE
+  };
 
   explicit IterativeClosestPoint(Method method = Method::POINT_TO_PLANE) {
     qtr_default_icp_params(&prm_);
@@ -28,12 +34,21 @@ class IterativeClosestPoint {
     final_ = Eigen::Matrix4d::Identity();
   }
 
-  void setInputSource(const PointCloudSourceConstPtr& cloud) { input_ = cloud; }
+  void setInputSource(const PointCloudSourceConstPtr& cloud) {
+    input_ = cloud;
+    src_normals_.clear();
+  }
+  // nx, ny, nz per source point, source frame (plane-to-plane); not called: computed at normal_radius on the device
+  void setSourceNormals(const std::vector<float>& nxyz) {
+    src_normals_.assign(nxyz.size() / 3 * 4, 0.f);
+    for (size_t i = 0; i < nxyz.size() / 3; ++i)
+      for (int a = 0; a < 3; ++a) src_normals_[4 * i + a] = nxyz[3 * i + a];
+  }
   void setInputTarget(const PointCloudTargetConstPtr& cloud) {
     target_ = cloud;
     normals_.clear();
   }
-  // nx, ny, nz per target point (point-to-plane); not called: computed at normal_radius on the device
+  // nx, ny, nz per target point (point-to-plane, plane-to-plane); not called: computed at normal_radius on the device
   void setTargetNormals(const std::vector<float>& nxyz) {
     normals_.assign(nxyz.size() / 3 * 4, 0.f);
     for (size_t i = 0; i < nxyz.size() / 3; ++i)
@@ -57,8 +72,15 @@ class IterativeClosestPoint {
       for (int c = 0; c < 4; ++c) g[4 * r + c] = guess(r, c);
     const int ns = static_cast<int>(input_->points.size()), nt = static_cast<int>(target_->points.size());
     const bool given = !normals_.empty() && normals_.size() == 4 * target_->points.size();
-    const int rc = qtr_icp(h, slot_lease.slot, xyz4(input_->points), ns, xyz4(target_->points), nt,
-                           given ? normals_.data() : nullptr, g, &prm_, &res_, QTR_MEM_HOST);
+    int rc;
+    if (prm_.method == QTR_ICP_PLANE_TO_PLANE) {
+      const bool src_given = !src_normals_.empty() && src_normals_.size() == 4 * input_->points.size();
+      rc = qtr_gicp(h, slot_lease.slot, xyz4(input_->points), ns, src_given ? src_normals_.data() : nullptr,
+                    xyz4(target_->points), nt, given ? normals_.data() : nullptr, g, &prm_, &res_, QTR_MEM_HOST);
+    } else {
+      rc = qtr_icp(h, slot_lease.slot, xyz4(input_->points), ns, xyz4(target_->points), nt,
+                   given ? normals_.data() : nullptr, g, &prm_, &res_, QTR_MEM_HOST);
+    }
     check(h, rc);
     for (int r = 0; r < 4; ++r)
       for (int c = 0; c < 4; ++c) final_(r, c) = res_.T[4 * r + c];
@@ -80,7 +102,7 @@ class IterativeClosestPoint {
  private:
   PointCloudSourceConstPtr input_;
   PointCloudTargetConstPtr target_;
-  std::vector<float> normals_;
+  std::vector<float> normals_, src_normals_;
   qtr_icp_params prm_;
   qtr_icp_result res_{};
   Eigen::Matrix4d final_;

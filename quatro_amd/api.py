@@ -418,16 +418,18 @@ class IterativeClosestPoint:
     """pcl::IterativeClosestPoint's surface (setInputSource / setInputTarget / the convergence knobs / align) over
     qtr_icp: the 6-DoF refinement that normally follows a global registration.  Point-to-plane by default
     (pcl::IterativeClosestPointWithNormals; target normals at normal_radius unless setTargetNormals gives them),
-    point-to-point with method="point_to_point".  Everything numerical runs on the device."""
+    point-to-point with method="point_to_point", plane-to-plane (Generalized ICP; setSourceNormals / setTargetNormals, or
+    both normal sets at normal_radius) with method="plane_to_plane".  Everything numerical runs on the device."""
 
     def __init__(self, handle=None, method: str = "point_to_plane", normal_radius: float = 0.5):
-        if method not in ("point_to_plane", "point_to_point"):
-            raise ValueError("method must be 'point_to_plane' or 'point_to_point'")
+        methods = {"point_to_plane": _ql.ICP_POINT_TO_PLANE, "point_to_point": _ql.ICP_POINT_TO_POINT,
+                   "plane_to_plane": _ql.ICP_PLANE_TO_PLANE}
+        if method not in methods:
+            raise ValueError("method must be 'point_to_plane', 'point_to_point' or 'plane_to_plane'")
         self._h = handle
-        self.params_ = _ql.default_icp_params(
-            method=_ql.ICP_POINT_TO_PLANE if method == "point_to_plane" else _ql.ICP_POINT_TO_POINT,
-            normal_radius=float(normal_radius))
+        self.params_ = _ql.default_icp_params(method=methods[method], normal_radius=float(normal_radius))
         self.input_ = None
+        self.source_normals_ = None
         self.target_ = None
         self.target_normals_ = None
         self.final_transformation_ = np.eye(4)
@@ -436,10 +438,15 @@ class IterativeClosestPoint:
 
     def setInputSource(self, cloud):
         self.input_ = _as_cloud(cloud)
+        self.source_normals_ = None
 
     def setInputTarget(self, cloud):
         self.target_ = _as_cloud(cloud)
         self.target_normals_ = None
+
+    def setSourceNormals(self, normals):
+        """plane-to-plane only: the source's normals (source frame); None = computed at normal_radius"""
+        self.source_normals_ = None if normals is None else _as_cloud(normals)
 
     def setTargetNormals(self, normals):
         self.target_normals_ = None if normals is None else _as_cloud(normals)
@@ -468,7 +475,11 @@ class IterativeClosestPoint:
         if self.input_ is None or self.target_ is None:
             raise ValueError("input clouds not set")
         h = self._h or _handle()
-        r = h.icp(self.input_, self.target_, self.target_normals_, np.eye(4) if guess is None else guess, self.params_)
+        g = np.eye(4) if guess is None else guess
+        if self.params_.method == _ql.ICP_PLANE_TO_PLANE:
+            r = h.gicp(self.input_, self.target_, self.source_normals_, self.target_normals_, g, self.params_)
+        else:
+            r = h.icp(self.input_, self.target_, self.target_normals_, g, self.params_)
         self.result_ = r
         self.final_transformation_ = r["T"]
         self.converged_ = r["converged"]

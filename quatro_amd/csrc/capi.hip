@@ -1958,7 +1958,7 @@ static void icp_result_from(qtr_icp_result* res, const QtrIcpState& st);
 static QtrIcpCfg icp_cfg_of(const qtr_icp_params* prm);
 static bool icp_grid_of(IcpView& v, const int* bbox, double max_d, int cap_cells);
 static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const float4* d_tgt, int nt, const float4* d_nrm,
-                      const double* guess, const qtr_icp_params* prm, qtr_icp_result* res);
+                      const float4* d_src_nrm, const double* guess, const qtr_icp_params* prm, qtr_icp_result* res);
 
 // The refined records the job has not produced: QTR_ERR_NOT_RUN, valid = 0, T = the registration's T.  After a job
 // failure (failed), a pair whose registration did not finish takes its result's status, a pair whose refinement was under
@@ -2255,7 +2255,8 @@ static int lane_enqueue_refine(qtr_handle* h, Lane& ln) {
   ln.active.swap(ref);
   if (ln.active.empty()) return lane_start_chunk(h, ln);
   const QtrIcpCfg cfg = icp_cfg_of(&J.icp);
-  const bool plane = J.icp.method == QTR_ICP_POINT_TO_PLANE;
+  const bool gicp = J.icp.method == QTR_ICP_PLANE_TO_PLANE;
+  const bool plane = J.icp.method == QTR_ICP_POINT_TO_PLANE || gicp;
   ln.iv.clear();
   std::vector<int> seqs;
   int max_nt = 1;
@@ -2266,6 +2267,7 @@ static int lane_enqueue_refine(qtr_handle* h, Lane& ln) {
     v.src = s.fb.cloud[0].vox;
     v.tgt = s.fb.cloud[1].vox;
     v.nrm = plane ? s.fb.cloud[1].normals : nullptr;
+    v.src_nrm = gicp ? s.fb.cloud[0].normals : nullptr;  // (the FPFH stage's; nothing writes them after it)
     v.ns = ln.ns[g];
     v.nt = ln.nt[g];
     v.cfg = cfg;
@@ -2301,7 +2303,8 @@ static int lane_enqueue_icp_block(qtr_handle* h, Lane& ln) {
   }
   const int block = h->icp_block > 0 ? h->icp_block : J.icp.max_iterations;
   const int m = std::min(block, J.icp.max_iterations - ln.ref_it);
-  QTR_HIP_TRY(h, icp_iter_enqueue_group(ln.ref_views, (int)seqs.size(), ln.ref_nchunk, m, ds, lead.stream));
+  QTR_HIP_TRY(h, icp_iter_enqueue_group(ln.ref_views, (int)seqs.size(), ln.ref_nchunk, m, ds, lead.stream,
+                                        J.icp.method == QTR_ICP_PLANE_TO_PLANE));
   ln.ref_it += m;
   ln.phase = 5;
   return QTR_OK;
@@ -2547,7 +2550,8 @@ static int lane_poll(qtr_handle* h, Lane& ln, bool* progress) {
         if (J.refine && (r.status == QTR_OK || r.status == QTR_ERR_CLIQUE_TOO_SMALL)) {
           // (the slot holds this pair's clouds as after qtr_register_pair: qtr_refine_pair's own path, on the slot's stream)
           J.ref_state[ln.first_pair + g] = 1;
-          if (icp_device(h, s, s.fb.cloud[0].vox, s.last_ns, s.fb.cloud[1].vox, s.last_nt, s.fb.cloud[1].normals, r.T, &J.icp,
+          if (icp_device(h, s, s.fb.cloud[0].vox, s.last_ns, s.fb.cloud[1].vox, s.last_nt, s.fb.cloud[1].normals,
+                         s.fb.cloud[0].normals, r.T, &J.icp,
                          &J.refined[ln.first_pair + g]) != QTR_OK)
             return QTR_ERR_HIP;
           J.ref_state[ln.first_pair + g] = 2;
@@ -2819,7 +2823,7 @@ static int check_icp_params(qtr_handle* h, const qtr_icp_params* p) {
   if (!p || !icp_finite(p->max_correspondence_distance) || !(p->max_correspondence_distance > 0) ||
       !icp_finite(p->transformation_epsilon) || p->transformation_epsilon < 0 || !icp_finite(p->euclidean_fitness_epsilon) ||
       p->euclidean_fitness_epsilon < 0 || p->max_iterations < 1 || p->max_iterations > QTR_ICP_MAX_ITERATIONS ||
-      (p->method != QTR_ICP_POINT_TO_PLANE && p->method != QTR_ICP_POINT_TO_POINT) || p->min_correspondences < 0 ||
+      (p->method != QTR_ICP_POINT_TO_PLANE && p->method != QTR_ICP_POINT_TO_POINT && p->method != QTR_ICP_PLANE_TO_PLANE) || p->min_correspondences < 0 ||
       !icp_finite((double)p->normal_radius) || !(p->normal_radius > 0)) {
     snprintf(h->err, sizeof(h->err), "invalid ICP parameter");
     return QTR_ERR_BAD_ARG;
@@ -2834,7 +2838,10 @@ static QtrIcpCfg icp_cfg_of(const qtr_icp_params* prm) {
   c.fit_eps = prm->euclidean_fitness_epsilon;
   c.max_iterations = prm->max_iterations;
   c.method = prm->method;
-  c.min_corr = prm->min_correspondences > 0 ? prm->min_correspondences : (prm->method == QTR_ICP_POINT_TO_PLANE ? 6 : 3);
+  c.min_corr = prm->min_correspondences > 0 ? prm->min_correspondences
+               : prm->method == QTR_ICP_POINT_TO_PLANE ? 6
+               : prm->method == QTR_ICP_PLANE_TO_PLANE ? 4  // (pcl GICP's min_number_correspondences_)
+                                                       : 3;
   c.pad = 0;
   return c;
 }
@@ -2878,7 +2885,7 @@ static void icp_result_from(qtr_icp_result* res, const QtrIcpState& st) {
 // The loop on device-resident clouds: grid over the target, then the iterations, one launch each, with no host read-back
 // inside a block of h->icp_block launches (0: all max_iterations of them in one go).
 static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const float4* d_tgt, int nt, const float4* d_nrm,
-                      const double* guess, const qtr_icp_params* prm, qtr_icp_result* res) {
+                      const float4* d_src_nrm, const double* guess, const qtr_icp_params* prm, qtr_icp_result* res) {
   QtrIcpState init;
   qtr_icp_init(&init, guess);
   init.reason = QTR_ICP_STOP_TOO_FEW;  // (what an empty cloud reports; the device state starts RUNNING)
@@ -2888,12 +2895,18 @@ static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const
   s.icp_iters = 0;
   s.icp_ms[0] = s.icp_ms[1] = 0.f;
   if (ns == 0 || nt == 0) return QTR_OK;
+  const bool gicp = prm->method == QTR_ICP_PLANE_TO_PLANE;
+  if (gicp && (!d_nrm || !d_src_nrm)) {
+    snprintf(h->err, sizeof(h->err), "plane-to-plane needs the normals of both clouds");
+    return QTR_ERR_BAD_ARG;
+  }
   IcpBufs& B = s.icp;
   QTR_HIP_TRY(h, icp_reserve(B, h->lim.max_voxels, QTR_ICP_MAX_ITERATIONS));
   IcpView& v = B.v;
   v.src = d_src;
   v.tgt = d_tgt;
-  v.nrm = prm->method == QTR_ICP_POINT_TO_PLANE ? d_nrm : nullptr;
+  v.nrm = (prm->method == QTR_ICP_POINT_TO_PLANE || gicp) ? d_nrm : nullptr;
+  v.src_nrm = gicp ? d_src_nrm : nullptr;
   v.ns = ns;
   v.nt = nt;
   v.cfg = icp_cfg_of(prm);
@@ -2928,7 +2941,10 @@ static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const
   const int block = h->icp_block > 0 ? h->icp_block : prm->max_iterations;
   for (int it = 0; it < prm->max_iterations;) {
     const int m = std::min(block, prm->max_iterations - it);
-    for (int k = 0; k < m; ++k) hipLaunchKernelGGL(k_icp_iter, dim3(nchunk), dim3(256), 0, st, v);
+    for (int k = 0; k < m; ++k) {
+      if (gicp) hipLaunchKernelGGL(k_icp_iter_gicp, dim3(nchunk), dim3(256), 0, st, v);
+      else hipLaunchKernelGGL(k_icp_iter, dim3(nchunk), dim3(256), 0, st, v);
+    }
     QTR_HIP_TRY(h, hipGetLastError());
     it += m;
     if (it >= prm->max_iterations) break;
@@ -2967,6 +2983,8 @@ int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const float* tg
   Slot& s = *sp;
   int rc = check_icp_params(h, prm);
   if (rc != QTR_OK) return res->status = rc;
+  if (prm->method == QTR_ICP_PLANE_TO_PLANE)  // (the source normals at normal_radius)
+    return qtr_gicp(h, slot, src4, n_s, nullptr, tgt4, n_t, tgt_normals4, guess, prm, res, mem);
   if (n_s < 0 || n_t < 0 || (n_s > 0 && !src4) || (n_t > 0 && !tgt4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE) ||
       (guess && !icp_guess_ok(guess))) {
     snprintf(h->err, sizeof(h->err), "bad ICP arguments");
@@ -2977,7 +2995,7 @@ int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const float* tg
     return res->status = QTR_ERR_CAPACITY;
   }
   const double* g = guess ? guess : kIcpIdentity;
-  if (n_s == 0 || n_t == 0) return icp_device(h, s, nullptr, n_s, nullptr, n_t, nullptr, g, prm, res);
+  if (n_s == 0 || n_t == 0) return icp_device(h, s, nullptr, n_s, nullptr, n_t, nullptr, nullptr, g, prm, res);
   QTR_HIP_TRY(h, hipSetDevice(h->device));
   const float4 *d_s = (const float4*)src4, *d_t = (const float4*)tgt4, *d_n = (const float4*)tgt_normals4;
   const bool plane = prm->method == QTR_ICP_POINT_TO_PLANE;
@@ -3010,7 +3028,78 @@ int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const float* tg
     }
     d_n = cb.normals;
   }
-  rc = icp_device(h, s, d_s, n_s, d_t, n_t, d_n, g, prm, res);
+  rc = icp_device(h, s, d_s, n_s, d_t, n_t, d_n, nullptr, g, prm, res);
+  return res->status = rc;
+}
+
+// Plane-to-plane on any two clouds.  The source lives in the first cloud's arena and the target in the second's (as after a
+// registration); a normal set the caller does not bring comes from the normal stage of the FPFH chain (qtr_fpfh's dense
+// mode) at normal_radius — both clouds in one chain when both are missing.
+int qtr_gicp(qtr_handle* h, int slot, const float* src4, int n_s, const float* src_normals4, const float* tgt4, int n_t,
+             const float* tgt_normals4, const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res, int mem) {
+  Slot* sp = get_slot(h, slot);
+  if (!sp || !res) return QTR_ERR_BAD_ARG;
+  memset(res, 0, sizeof(*res));
+  Slot& s = *sp;
+  int rc = check_icp_params(h, prm);
+  if (rc != QTR_OK) return res->status = rc;
+  if (prm->method != QTR_ICP_PLANE_TO_PLANE) {
+    snprintf(h->err, sizeof(h->err), "qtr_gicp: method must be QTR_ICP_PLANE_TO_PLANE");
+    return res->status = QTR_ERR_BAD_ARG;
+  }
+  if (n_s < 0 || n_t < 0 || (n_s > 0 && !src4) || (n_t > 0 && !tgt4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE) ||
+      (guess && !icp_guess_ok(guess))) {
+    snprintf(h->err, sizeof(h->err), "bad ICP arguments");
+    return res->status = QTR_ERR_BAD_ARG;
+  }
+  if (n_s > h->lim.max_voxels || n_t > h->lim.max_voxels) {
+    snprintf(h->err, sizeof(h->err), "ICP cloud exceeds max_voxels=%d", h->lim.max_voxels);
+    return res->status = QTR_ERR_CAPACITY;
+  }
+  const double* g = guess ? guess : kIcpIdentity;
+  if (n_s == 0 || n_t == 0) return icp_device(h, s, nullptr, n_s, nullptr, n_t, nullptr, nullptr, g, prm, res);
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  const float4* d_pts[2] = {(const float4*)src4, (const float4*)tgt4};
+  const float4* d_nrm[2] = {(const float4*)src_normals4, (const float4*)tgt_normals4};
+  const int n[2] = {n_s, n_t};
+  if (mem == QTR_MEM_HOST) {  // (staging: the raw-scan buffers, max_points >= max_voxels points each)
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, src4, (size_t)n_s * 16, hipMemcpyHostToDevice, s.stream));
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_tgt, tgt4, (size_t)n_t * 16, hipMemcpyHostToDevice, s.stream));
+    d_pts[0] = s.in_src;
+    d_pts[1] = s.in_tgt;
+    for (int c = 0; c < 2; ++c)
+      if (d_nrm[c]) {
+        QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[c].normals, d_nrm[c], (size_t)n[c] * 16, hipMemcpyHostToDevice, s.stream));
+        d_nrm[c] = s.fb.cloud[c].normals;
+      }
+  }
+  const int first = d_nrm[0] ? 1 : 0, last = d_nrm[1] ? 0 : 1;  // clouds first..last need their normals
+  if (first <= last) {
+    int nn[2] = {0, 0};
+    for (int c = first; c <= last; ++c) {
+      CloudBufs& cb = s.fb.cloud[c];
+      QTR_HIP_TRY(h, hipMemcpyAsync(cb.vox, d_pts[c], (size_t)n[c] * 16, hipMemcpyDeviceToDevice, s.stream));
+      QTR_HIP_TRY(h, hipMemsetAsync(cb.counts, 0, 16 * sizeof(int), s.stream));
+      QTR_HIP_TRY(h, set_count_enqueue(cb, CNT_NVOX, n[c], s.stream));
+      nn[c - first] = n[c];
+    }
+    QTR_TRY(ensure_long_arenas(h, s));
+    QTR_HIP_TRY(h, fpfh_enqueue(s.fb, first, last - first + 1, nn, prm->normal_radius, prm->normal_radius, s.stream, false,
+                                false, true));
+    for (int c = first; c <= last; ++c)
+      QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32 + 16 * c, s.fb.cloud[c].counts, 16 * sizeof(int), hipMemcpyDeviceToHost,
+                                    s.stream));
+    QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
+    for (int c = first; c <= last; ++c) {
+      if (s.pinned_i32[16 * c + CNT_NBR_CAPACITY]) {
+        snprintf(h->err, sizeof(h->err), "normals at normal_radius: radius-neighbour lists exceed the long-list arena "
+                 "(qtr_limits.max_long_neighbors is %d)", h->lim.max_long_neighbors);
+        return res->status = QTR_ERR_CAPACITY;
+      }
+      d_nrm[c] = s.fb.cloud[c].normals;
+    }
+  }
+  rc = icp_device(h, s, d_pts[0], n_s, d_pts[1], n_t, d_nrm[1], d_nrm[0], g, prm, res);
   return res->status = rc;
 }
 
@@ -3031,9 +3120,10 @@ int qtr_refine_pair(qtr_handle* h, int slot, const double guess[16], const qtr_i
   }
   QTR_HIP_TRY(h, hipSetDevice(h->device));
   // cloud[0] / cloud[1] hold the caller's source / target whatever roles the matcher gave them (it swaps views, not
-  // arenas); the target's normals are the FPFH stage's, at the registration's normal_radius
+  // arenas); the normals of both are the FPFH stage's, at the registration's normal_radius (k2_normals is their only
+  // writer: the matcher and the solver read them or leave them alone)
   rc = icp_device(h, s, s.fb.cloud[0].vox, s.last_ns, s.fb.cloud[1].vox, s.last_nt, s.fb.cloud[1].normals,
-                  guess ? guess : s.reg_T, prm, res);
+                  s.fb.cloud[0].normals, guess ? guess : s.reg_T, prm, res);
   return res->status = rc;
 }
 

@@ -1,4 +1,5 @@
-// icp.hip — 6-DoF ICP refinement on the device (qtr_icp / qtr_refine_pair): point-to-plane (default) and point-to-point.
+// icp.hip — 6-DoF ICP refinement on the device (qtr_icp / qtr_gicp / qtr_refine_pair): point-to-plane (default),
+// point-to-point and plane-to-plane (Generalized ICP; its iteration is an instantiation of its own, d_icp_iter<true>).
 //
 // Per call: a uniform cell grid over the finite target points (cell side >= max_correspondence_distance, so the
 // nearest target within reach of any query lies in its 27 neighbouring cells), built by a counting sort into the
@@ -24,7 +25,7 @@
 struct IcpView {
   const float4* src;      // [ns] source points (x, y, z, *)
   const float4* tgt;      // [nt] target points
-  const float4* nrm;      // [nt] target normals (point-to-plane) or null
+  const float4* nrm;      // [nt] target normals (point-to-plane, plane-to-plane) or null
   int ns, nt;
   float4* spts;           // [nt] finite target points in cell order, w = original index
   float4* snrm;           // [nt] their normals in the same order
@@ -43,7 +44,7 @@ struct IcpView {
   int* corr;              // [ns] target index of every source point in the last evaluated iteration (-1: none)
   double* trace;          // [max_iterations][18]
   int* mail;              // grouped launches: device view of the slot's host mailbox (frontend.h MAIL_ICP*), else null
-  int pad_[2];
+  const float4* src_nrm;  // [ns] source normals, source frame (plane-to-plane) or null
 };
 
 __device__ __forceinline__ int icp_enc(float f) {  // order-preserving int of a finite float (for atomicMin / Max)
@@ -120,7 +121,9 @@ __global__ __launch_bounds__(256) void k_icp_init(IcpView v, QtrIcpState init) {
 
 __device__ __forceinline__ double icp_shfl_down(double x, int off) { return __shfl_down(x, off, 64); }
 
-// One workgroup (chunk `blk` of `nblk`) of one iteration of one pair.
+// One workgroup (chunk `blk` of `nblk`) of one iteration of one pair.  GICP: the plane-to-plane body (cfg.method == 2);
+// the other two methods share the instantiation they always had.
+template <bool GICP>
 __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) {
   __shared__ double s_w[4][QTR_ICP_NT];
   __shared__ double s_S[QTR_ICP_NT];
@@ -139,7 +142,12 @@ __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) 
     const float4 p = v.src[i];
     int best = -1, bat = -1;
     double bd = 0.0, q[3];
-    if (qtr_icp_finite3(p.x, p.y, p.z) && v.ncell > 0) {
+    bool use = qtr_icp_finite3(p.x, p.y, p.z) && v.ncell > 0;
+    if (GICP && use) {  // (a source point without a usable normal is skipped before the search)
+      const float4 a = v.src_nrm[i];
+      use = qtr_icp_normal_ok(a.x, a.y, a.z);
+    }
+    if (use) {
       qtr_icp_transform(T, p.x, p.y, p.z, q);
       int lo[3], hi[3];
       bool any = true;
@@ -174,15 +182,29 @@ __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) 
           }
       }
     }
-    if (best >= 0 && v.cfg.method == 0) {
-      const float4 n = v.snrm[bat];
-      if (!qtr_icp_finite3(n.x, n.y, n.z)) best = -1;
-    }
-    v.corr[i] = best;
-    if (best >= 0) {
-      const float4 t = v.spts[bat];
-      const float4 n = v.cfg.method == 0 ? v.snrm[bat] : make_float4(0.f, 0.f, 0.f, 0.f);
-      qtr_icp_terms(v.cfg.method, q, t.x, t.y, t.z, n.x, n.y, n.z, bd, o);
+    if (GICP) {
+      if (best >= 0) {
+        const float4 n = v.snrm[bat];
+        if (!qtr_icp_normal_ok(n.x, n.y, n.z)) best = -1;
+      }
+      v.corr[i] = best;
+      if (best >= 0) {
+        const float4 t = v.spts[bat];
+        const float4 n = v.snrm[bat];
+        const float4 a = v.src_nrm[i];
+        qtr_icp_gicp_terms(T, q, a.x, a.y, a.z, t.x, t.y, t.z, n.x, n.y, n.z, bd, o);
+      }
+    } else {
+      if (best >= 0 && v.cfg.method == 0) {
+        const float4 n = v.snrm[bat];
+        if (!qtr_icp_finite3(n.x, n.y, n.z)) best = -1;
+      }
+      v.corr[i] = best;
+      if (best >= 0) {
+        const float4 t = v.spts[bat];
+        const float4 n = v.cfg.method == 0 ? v.snrm[bat] : make_float4(0.f, 0.f, 0.f, 0.f);
+        qtr_icp_terms(v.cfg.method, q, t.x, t.y, t.z, n.x, n.y, n.z, bd, o);
+      }
     }
   }
   // fixed-shape sum: the shfl_down fold inside each wave (qtr_icp_fold64), then (w0 + w1) + (w2 + w3)
@@ -231,7 +253,8 @@ __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) 
   }
 }
 
-__global__ __launch_bounds__(256) void k_icp_iter(IcpView v) { d_icp_iter(v, (int)blockIdx.x, (int)gridDim.x); }
+__global__ __launch_bounds__(256) void k_icp_iter(IcpView v) { d_icp_iter<false>(v, (int)blockIdx.x, (int)gridDim.x); }
+__global__ __launch_bounds__(256) void k_icp_iter_gicp(IcpView v) { d_icp_iter<true>(v, (int)blockIdx.x, (int)gridDim.x); }
 
 // ---- grouped forms (the lane's refine phase of qtr_submit_batch_refine): blockIdx.y = pair of the group ----------------
 // A launch is as wide as the group's largest pair; workgroups past the pair's own end return first.
@@ -319,7 +342,13 @@ __global__ __launch_bounds__(256) void k_icp_iter_group(ViewExt<IcpView> x) {
   const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
   const int nblk = (v.ns + QTR_ICP_CHUNK - 1) / QTR_ICP_CHUNK;
   if ((int)blockIdx.x >= nblk) return;  // (before the stop flag and the ticket)
-  d_icp_iter(v, (int)blockIdx.x, nblk);
+  d_icp_iter<false>(v, (int)blockIdx.x, nblk);
+}
+__global__ __launch_bounds__(256) void k_icp_iter_gicp_group(ViewExt<IcpView> x) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  const int nblk = (v.ns + QTR_ICP_CHUNK - 1) / QTR_ICP_CHUNK;
+  if ((int)blockIdx.x >= nblk) return;
+  d_icp_iter<true>(v, (int)blockIdx.x, nblk);
 }
 
 // the first QTR_ICP_MAIL_WORDS words of every pair's state into its mailbox (three tagged lines from MAIL_ICP), then
@@ -430,11 +459,14 @@ static hipError_t icp_grid_enqueue_group(const IcpView* dv, const QtrIcpState* d
   return hipGetLastError();
 }
 
-// `launches` iterations of the group, then every pair's state into its mailbox
+// `launches` iterations of the group (gicp: the plane-to-plane instantiation), then every pair's state into its mailbox
 static hipError_t icp_iter_enqueue_group(const IcpView* dv, int G, int max_nchunk, int launches, const int* dseqs,
-                                         hipStream_t st) {
+                                         hipStream_t st, bool gicp) {
   const ViewExt<IcpView> x{dv, {0, 0, 0}};
-  for (int k = 0; k < launches; ++k) hipLaunchKernelGGL(k_icp_iter_group, dim3(max_nchunk, G), dim3(256), 0, st, x);
+  for (int k = 0; k < launches; ++k) {
+    if (gicp) hipLaunchKernelGGL(k_icp_iter_gicp_group, dim3(max_nchunk, G), dim3(256), 0, st, x);
+    else hipLaunchKernelGGL(k_icp_iter_group, dim3(max_nchunk, G), dim3(256), 0, st, x);
+  }
   hipLaunchKernelGGL(k_icp_publish_group, dim3(G), dim3(64), 0, st, x, dseqs);
   return hipGetLastError();
 }

@@ -23,7 +23,7 @@ DBG_GRAPH_BITMAP, DBG_CORE, DBG_PERM, DBG_NBR_OFFSETS, DBG_NBR_INDEX, DBG_NBR_DI
 DBG_NN_LARGE_OF_SMALL, DBG_NN_SMALL_OF_LARGE, DBG_VOX_SRC, DBG_VOX_TGT, DBG_CORR, DBG_MATCH_STATS = 8, 9, 10, 11, 12, 13
 DBG_SOLVER_STATE = 14
 DBG_ICP_CORR, DBG_ICP_TRACE, DBG_ICP_TIMES = 15, 16, 17
-ICP_POINT_TO_PLANE, ICP_POINT_TO_POINT = 0, 1
+ICP_POINT_TO_PLANE, ICP_POINT_TO_POINT, ICP_PLANE_TO_PLANE = 0, 1, 2
 ICP_STOP_NONE, ICP_STOP_MAX_ITERATIONS, ICP_STOP_TRANSFORMATION, ICP_STOP_FITNESS, ICP_STOP_TOO_FEW, ICP_STOP_DEGENERATE = range(6)
 
 
@@ -102,7 +102,7 @@ EXPORTS = [
     "qtr_default_frontend_params", "qtr_num_slots", "qtr_slot_stream", "qtr_voxelize", "qtr_fpfh", "qtr_match",
     "qtr_solve", "qtr_max_clique", "qtr_compute_tims", "qtr_scale_mask", "qtr_gnc_rotation2d",
     "qtr_cote_estimate", "qtr_cote_estimate_ranges", "qtr_ip_default_params", "qtr_segment_cloud", "qtr_pw_default_params", "qtr_patchwork", "qtr_gnc_rotation3d", "qtr_exact_stats", "qtr_read_kitti_bin", "qtr_write_pcd_xyz", "qtr_read_pcd_xyz", "qtr_register_pair", "qtr_register_pair_corr", "qtr_feature_pair", "qtr_get_stage_times", "qtr_get_nn_dir_times", "qtr_set_stage_events", "qtr_set_nn_event_stride", "qtr_get_nn_totals", "qtr_debug_fetch", "qtr_debug_math", "qtr_submit_batch", "qtr_wait", "qtr_set_batch_preprocess", "qtr_comm_unique_id", "qtr_comm_init", "qtr_gather_results", "qtr_gather_results_v", "qtr_comm_destroy",
-    "qtr_default_icp_params", "qtr_icp", "qtr_refine_pair", "qtr_submit_batch_refine",
+    "qtr_default_icp_params", "qtr_icp", "qtr_refine_pair", "qtr_submit_batch_refine", "qtr_gicp",
 ]
 
 _lib = None
@@ -255,6 +255,8 @@ def load(path: str | None = None):
     lib.qtr_default_icp_params.argtypes = [C.POINTER(IcpParams)]
     lib.qtr_icp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                             C.POINTER(IcpParams), C.POINTER(IcpResult), C.c_int]
+    lib.qtr_gicp.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                             C.POINTER(IcpParams), C.POINTER(IcpResult), C.c_int]
     lib.qtr_refine_pair.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(IcpParams), C.POINTER(IcpResult)]
     lib.qtr_submit_batch_refine.argtypes = [C.c_void_p, C.POINTER(PairDesc), C.c_int, C.POINTER(FrontendParams),
                                             C.POINTER(Params), C.POINTER(IcpParams), C.POINTER(Result),
@@ -771,7 +773,8 @@ class Handle:
     def icp(self, src4, tgt4, tgt_normals4=None, guess=None, params: IcpParams | None = None, slot: int = 0) -> dict:
         """6-DoF ICP of src4 onto tgt4 (qtr_icp).  numpy arrays (host) or contiguous [N,4] float32 torch device tensors
         (all on the device: mem = QTR_MEM_DEVICE).  tgt_normals4 None: the target normals are computed at
-        params.normal_radius (point-to-plane).  Returns the result record as a dict (T row-major 4x4)."""
+        params.normal_radius (point-to-plane; plane-to-plane computes the source's as well: gicp with src_normals4 = None).
+        Returns the result record as a dict (T row-major 4x4)."""
         prm = params or default_icp_params()
         if isinstance(src4, np.ndarray) or isinstance(tgt4, np.ndarray):
             src4, tgt4 = _f4(src4), _f4(tgt4)
@@ -788,6 +791,33 @@ class Handle:
         res = IcpResult()
         rc = self._lib.qtr_icp(self._h, slot, ps, int(src4.shape[0]), pt, int(tgt4.shape[0]), pn,
                                None if g is None else g.ctypes.data, C.byref(prm), C.byref(res), mem)
+        self._check(rc)
+        return _icp_dict(res)
+
+    def gicp(self, src4, tgt4, src_normals4=None, tgt_normals4=None, guess=None, params: IcpParams | None = None,
+             slot: int = 0) -> dict:
+        """Plane-to-plane (Generalized) ICP of src4 onto tgt4 with both normal sets (qtr_gicp); a normal set given as None
+        is computed at params.normal_radius.  Arrays as for icp (numpy on the host, or torch tensors all on the device);
+        params None = the defaults with method = ICP_PLANE_TO_PLANE."""
+        prm = params or default_icp_params(method=ICP_PLANE_TO_PLANE)
+        if isinstance(src4, np.ndarray) or isinstance(tgt4, np.ndarray):
+            src4, tgt4 = _f4(src4), _f4(tgt4)
+            src_normals4 = None if src_normals4 is None else _f4(src_normals4)
+            tgt_normals4 = None if tgt_normals4 is None else _f4(tgt_normals4)
+            ps, pt, mem = src4.ctypes.data, tgt4.ctypes.data, MEM_HOST
+            pa = None if src_normals4 is None else src_normals4.ctypes.data
+            pn = None if tgt_normals4 is None else tgt_normals4.ctypes.data
+        else:
+            (ps, m1), (pt, m2) = _ptr(src4), _ptr(tgt4)
+            (pa, m3), (pn, m4) = _ptr(src_normals4), _ptr(tgt_normals4)
+            assert m1 == m2 == MEM_DEVICE and m3 in (None, MEM_DEVICE) and m4 in (None, MEM_DEVICE), \
+                "torch tensors must all be on the device"
+            assert src4.dtype == tgt4.dtype and src4.shape[-1] == 4 and tgt4.shape[-1] == 4
+            mem = MEM_DEVICE
+        g = _guess16(guess)
+        res = IcpResult()
+        rc = self._lib.qtr_gicp(self._h, slot, ps, int(src4.shape[0]), pa, pt, int(tgt4.shape[0]), pn,
+                                None if g is None else g.ctypes.data, C.byref(prm), C.byref(res), mem)
         self._check(rc)
         return _icp_dict(res)
 
