@@ -484,6 +484,73 @@ QTR_API int qtr_submit_batch_refine(qtr_handle* h, const qtr_pair_desc* pairs, i
                                     const qtr_params* prm, const qtr_icp_params* icp, qtr_result* results,
                                     qtr_icp_result* refined, int mem);
 
+/* Keyframes: the products of ONE scan's front end (voxel grid, normals, FPFH, the matcher's sequential mean and its
+ * per-descriptor preparation) kept on the device, in an allocation sized to the scan, so that a scan that is registered
+ * more than once pays for its front end once.  Loop closing registers one query against K candidates with K + 1 front
+ * ends instead of 2 K; odometry reuses scan k's keyframe as the source of pair (k, k + 1), the reference's
+ * FPFHManager::is_odometry_test_ / swapTgt2Src (include/fpfh_manager.hpp:111-118) without the trip through host vectors.
+ * Results are bit-identical to the raw-scan entries (qtr_register_pair, qtr_submit_batch, qtr_submit_batch_refine).
+ *   qtr_keyframe_create     runs the one-cloud front end on `slot` — with qtr_register_pair's rules: the pcl::VoxelGrid
+ *                           pass-through, the capacity errors and their messages — and packs what a registration needs
+ *                           into one device allocation: 176 bytes per voxel plus alignment, device_bytes <=
+ *                           256 * n_voxels + 4096 (about 3 MB for a 16 k-voxel KITTI scan).  A set-up call: it returns
+ *                           after the pack has completed, whatever `mem` says; the caller's scan is free on return and
+ *                           nothing of the keyframe aliases slot memory.  The keyframe belongs to the handle;
+ *                           qtr_destroy frees the keyframes the caller did not destroy.
+ *   qtr_keyframe_fetch      copies a stored item to host memory, like qtr_debug_fetch: up to `bytes` bytes to `dst`, returns
+ *                           the bytes the item holds or < 0
+ *   qtr_keyframe_destroy    frees it.  Destroying a keyframe that a pending batch names is the caller's error, as is using
+ *                           one afterwards.
+ *   qtr_register_keyframes  the whole path of qtr_register_pair with the two front ends replaced by ONE copy launch that
+ *                           loads both keyframes into the slot's cloud arenas; the matcher, the solver and everything that
+ *                           reads the slot afterwards (qtr_refine_pair with every method, QTR_DBG_VOX_SRC / _TGT, QTR_DBG_CORR)
+ *                           work as after qtr_register_pair.  fp->voxel_size, normal_radius and fpfh_radius must equal BOTH
+ *                           keyframes' (compared as float bits; QTR_ERR_BAD_ARG otherwise); tuple_scale, use_crosscheck,
+ *                           use_tuple_test and seed are free per call.  A keyframe of another handle: QTR_ERR_BAD_ARG.
+ *                           kf_src == kf_tgt is legal.  res->n_src / n_tgt are the keyframes' voxel counts;
+ *                           qtr_stage_times.voxelize and .fpfh read 0 (.match covers the load and the matcher).  clique /
+ *                           final_inliers are host buffers.  Keyframes are immutable: any number of slots, from different
+ *                           host threads, may register against the same keyframe at once. */
+typedef struct qtr_keyframe qtr_keyframe; /* opaque, owned by the handle that made it */
+typedef struct qtr_keyframe_info {
+  int n_points, n_voxels;                       /* raw points in, down-sampled points kept */
+  float voxel_size, normal_radius, fpfh_radius; /* the front-end knobs baked into it */
+  int passed_through;                           /* 1: pcl::VoxelGrid's int32-overflow pass-through happened */
+  unsigned long long device_bytes;              /* HBM this keyframe holds */
+} qtr_keyframe_info;
+#define QTR_KF_VOX 1     /* float4[n_voxels] */
+#define QTR_KF_NORMALS 2 /* float4[n_voxels] nx,ny,nz,curvature */
+#define QTR_KF_FPFH 3    /* float[n_voxels][33] */
+#define QTR_KF_MEAN 4    /* float[4] sequential float mean of the voxels (Matcher::normalizePoints) */
+QTR_API int qtr_keyframe_create(qtr_handle* h, int slot, const float* raw4, int P, const qtr_frontend_params* fp, int mem,
+                                qtr_keyframe** out);
+QTR_API int qtr_keyframe_get_info(const qtr_keyframe* kf, qtr_keyframe_info* info);
+QTR_API long long qtr_keyframe_fetch(qtr_handle* h, const qtr_keyframe* kf, int what, void* dst, size_t bytes);
+QTR_API void qtr_keyframe_destroy(qtr_handle* h, qtr_keyframe* kf);
+QTR_API int qtr_register_keyframes(qtr_handle* h, int slot, const qtr_keyframe* kf_src, const qtr_keyframe* kf_tgt,
+                                   const qtr_frontend_params* fp, const qtr_params* prm, qtr_result* res, int* clique,
+                                   int* final_inliers, int cap);
+/* Batched registration of keyframe pairs: qtr_submit_batch's lanes with the voxel chain gone and the FPFH chain replaced
+ * by one grouped load; the solver chain and, with icp != NULL, the refinement phases of qtr_submit_batch_refine are the
+ * same.  results[i] / refined[i] are bit-identical to what those entries produce for the raw scans of the keyframes.
+ * One query against K candidates is K descriptors with the same src.  icp = NULL: no refinement, and refined must be NULL
+ * too; icp != NULL: refined is required.  Contract as qtr_submit_batch: one job per handle, driven by qtr_wait, every
+ * record pre-filled with QTR_ERR_NOT_RUN, per-pair statuses, qtr_refine_pair refused afterwards.  All arguments are
+ * validated before anything is enqueued — a NULL or foreign keyframe, or one whose radii differ from fp's, in ANY pair:
+ * QTR_ERR_BAD_ARG and no job.  pairs, results, refined AND every keyframe named must stay valid until qtr_wait returns;
+ * clique / final_inliers are host buffers. */
+typedef struct qtr_kf_pair_desc {
+  const qtr_keyframe* src;
+  const qtr_keyframe* tgt;
+  unsigned long long seed; /* tuple-test RNG seed of this pair (qtr_frontend_params.seed is ignored) */
+  int* clique;             /* optional, capacity `cap` ints */
+  int* final_inliers;      /* optional */
+  int cap;
+} qtr_kf_pair_desc;
+QTR_API int qtr_submit_batch_keyframes(qtr_handle* h, const qtr_kf_pair_desc* pairs, int B, const qtr_frontend_params* fp,
+                                       const qtr_params* prm, const qtr_icp_params* icp, qtr_result* results,
+                                       qtr_icp_result* refined);
+
 /* Inspection of intermediates of the LAST call on a slot (tests / parity debugging).  Copies up to
  * `bytes` bytes to host memory `dst`; returns the number of bytes the item holds, or <0 on error. */
 #define QTR_DBG_GRAPH_BITMAP 1   /* uint64[L][ceil(L/64)] adjacency, original labels */

@@ -514,3 +514,31 @@ def refine_quatro(quatro: "Quatro", source_cloud, target_cloud, icp: IterativeCl
     icp.setInputTarget(target_cloud)
     icp.align(guess)
     return icp.getFinalTransformation()
+
+
+def best_candidate(records) -> int:
+    """Index of the best registration record of a one-to-many job: the largest number of final inliers among the
+    records with valid set, ties to the lowest index; -1 when no record is valid.  Host side only."""
+    best, best_n = -1, -1
+    for i, r in enumerate(records):
+        if not r.get("valid"):
+            continue
+        n = int(r["n_final"]) if "n_final" in r else int(len(r["final_inliers"]))
+        if n > best_n:
+            best, best_n = i, n
+    return best
+
+
+def register_one_to_many(handle, query_kf, candidate_kfs, fp=None, params=None, icp=None, seeds=None):
+    """Loop closing: one query keyframe (the source) against K candidate keyframes (the targets), as ONE batched job
+    (Handle.register_batch_keyframes: K + 1 front ends were paid when the keyframes were made, none here).  seeds: one
+    tuple-test seed per candidate (default: fp.seed for all).  Returns (records, best) — the per-candidate result dicts
+    and best_candidate(records) — or with icp (records, refined, best)."""
+    fp = fp or _ql.default_frontend_params()
+    K = len(candidate_kfs)
+    seeds = [int(fp.seed)] * K if seeds is None else [int(x) for x in seeds]
+    assert len(seeds) == K
+    out = handle.register_batch_keyframes([(query_kf, c, s) for c, s in zip(candidate_kfs, seeds)], fp, params, icp)
+    if icp is None:
+        return out, best_candidate(out)
+    return out[0], out[1], best_candidate(out[0])

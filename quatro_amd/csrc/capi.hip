@@ -44,7 +44,7 @@ struct Slot {
   int seq = 0;                   // last sequence number handed to a phase-ending kernel
   unsigned long long exact_nodes = 0;  // search-tree nodes of the last PMC_EXACT run
   int exact_aborted = 0;               // 1: its time limit was hit (heuristic clique returned)
-  int times_pending = 0;         // 1: qtr_solve, 2: qtr_register_pair — stage times are read off the events lazily
+  int times_pending = 0;         // 1: qtr_solve, 2: qtr_register_pair, 5: qtr_register_keyframes — stage times are read off the events lazily
   int nn_pending = 0;            // the nearest-neighbour events of the last match have not been added to the totals yet
   int nn_timed_last = 0;         // the last match had its event pairs attached (qtr_set_nn_event_stride)
   long long n_matches = 0;       // matches this slot has run
@@ -82,6 +82,13 @@ struct Lane {
   const IcpView* ref_views = nullptr;  // the same views in the stage (device)
   int ref_it = 0, ref_nchunk = 1;      // iterations enqueued so far; the group's widest iteration launch
 };
+// A device-resident keyframe (keyframe.hip): one allocation sized to the scan, read-only after qtr_keyframe_create.
+struct qtr_keyframe {
+  qtr_handle* owner = nullptr;
+  void* dev = nullptr;
+  qtr_keyframe_info info = {};
+};
+
 struct BatchJob {
   const qtr_pair_desc* pairs = nullptr;
   int B = 0, next = 0, done = 0;
@@ -95,6 +102,11 @@ struct BatchJob {
   qtr_icp_params icp;
   qtr_icp_result* refined = nullptr;
   std::vector<unsigned char> ref_state; // per pair: 0 not refined, 1 refinement under way, 2 refined record final
+  // qtr_submit_batch_keyframes: the pairs travel through the lanes as pair descriptors whose scan pointers are the two
+  // qtr_keyframe objects and whose sizes are their voxel counts (`pairs` points at this copy); the lanes load the keyframes
+  // into the slots where a raw-scan job runs the voxel grid and the FPFH chain
+  bool kf = false;
+  std::vector<qtr_pair_desc> kf_shadow;
 };
 
 struct qtr_handle {
@@ -128,6 +140,8 @@ struct qtr_handle {
   int stage_events = 1;  // QTR_STAGE_EVENTS=0: only the first/last event of a call are recorded (stage times read 0)
   int nn_event_stride = 1;  // every n-th match of a slot carries the nearest-neighbour event pairs (0: none)
   int icp_block = 0;  // QTR_ICP_BLOCK=n: ICP launches enqueued between two read-backs of the stop flag (0: all at once)
+  std::mutex kf_mu;                    // guards `keyframes` (qtr_keyframe_create / _destroy from several threads)
+  std::vector<qtr_keyframe*> keyframes;  // the live keyframes of this handle: qtr_destroy frees what the caller forgot
   char err[512];
 };
 
@@ -382,6 +396,11 @@ void qtr_destroy(qtr_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   qtr_comm_destroy(h);
+  for (qtr_keyframe* kf : h->keyframes) {  // (keyframes the caller did not destroy)
+    if (kf->dev) (void)hipFree(kf->dev);
+    delete kf;
+  }
+  h->keyframes.clear();
   for (auto& l : h->lanes) {
     if (l.stage.h) (void)hipHostFree(l.stage.h);
     if (l.stage.d) (void)hipFree(l.stage.d);
@@ -671,6 +690,10 @@ static void compute_times(Slot& s) {
   s.times = qtr_stage_times{};
   if (s.times_pending == 1) {
     if (hipEventElapsedTime(&ms, s.ev[1], s.ev[2]) == hipSuccess) s.times.graph = ms;
+  } else if (s.times_pending == 5) {  // qtr_register_keyframes: no voxel grid, no FPFH chain (both read 0); match = load + matcher
+    if (hipEventElapsedTime(&ms, s.ev[0], s.ev[7]) == hipSuccess) s.times.match = ms;
+    if (hipEventElapsedTime(&ms, s.ev[7], s.ev[2]) == hipSuccess) s.times.graph = ms;
+    fill_nn_times(s);
   } else {
     if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.times.voxelize = ms;
     if (hipEventElapsedTime(&ms, s.ev[1], s.ev[6]) == hipSuccess) s.times.fpfh = ms;
@@ -1943,6 +1966,247 @@ int qtr_feature_pair(qtr_handle* h, int slot, const float* src_raw4, int Ps, con
 }
 
 // ------------------------------------------------------------------------------------------------
+// keyframes (keyframe.hip): one scan's front end, kept on the device
+// The one-cloud front end on cloud[0] of a slot: voxel grid -> mean -> FPFH chain with the matcher's per-descriptor
+// preparation, under front_device's rules (pass-through, radix-pass speculation, long_lists retry, capacity errors).  The
+// counters a whole-path call receives in its matcher's mail are read back here: nothing runs a matcher.
+static int front_one_device(qtr_handle* h, Slot& s, const float* raw4, int P, const qtr_frontend_params* fp, int mem,
+                            int* n_out, int* passed_out) {
+  int rc = QTR_OK;
+  if (fp->normal_radius > fp->fpfh_radius) {
+    snprintf(h->err, sizeof(h->err), "[FPFHManager]: Normal should be lower than fpfh_radius!!!!");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (P <= 0 || !raw4) {
+    snprintf(h->err, sizeof(h->err), "Invalid or empty point cloud dataset given!");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (P > h->lim.max_points) {
+    snprintf(h->err, sizeof(h->err), "cloud exceeds max_points=%d", h->lim.max_points);
+    return QTR_ERR_CAPACITY;
+  }
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  const float4* d_raw = (const float4*)raw4;
+  if (mem == QTR_MEM_HOST) {
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, raw4, (size_t)P * 16, hipMemcpyHostToDevice, s.stream));
+    d_raw = s.in_src;
+  }
+  auto fail_drained = [&](int code) {  // (see front_device: the scan is not handed back while a kernel may still read it)
+    (void)hipStreamSynchronize(s.stream);
+    return code;
+  };
+  for (int attempt = 0;; ++attempt) {  // the voxel sort's radix passes are speculated as in front_device
+    const int launched = s.fb.vox_passes;
+    s.fb.mail_seq = ++s.seq;
+    QTR_HIP_TRY(h, voxelize_enqueue(s.fb, 1, &d_raw, &P, fp->voxel_size, s.stream, launched, fp->fpfh_radius * 1.001f));
+    if ((rc = wait_mail(h, s, MAIL_SEQ_VOX0, s.seq)) != QTR_OK) return fail_drained(rc);
+    const int needed = std::min(4, std::max(1, (s.mail[MAIL_VOX0 + CNT_SORT_BITS] + 7) / 8));
+    if (needed > launched && attempt == 0) {
+      s.fb.vox_passes = 4;
+      s.fb.vox_fewer = 0;
+      continue;
+    }
+    if (needed < launched) {
+      if (++s.fb.vox_fewer >= 4) {
+        s.fb.vox_passes = needed;
+        s.fb.vox_fewer = 0;
+      }
+    } else {
+      s.fb.vox_fewer = 0;
+    }
+    break;
+  }
+  int n = s.mail[MAIL_VOX0 + CNT_NVOX];
+  if (n < 0) {
+    snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out");
+    return fail_drained(QTR_ERR_HIP);
+  }
+  const bool pass = s.mail[MAIL_VOX0 + CNT_VOX_OVERFLOW] != 0;
+  if (pass) {  // pcl::VoxelGrid: the cloud passes through as it is (see front_device)
+    if (P > h->lim.max_voxels) {
+      snprintf(h->err, sizeof(h->err), "voxel grid would overflow int32 (leaf too small): the cloud passes through as it "
+               "is (pcl::VoxelGrid), and its %d points exceed max_voxels=%d", P, h->lim.max_voxels);
+      return fail_drained(QTR_ERR_CAPACITY);
+    }
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[0].vox, d_raw, (size_t)P * 16, hipMemcpyDeviceToDevice, s.stream));
+    n = P;
+  }
+  if (n > h->lim.max_voxels) {
+    snprintf(h->err, sizeof(h->err), "voxel count %d exceeds max_voxels=%d", n, h->lim.max_voxels);
+    return fail_drained(QTR_ERR_CAPACITY);
+  }
+  if (n <= 0) {
+    snprintf(h->err, sizeof(h->err), "Invalid or empty point cloud dataset given!");
+    return fail_drained(QTR_ERR_BAD_ARG);
+  }
+  s.last_ns = s.last_n = n;
+  s.last_nt = 0;
+  QTR_HIP_TRY(h, mean_enqueue(s.fb, 0, 1, &n, s.stream));
+  if (h->long_lists) QTR_TRY(ensure_long_arenas(h, s));
+  const int ncell = s.mail[MAIL_VOX0 + CNT_NCELL];
+  QTR_HIP_TRY(h, fpfh_enqueue(s.fb, 0, 1, &n, fp->normal_radius, fp->fpfh_radius, s.stream, false, true, h->long_lists, true,
+                              cell_table_cells(ncell, ncell)));
+  QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32, s.fb.cloud[0].counts, 16 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
+  QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
+  if (s.pinned_i32[CNT_VOX_TAILERR]) {
+    snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out in a tile (centroids incomplete)");
+    return QTR_ERR_HIP;
+  }
+  if (s.pinned_i32[CNT_NBR_CAPACITY]) {
+    snprintf(h->err, sizeof(h->err), "radius-neighbour lists longer than %d entries (longest %d) exceed the long-list "
+             "arena: qtr_limits.max_long_neighbors is %d", QTR_KMAX, s.pinned_i32[CNT_KMAX], h->lim.max_long_neighbors);
+    return QTR_ERR_CAPACITY;
+  }
+  if (!h->long_lists && s.pinned_i32[CNT_NBR_OVERFLOW]) {  // (see front_device: the chain ran without k2_neighbors_big)
+    h->long_lists = true;
+    return front_one_device(h, s, raw4, P, fp, mem, n_out, passed_out);
+  }
+  *n_out = n;
+  *passed_out = pass ? 1 : 0;
+  return QTR_OK;
+}
+
+int qtr_keyframe_create(qtr_handle* h, int slot, const float* raw4, int P, const qtr_frontend_params* fp, int mem,
+                        qtr_keyframe** out) {
+  if (out) *out = nullptr;
+  Slot* sp = get_slot(h, slot);
+  if (!sp || !fp || !out) return QTR_ERR_BAD_ARG;
+  Slot& s = *sp;
+  s.times_pending = 0;
+  int n = 0, passed = 0;
+  QTR_TRY(front_one_device(h, s, raw4, P, fp, mem, &n, &passed));
+  qtr_keyframe* kf = new (std::nothrow) qtr_keyframe();
+  if (!kf) return QTR_ERR_CAPACITY;
+  const KfLayout lay = kf_layout(n);
+  if (hipMalloc(&kf->dev, lay.total) != hipSuccess) {
+    (void)hipGetLastError();
+    delete kf;
+    snprintf(h->err, sizeof(h->err), "keyframe: no device memory for %zu bytes", lay.total);
+    return QTR_ERR_HIP;
+  }
+  hipError_t e = kf_pack_enqueue(s.fb, kf->dev, n, s.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
+  if (e != hipSuccess) {
+    (void)hipFree(kf->dev);
+    delete kf;
+    snprintf(h->err, sizeof(h->err), "keyframe pack: %s", hipGetErrorString(e));
+    return QTR_ERR_HIP;
+  }
+  kf->owner = h;
+  kf->info.n_points = P;
+  kf->info.n_voxels = n;
+  kf->info.voxel_size = fp->voxel_size;
+  kf->info.normal_radius = fp->normal_radius;
+  kf->info.fpfh_radius = fp->fpfh_radius;
+  kf->info.passed_through = passed;
+  kf->info.device_bytes = (unsigned long long)lay.total;
+  {
+    std::lock_guard<std::mutex> lk(h->kf_mu);
+    h->keyframes.push_back(kf);
+  }
+  *out = kf;
+  return QTR_OK;
+}
+
+int qtr_keyframe_get_info(const qtr_keyframe* kf, qtr_keyframe_info* info) {
+  if (!kf || !info) return QTR_ERR_BAD_ARG;
+  *info = kf->info;
+  return QTR_OK;
+}
+
+long long qtr_keyframe_fetch(qtr_handle* h, const qtr_keyframe* kf, int what, void* dst, size_t bytes) {
+  if (!h || !kf || kf->owner != h) return -1;
+  if (hipSetDevice(h->device) != hipSuccess) return -1;
+  const KfLayout lay = kf_layout(kf->info.n_voxels);
+  const size_t n = (size_t)kf->info.n_voxels;
+  size_t off = 0, have = 0;
+  switch (what) {
+    case QTR_KF_VOX: off = lay.vox; have = n * 16; break;
+    case QTR_KF_NORMALS: off = lay.normals; have = n * 16; break;
+    case QTR_KF_FPFH: off = lay.fpfh; have = n * 132; break;
+    case QTR_KF_MEAN: off = 64; have = 16; break;
+    default: return -1;
+  }
+  const size_t m = have < bytes ? have : bytes;
+  if (dst && m > 0 && hipMemcpy(dst, (const char*)kf->dev + off, m, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return (long long)have;
+}
+
+void qtr_keyframe_destroy(qtr_handle* h, qtr_keyframe* kf) {
+  if (!h || !kf || kf->owner != h) return;
+  {
+    std::lock_guard<std::mutex> lk(h->kf_mu);
+    auto it = std::find(h->keyframes.begin(), h->keyframes.end(), kf);
+    if (it == h->keyframes.end()) return;
+    h->keyframes.erase(it);
+  }
+  (void)hipSetDevice(h->device);
+  if (kf->dev) (void)hipFree(kf->dev);
+  delete kf;
+}
+
+// a pair of keyframes against the handle and the call's front-end knobs
+static int check_keyframes(qtr_handle* h, const qtr_keyframe* a, const qtr_keyframe* b, const qtr_frontend_params* fp) {
+  if (!a || !b) {
+    snprintf(h->err, sizeof(h->err), "keyframe is NULL");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (a->owner != h || b->owner != h) {
+    snprintf(h->err, sizeof(h->err), "keyframe belongs to another handle");
+    return QTR_ERR_BAD_ARG;
+  }
+  auto same = [](float x, float y) { return memcmp(&x, &y, 4) == 0; };
+  for (const qtr_keyframe* k : {a, b})
+    if (!same(k->info.voxel_size, fp->voxel_size) || !same(k->info.normal_radius, fp->normal_radius) ||
+        !same(k->info.fpfh_radius, fp->fpfh_radius)) {
+      snprintf(h->err, sizeof(h->err), "keyframe was made with voxel_size %g, normal_radius %g, fpfh_radius %g; the call asks "
+               "for %g, %g, %g", k->info.voxel_size, k->info.normal_radius, k->info.fpfh_radius, fp->voxel_size,
+               fp->normal_radius, fp->fpfh_radius);
+      return QTR_ERR_BAD_ARG;
+    }
+  return QTR_OK;
+}
+
+int qtr_register_keyframes(qtr_handle* h, int slot, const qtr_keyframe* kf_src, const qtr_keyframe* kf_tgt,
+                           const qtr_frontend_params* fp, const qtr_params* prm, qtr_result* res, int* clique,
+                           int* final_inliers, int cap) {
+  Slot* sp = get_slot(h, slot);
+  if (!sp || !res || !fp) return QTR_ERR_BAD_ARG;
+  Slot& s = *sp;
+  memset(res, 0, sizeof(*res));
+  int rc = check_params(h, prm);
+  if (rc != QTR_OK) return res->status = rc;
+  if ((rc = check_keyframes(h, kf_src, kf_tgt, fp)) != QTR_OK) return res->status = rc;
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  const int ns = kf_src->info.n_voxels, nt = kf_tgt->info.n_voxels;
+  res->n_src = s.last_ns = ns;
+  res->n_tgt = s.last_nt = nt;
+  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[0], s.stream));
+  // the matcher's clean slate first — it clears the duplicate tables the load fills, and the solver's state rides in it —
+  // then ONE launch for both clouds; the matcher starts at its operand tables (init_done, prep_done)
+  QTR_HIP_TRY(h, match_init_enqueue(s.fb, ns, nt, *fp, s.stream, true, (int*)s.sb.st, (int)(sizeof(SolverState) / 4)));
+  QTR_HIP_TRY(h, kf_load_enqueue(s.fb, kf_src->dev, ns, kf_tgt->dev, nt, s.stream));
+  int L = 0;
+  rc = match_device(h, s, ns, nt, fp, &L, true, true);
+  res->n_corr = L;
+  if (rc != QTR_OK) return res->status = rc;
+  s.last_L = L;
+  if (L > h->lim.max_corr) {
+    snprintf(h->err, sizeof(h->err), "L=%d exceeds max_corr=%d", L, h->lim.max_corr);
+    return res->status = QTR_ERR_CAPACITY;
+  }
+  QTR_HIP_TRY(h, gather_matched_enqueue(s.fb, L, s.m_src, s.m_tgt, s.stream));
+  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[7], s.stream));
+  rc = solve_device(h, s, s.m_src, s.m_tgt, L, prm, res, true);
+  if (rc != QTR_OK && rc != QTR_ERR_CLIQUE_TOO_SMALL) return rc;
+  s.times_pending = h->stage_events ? 5 : 4;
+  const int rc2 = copy_out_lists(h, s, res, clique, nullptr, final_inliers, cap, QTR_MEM_HOST);
+  if (rc2 != QTR_OK) return res->status = rc2;
+  mark_registration(s, rc, res);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
 // batched registration: lanes of slots stepped through the three launch chains in lockstep
 static void batch_fail_pair(qtr_handle* h, int pair, int status) {
   qtr_result& r = h->job.results[pair];
@@ -2066,6 +2330,8 @@ static int lane_start_chunk(qtr_handle* h, Lane& ln) {
   std::vector<FrontBufs*> F;
   std::vector<const float4*> raws;
   std::vector<int> Ps;
+  std::vector<void*> kf_dev;                  // keyframe job: the device allocations, two per pair (Ps: their voxel counts)
+  std::vector<unsigned long long> kf_seeds;
   // The demo's STEP 2 and 3 on raw sweeps (reference examples/run_global_registration.cpp:136-160): per scan
   // PatchWork::estimate_ground -> non-ground points -> ImageProjection::segmentCloud -> valid segments.  Both stages hand a
   // count to the next one through the host, so a scan is a chain of four host-visible steps — run for ALL pairs of the
@@ -2080,7 +2346,7 @@ static int lane_start_chunk(qtr_handle* h, Lane& ln) {
     int n[2] = {0, 0};  // valid points of source / target
   };
   std::vector<PreScan> pre((size_t)ln.count);
-  if (h->pre_on) {
+  if (h->pre_on && !J.kf) {
     int open = 0;
     for (int g = 0; g < ln.count; ++g) {
       const qtr_pair_desc& pd = J.pairs[ln.first_pair + g];
@@ -2172,6 +2438,20 @@ static int lane_start_chunk(qtr_handle* h, Lane& ln) {
       continue;
     }
     s.times_pending = 0;
+    if (J.kf) {  // a keyframe pair (validated at submission): no voxel chain — the load and the matcher follow the loop
+      const qtr_keyframe *ks = (const qtr_keyframe*)pd.src_raw4, *kt = (const qtr_keyframe*)pd.tgt_raw4;
+      r.n_src = ln.ns[g] = s.last_ns = ks->info.n_voxels;
+      r.n_tgt = ln.nt[g] = s.last_nt = kt->info.n_voxels;
+      s.fb.mail_seq = ++s.seq;
+      ln.active.push_back(g);
+      F.push_back(&s.fb);
+      kf_dev.push_back(ks->dev);
+      kf_dev.push_back(kt->dev);
+      Ps.push_back(ks->info.n_voxels);
+      Ps.push_back(kt->info.n_voxels);
+      kf_seeds.push_back(pd.seed);
+      continue;
+    }
     if (corr) {
       r.n_corr = pd.n_corr;
       ln.L[g] = pd.n_corr;
@@ -2228,6 +2508,16 @@ static int lane_start_chunk(qtr_handle* h, Lane& ln) {
     Ps.push_back(P_t);
   }
   if (ln.active.empty()) return lane_enqueue_solver(h, ln, {});  // no scans in this chunk (or nothing valid at all)
+  if (J.kf) {
+    // phase 1 is gone and phase 2 is a grouped load (blockIdx.z = pair) in front of the matcher, which finds the
+    // per-descriptor preparation done as after the whole path's k2_fpfh.  The lists' checks were made when the keyframes
+    // were created and the load leaves their counter words clean: the chunk counts as one that ran k2_neighbors_big.
+    QTR_HIP_TRY(h, kf_load_enqueue_group(F.data(), (int)F.size(), kf_dev.data(), Ps.data(), &ln.stage, lead.stream));
+    ln.long_lists = true;
+    QTR_HIP_TRY(h, match_enqueue_group(F.data(), (int)F.size(), Ps.data(), &J.fp, kf_seeds.data(), &ln.stage, lead.stream, true));
+    ln.phase = 2;
+    return QTR_OK;
+  }
   QTR_HIP_TRY(h, voxelize_enqueue_group(F.data(), (int)F.size(), raws.data(), Ps.data(), J.fp.voxel_size, &ln.stage,
                                         lead.stream, J.fp.fpfh_radius * 1.001f));
   QTR_HIP_TRY(h, hipEventRecord(lead.ev_vox, lead.stream));
@@ -2668,7 +2958,7 @@ int qtr_set_batch_preprocess(qtr_handle* h, const qtr_pw_params* pw, const qtr_i
 // icp = NULL: plain qtr_submit_batch (no refine phase, no ICP arena, no extra launch)
 static int submit_batch_impl(qtr_handle* h, const qtr_pair_desc* pairs, int B, const qtr_frontend_params* fp,
                              const qtr_params* prm, const qtr_icp_params* icp, qtr_result* results, qtr_icp_result* refined,
-                             int mem) {
+                             int mem, bool kf = false /* pairs: BatchJob::kf_shadow */) {
   if (h->job.active) {
     snprintf(h->err, sizeof(h->err), "a batch is already in flight on this handle (call qtr_wait first)");
     return QTR_ERR_BAD_ARG;
@@ -2699,6 +2989,7 @@ static int submit_batch_impl(qtr_handle* h, const qtr_pair_desc* pairs, int B, c
   J.prm = *prm;
   J.results = results;
   J.mem = mem;
+  J.kf = kf;
   J.active = true;
   J.finished.assign((size_t)B, 0);
   for (int i = 0; i < B; ++i) {  // until a pair's record is final it says so (a caller that looks only at the
@@ -2746,6 +3037,39 @@ int qtr_submit_batch_refine(qtr_handle* h, const qtr_pair_desc* pairs, int B, co
     return QTR_ERR_BAD_ARG;
   }
   return submit_batch_impl(h, pairs, B, fp, prm, icp, results, refined, mem);
+}
+
+int qtr_submit_batch_keyframes(qtr_handle* h, const qtr_kf_pair_desc* pairs, int B, const qtr_frontend_params* fp,
+                               const qtr_params* prm, const qtr_icp_params* icp, qtr_result* results,
+                               qtr_icp_result* refined) {
+  if (!h) return QTR_ERR_BAD_ARG;
+  if (h->job.active) {
+    snprintf(h->err, sizeof(h->err), "a batch is already in flight on this handle (call qtr_wait first)");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (B < 0 || (B > 0 && (!pairs || !results)) || !fp) {
+    snprintf(h->err, sizeof(h->err), "bad batch arguments");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (icp) QTR_TRY(check_icp_params(h, icp));
+  if ((icp == nullptr) != (refined == nullptr) && (B > 0 || refined)) {
+    snprintf(h->err, sizeof(h->err), "bad batch arguments (refined goes with icp)");
+    return QTR_ERR_BAD_ARG;
+  }
+  for (int i = 0; i < B; ++i) QTR_TRY(check_keyframes(h, pairs[i].src, pairs[i].tgt, fp));
+  std::vector<qtr_pair_desc>& sh = h->job.kf_shadow;
+  sh.assign((size_t)B, qtr_pair_desc{});
+  for (int i = 0; i < B; ++i) {
+    sh[(size_t)i].src_raw4 = (const float*)pairs[i].src;  // (the lanes read them back as keyframes: BatchJob::kf)
+    sh[(size_t)i].n_src = pairs[i].src->info.n_voxels;
+    sh[(size_t)i].tgt_raw4 = (const float*)pairs[i].tgt;
+    sh[(size_t)i].n_tgt = pairs[i].tgt->info.n_voxels;
+    sh[(size_t)i].seed = pairs[i].seed;
+    sh[(size_t)i].clique = pairs[i].clique;
+    sh[(size_t)i].final_inliers = pairs[i].final_inliers;
+    sh[(size_t)i].cap = pairs[i].cap;
+  }
+  return submit_batch_impl(h, sh.data(), B, fp, prm, icp, results, refined, QTR_MEM_HOST, true);
 }
 
 int qtr_wait(qtr_handle* h) {

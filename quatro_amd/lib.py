@@ -97,12 +97,26 @@ class IcpResult(C.Structure):
                 ("rmse", C.c_double)]
 
 
+class KeyframeInfo(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("n_voxels", C.c_int), ("voxel_size", C.c_float), ("normal_radius", C.c_float),
+                ("fpfh_radius", C.c_float), ("passed_through", C.c_int), ("device_bytes", C.c_ulonglong)]
+
+
+class KfPairDesc(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("tgt", C.c_void_p), ("seed", C.c_ulonglong), ("clique", C.c_void_p),
+                ("final_inliers", C.c_void_p), ("cap", C.c_int)]
+
+
+KF_VOX, KF_NORMALS, KF_FPFH, KF_MEAN = 1, 2, 3, 4
+
 EXPORTS = [
     "qtr_create", "qtr_destroy", "qtr_last_error", "qtr_default_limits", "qtr_default_params", "qtr_demo_params",
     "qtr_default_frontend_params", "qtr_num_slots", "qtr_slot_stream", "qtr_voxelize", "qtr_fpfh", "qtr_match",
     "qtr_solve", "qtr_max_clique", "qtr_compute_tims", "qtr_scale_mask", "qtr_gnc_rotation2d",
     "qtr_cote_estimate", "qtr_cote_estimate_ranges", "qtr_ip_default_params", "qtr_segment_cloud", "qtr_pw_default_params", "qtr_patchwork", "qtr_gnc_rotation3d", "qtr_exact_stats", "qtr_read_kitti_bin", "qtr_write_pcd_xyz", "qtr_read_pcd_xyz", "qtr_register_pair", "qtr_register_pair_corr", "qtr_feature_pair", "qtr_get_stage_times", "qtr_get_nn_dir_times", "qtr_set_stage_events", "qtr_set_nn_event_stride", "qtr_get_nn_totals", "qtr_debug_fetch", "qtr_debug_math", "qtr_submit_batch", "qtr_wait", "qtr_set_batch_preprocess", "qtr_comm_unique_id", "qtr_comm_init", "qtr_gather_results", "qtr_gather_results_v", "qtr_comm_destroy",
     "qtr_default_icp_params", "qtr_icp", "qtr_refine_pair", "qtr_submit_batch_refine", "qtr_gicp",
+    "qtr_keyframe_create", "qtr_keyframe_get_info", "qtr_keyframe_fetch", "qtr_keyframe_destroy", "qtr_register_keyframes",
+    "qtr_submit_batch_keyframes",
 ]
 
 _lib = None
@@ -262,6 +276,18 @@ def load(path: str | None = None):
                                             C.POINTER(Params), C.POINTER(IcpParams), C.POINTER(Result),
                                             C.POINTER(IcpResult), C.c_int]
     lib.qtr_comm_destroy.restype = None
+    lib.qtr_keyframe_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(FrontendParams), C.c_int,
+                                        C.POINTER(C.c_void_p)]
+    lib.qtr_keyframe_get_info.argtypes = [C.c_void_p, C.POINTER(KeyframeInfo)]
+    lib.qtr_keyframe_fetch.restype = C.c_longlong
+    lib.qtr_keyframe_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+    lib.qtr_keyframe_destroy.restype = None
+    lib.qtr_keyframe_destroy.argtypes = [C.c_void_p, C.c_void_p]
+    lib.qtr_register_keyframes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(FrontendParams),
+                                           C.POINTER(Params), C.POINTER(Result), C.c_void_p, C.c_void_p, C.c_int]
+    lib.qtr_submit_batch_keyframes.argtypes = [C.c_void_p, C.POINTER(KfPairDesc), C.c_int, C.POINTER(FrontendParams),
+                                               C.POINTER(Params), C.POINTER(IcpParams), C.POINTER(Result),
+                                               C.POINTER(IcpResult)]
     _libs[LIB_PATH] = lib
     if path is None:
         _lib = lib
@@ -341,6 +367,39 @@ def _f4(a):
     a = np.ascontiguousarray(a, dtype=np.float32)
     assert a.ndim == 2 and a.shape[1] == 4, "points must be [N,4] float32 (x,y,z,pad)"
     return a
+
+
+class Keyframe:
+    """One scan's front end kept on the device (qtr_keyframe): made by Handle.keyframe, read-only, freed by close() / the
+    context manager — or by the handle's close() at the latest (it is then dead: do not use it afterwards)."""
+
+    def __init__(self, handle: "Handle", ptr: int):
+        self._handle, self._kf = handle, C.c_void_p(ptr)
+        info = KeyframeInfo()
+        handle._check(handle._lib.qtr_keyframe_get_info(self._kf, C.byref(info)))
+        self.info = {n: getattr(info, n) for n, _ in KeyframeInfo._fields_}
+
+    def fetch(self, what: int = KF_VOX) -> np.ndarray:
+        """KF_VOX / KF_NORMALS -> [n, 4], KF_FPFH -> [n, 33], KF_MEAN -> [4] float32, copied to the host."""
+        h = self._handle
+        nbytes = h._lib.qtr_keyframe_fetch(h._h, self._kf, what, None, 0)
+        if nbytes < 0:
+            raise QuatroHipError(-1, "qtr_keyframe_fetch failed")
+        out = np.zeros(nbytes // 4, dtype=np.float32)
+        if nbytes and h._lib.qtr_keyframe_fetch(h._h, self._kf, what, out.ctypes.data, nbytes) < 0:
+            raise QuatroHipError(-1, "qtr_keyframe_fetch failed")
+        return out.reshape(-1, 33) if what == KF_FPFH else out if what == KF_MEAN else out.reshape(-1, 4)
+
+    def close(self):
+        if self._kf and getattr(self._handle, "_h", None):
+            self._handle._lib.qtr_keyframe_destroy(self._handle._h, self._kf)
+        self._kf = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class Handle:
@@ -670,6 +729,65 @@ class Handle:
             r = results[i]
             if want_lists and r.status in (QTR_OK, QTR_ERR_CLIQUE_TOO_SMALL):
                 out.append(_result_dict(r, cl, None, fin))
+            else:
+                out.append({"status": r.status, "valid": bool(r.valid), "T": np.array(r.T[:]).reshape(4, 4),
+                            "cost": r.cost, "n_src": r.n_src, "n_tgt": r.n_tgt, "L": r.n_corr,
+                            "n_clique": r.n_clique, "n_final": r.n_final, "n_rot_inliers": r.n_rot_inliers})
+        if icp is None:
+            return out
+        return out, [_icp_dict(refined[i]) for i in range(B)]
+
+    # ---- keyframes: a scan's front end once, registrations against it many times
+    def keyframe(self, raw4, fp: FrontendParams | None = None, slot: int = 0) -> Keyframe:
+        """qtr_keyframe_create on a host scan ([P, 4] float32) or a contiguous torch device tensor."""
+        fp = fp or default_frontend_params()
+        if isinstance(raw4, np.ndarray):
+            raw4 = _f4(raw4)
+        ptr, mem = _ptr(raw4)
+        kf = C.c_void_p()
+        self._check(self._lib.qtr_keyframe_create(self._h, slot, ptr, int(raw4.shape[0]), C.byref(fp), mem, C.byref(kf)))
+        return Keyframe(self, kf.value)
+
+    def register_keyframes(self, kf_src: Keyframe, kf_tgt: Keyframe, fp: FrontendParams | None = None,
+                           params: Params | None = None, slot: int = 0):
+        """qtr_register_keyframes: register_pair's dict for two keyframes (fp's radii must be the keyframes')."""
+        fp = fp or default_frontend_params()
+        prm = params or demo_params()
+        res = Result()
+        cap = int(self.limits.max_corr)
+        cl = np.zeros(cap, dtype=np.int32)
+        fin = np.zeros(cap, dtype=np.int32)
+        rc = self._lib.qtr_register_keyframes(self._h, slot, kf_src._kf, kf_tgt._kf, C.byref(fp), C.byref(prm),
+                                              C.byref(res), cl.ctypes.data, fin.ctypes.data, cap)
+        self._check(rc, ok=(QTR_OK, QTR_ERR_CLIQUE_TOO_SMALL))
+        return _result_dict(res, cl, None, fin)
+
+    def register_batch_keyframes(self, pairs, fp: FrontendParams | None = None, params: Params | None = None,
+                                 icp: IcpParams | None = None, want_lists=True):
+        """pairs: sequence of (Keyframe src, Keyframe tgt, seed) through qtr_submit_batch_keyframes / qtr_wait.  Returns what
+        register_batch returns, or with icp what register_batch_refine returns: (results, refined)."""
+        fp = fp or default_frontend_params()
+        prm = params or demo_params()
+        B = len(pairs)
+        descs = (KfPairDesc * max(B, 1))()
+        results = (Result * max(B, 1))()
+        refined = None if icp is None else (IcpResult * max(B, 1))()
+        cap = int(self.limits.max_corr)
+        keep = []
+        for i, (ks, kt, seed) in enumerate(pairs):
+            cl = np.zeros(cap if want_lists else 1, dtype=np.int32)
+            fin = np.zeros(cap if want_lists else 1, dtype=np.int32)
+            keep.append((cl, fin))
+            descs[i] = KfPairDesc(ks._kf, kt._kf, int(seed), cl.ctypes.data if want_lists else None,
+                                  fin.ctypes.data if want_lists else None, cap)
+        self._check(self._lib.qtr_submit_batch_keyframes(self._h, descs, B, C.byref(fp), C.byref(prm),
+                                                         None if icp is None else C.byref(icp), results, refined))
+        self._check(self._lib.qtr_wait(self._h))
+        out = []
+        for i in range(B):
+            r = results[i]
+            if want_lists and r.status in (QTR_OK, QTR_ERR_CLIQUE_TOO_SMALL):
+                out.append(_result_dict(r, keep[i][0], None, keep[i][1]))
             else:
                 out.append({"status": r.status, "valid": bool(r.valid), "T": np.array(r.T[:]).reshape(4, 4),
                             "cost": r.cost, "n_src": r.n_src, "n_tgt": r.n_tgt, "L": r.n_corr,
