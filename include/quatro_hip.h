@@ -551,6 +551,72 @@ QTR_API int qtr_submit_batch_keyframes(qtr_handle* h, const qtr_kf_pair_desc* pa
                                        const qtr_params* prm, const qtr_icp_params* icp, qtr_result* results,
                                        qtr_icp_result* refined);
 
+/* Place index: WHICH keyframes are worth registering against.  One Scan Context descriptor (Kim & Kim, IROS 2018) per added
+ * keyframe — a num_rings x num_sectors polar image of the maximum height, row-major float32, plus the squared norm of
+ * every column — kept in device memory, and an exhaustive search: every entry of an id range is compared with the query
+ * under all num_sectors column shifts, the k most similar come back with their shift.  The shift is a yaw estimate, and
+ * Quatro is a yaw + translation solver: the two agree on what a revisit looks like (roll / pitch small).  The arithmetic,
+ * to the bit, is include/qtr_place_math.h's (host and device compile the same functions):
+ *   descriptor   per finite point: zh = z + height_offset (skipped unless > 0), r = sqrt(x^2 + y^2) (skipped unless
+ *                < max_range), ring = floor(r * num_rings / max_range), sector from atan2(y, x) + pi in num_sectors equal
+ *                bins; cell = max zh, 0 when empty.  A function of the point SET, not of its order.
+ *   distance     d(s) = mean over the columns j where both the query's column j and the entry's column (j + s) mod S are
+ *                non-zero of 1 - cosine; no such column: 1.  distance = min_s d(s), ties to the lowest s = shift;
+ *                yaw = shift * 2 pi / S wrapped to (-pi, pi]: the yaw of the transform that maps the QUERY into the
+ *                entry's frame, comparable with the yaw of qtr_register_keyframes(query, entry)'s T.
+ *   qtr_place_index_create   capacity entries of device memory (about 5 kB each at 20 x 60), owned by the handle;
+ *                            params NULL = the defaults.  qtr_destroy frees the indexes the caller did not destroy.
+ *   qtr_place_describe       the descriptor of n points (16-byte records, host or device per `mem`; n = 0: all zero) to
+ *                            `desc` (num_rings * num_sectors floats, in the same memory space).  Complete on return.
+ *   qtr_place_index_add      the descriptor of a keyframe's stored voxels (QTR_KF_VOX) becomes the next entry; ids are
+ *                            0, 1, 2, ... in order of addition.  A full index: QTR_ERR_CAPACITY, index unchanged.  A
+ *                            keyframe or an index of another handle: QTR_ERR_BAD_ARG.  Complete on return.
+ *   qtr_place_index_add_desc the same for a descriptor the caller made earlier (qtr_place_describe, or fetched from an
+ *                            index of a previous session: an index is saved with qtr_place_index_fetch and reloaded with
+ *                            this call).  Cells must be finite and >= 0 (not checked).
+ *   qtr_place_index_fetch    copies a stored item of entry `id` to host memory, like qtr_keyframe_fetch.
+ *   qtr_place_query          scores the entries id_lo <= id < id_hi (clamped to [0, size]; excluding the most recent
+ *                            keyframes is a smaller id_hi) against the keyframe's descriptor and writes the
+ *                            min(k, candidates) best to `out` (host) in ascending (distance, id) order, *n_out their
+ *                            number.  k: 1 .. 64.  An empty range: QTR_OK, *n_out = 0.  Complete on return, after ONE host
+ *                            wait.  The query's descriptor must have the index's shape: a keyframe always has.
+ *   qtr_place_query_desc     the same for a descriptor in host or device memory.
+ * Threading: a query only reads the index — any number of slots, from different host threads, may query one index at
+ * once.  An add writes it: add and query (and two adds) on the same index must be serialised by the caller. */
+typedef struct qtr_place_params {
+  int num_rings;       /* 20  (4 .. 32) */
+  int num_sectors;     /* 60  (8 .. 64: one wavefront lane per shift) */
+  float max_range;     /* 80.0 m, > 0 */
+  float height_offset; /* 2.0 m added to z (the sensor's height), so that heights are positive */
+} qtr_place_params;
+typedef struct qtr_place_match {
+  int id;         /* entry */
+  int shift;      /* column shift of the minimum */
+  float distance; /* 0 (the same place) .. 1 */
+  float yaw;      /* shift * 2 pi / num_sectors in (-pi, pi]: query -> entry */
+} qtr_place_match;
+typedef struct qtr_place_index qtr_place_index; /* opaque, owned by the handle that made it */
+typedef struct qtr_place_index_info {
+  qtr_place_params params;
+  int size, capacity;              /* entries held, entries it can hold */
+  unsigned long long device_bytes; /* HBM this index holds */
+} qtr_place_index_info;
+#define QTR_PLACE_DESC 1     /* float[num_rings][num_sectors] */
+#define QTR_PLACE_COLNORM2 2 /* float[num_sectors] squared column norms */
+QTR_API void qtr_default_place_params(qtr_place_params* p);
+QTR_API int qtr_place_index_create(qtr_handle* h, const qtr_place_params* params, int capacity, qtr_place_index** out);
+QTR_API void qtr_place_index_destroy(qtr_handle* h, qtr_place_index* index);
+QTR_API int qtr_place_index_get_info(const qtr_place_index* index, qtr_place_index_info* info);
+QTR_API int qtr_place_describe(qtr_handle* h, int slot, const qtr_place_params* params, const float* xyz4, int n, float* desc,
+                               int mem);
+QTR_API int qtr_place_index_add(qtr_handle* h, int slot, qtr_place_index* index, const qtr_keyframe* kf, int* id_out);
+QTR_API int qtr_place_index_add_desc(qtr_handle* h, int slot, qtr_place_index* index, const float* desc, int mem, int* id_out);
+QTR_API long long qtr_place_index_fetch(qtr_handle* h, const qtr_place_index* index, int id, int what, void* dst, size_t bytes);
+QTR_API int qtr_place_query(qtr_handle* h, int slot, const qtr_place_index* index, const qtr_keyframe* query, int id_lo,
+                            int id_hi, int k, qtr_place_match* out, int* n_out);
+QTR_API int qtr_place_query_desc(qtr_handle* h, int slot, const qtr_place_index* index, const float* desc, int mem, int id_lo,
+                                 int id_hi, int k, qtr_place_match* out, int* n_out);
+
 /* Inspection of intermediates of the LAST call on a slot (tests / parity debugging).  Copies up to
  * `bytes` bytes to host memory `dst`; returns the number of bytes the item holds, or <0 on error. */
 #define QTR_DBG_GRAPH_BITMAP 1   /* uint64[L][ceil(L/64)] adjacency, original labels */

@@ -542,3 +542,25 @@ def register_one_to_many(handle, query_kf, candidate_kfs, fp=None, params=None, 
     if icp is None:
         return out, best_candidate(out)
     return out[0], out[1], best_candidate(out[0])
+
+
+def close_loop(handle, index, keyframes, query_kf, k, id_lo=0, id_hi=None, fp=None, params=None, icp=None):
+    """Loop closing from the first link: index.query(query_kf) picks the k entries of [id_lo, id_hi) whose Scan Context
+    descriptors are most similar (quatro_amd.lib.PlaceIndex), keyframes[id] are their keyframes, and register_one_to_many
+    registers the query against exactly those, in the order the search returned them.  Returns a dict: "matches" (the
+    search's dicts id / shift / distance / yaw), "records" (and "refined" with icp), "best" (best_candidate's index into
+    them, -1 when no registration is valid) and "best_id" (the index entry of the winner, -1 likewise).  No candidate —
+    an empty id range — registers nothing.  Host-side glue over existing calls."""
+    matches = index.query(query_kf, k, id_lo, id_hi)
+    out = {"matches": matches, "records": [], "best": -1, "best_id": -1}
+    if icp is not None:
+        out["refined"] = []
+    if not matches:
+        return out
+    got = register_one_to_many(handle, query_kf, [keyframes[m["id"]] for m in matches], fp, params, icp)
+    out["records"], out["best"] = got[0], got[-1]
+    if icp is not None:
+        out["refined"] = got[1]
+    if out["best"] >= 0:
+        out["best_id"] = matches[out["best"]]["id"]
+    return out

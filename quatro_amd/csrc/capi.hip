@@ -61,6 +61,7 @@ struct Slot {
   double reg_T[16] = {};         // ... and its transform
   int icp_ns = 0, icp_iters = 0; // source points and updates of the last ICP call (debug ids)
   float icp_ms[2] = {0, 0};      // its grid build and its iterations, milliseconds
+  PlaceScratch place;            // place-index scratch (allocated / grown on the first query or add: place.hip)
 };
 
 // One lane of the batch driver (qtr_submit_batch): a contiguous group of slots stepped through the three launch
@@ -87,6 +88,14 @@ struct qtr_keyframe {
   qtr_handle* owner = nullptr;
   void* dev = nullptr;
   qtr_keyframe_info info = {};
+};
+
+// A place index (place.hip): capacity entries of `stride` floats, entries [0, size) filled.
+struct qtr_place_index {
+  qtr_handle* owner = nullptr;
+  float* dev = nullptr;
+  int stride = 0;
+  qtr_place_index_info info = {};
 };
 
 struct BatchJob {
@@ -142,6 +151,7 @@ struct qtr_handle {
   int icp_block = 0;  // QTR_ICP_BLOCK=n: ICP launches enqueued between two read-backs of the stop flag (0: all at once)
   std::mutex kf_mu;                    // guards `keyframes` (qtr_keyframe_create / _destroy from several threads)
   std::vector<qtr_keyframe*> keyframes;  // the live keyframes of this handle: qtr_destroy frees what the caller forgot
+  std::vector<qtr_place_index*> place_indexes;  // the live place indexes, likewise (under kf_mu)
   char err[512];
 };
 
@@ -401,6 +411,11 @@ void qtr_destroy(qtr_handle* h) {
     delete kf;
   }
   h->keyframes.clear();
+  for (qtr_place_index* ix : h->place_indexes) {
+    if (ix->dev) (void)hipFree(ix->dev);
+    delete ix;
+  }
+  h->place_indexes.clear();
   for (auto& l : h->lanes) {
     if (l.stage.h) (void)hipHostFree(l.stage.h);
     if (l.stage.d) (void)hipFree(l.stage.d);
@@ -430,6 +445,8 @@ void qtr_destroy(qtr_handle* h) {
     if (s.pw_arena) (void)hipFree(s.pw_arena);
     if (s.ex_arena) (void)hipFree(s.ex_arena);
     icp_free(s.icp);
+    if (s.place.arena) (void)hipFree(s.place.arena);
+    if (s.place.pin) (void)hipHostFree(s.place.pin);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.stream2) (void)hipStreamDestroy(s.stream2);
   }
@@ -2143,6 +2160,274 @@ void qtr_keyframe_destroy(qtr_handle* h, qtr_keyframe* kf) {
   (void)hipSetDevice(h->device);
   if (kf->dev) (void)hipFree(kf->dev);
   delete kf;
+}
+
+// ------------------------------------------------------------------------------------------------
+// place index (place.hip): one Scan Context descriptor per keyframe, exhaustive search under all column shifts
+void qtr_default_place_params(qtr_place_params* p) {
+  if (!p) return;
+  p->num_rings = 20;
+  p->num_sectors = 60;
+  p->max_range = 80.0f;
+  p->height_offset = 2.0f;
+}
+
+static int check_place_params(qtr_handle* h, const qtr_place_params* p) {
+  if (p->num_rings < 4 || p->num_rings > QTR_PLACE_MAX_RINGS || p->num_sectors < 8 || p->num_sectors > QTR_PLACE_MAX_SECTORS ||
+      !(p->max_range > 0.0f) || (p->max_range - p->max_range) != 0.0f || (p->height_offset - p->height_offset) != 0.0f) {
+    snprintf(h->err, sizeof(h->err), "place params: num_rings %d (4 .. %d), num_sectors %d (8 .. %d), max_range %g (> 0), "
+             "height_offset %g (finite)", p->num_rings, QTR_PLACE_MAX_RINGS, p->num_sectors, QTR_PLACE_MAX_SECTORS, p->max_range,
+             p->height_offset);
+    return QTR_ERR_BAD_ARG;
+  }
+  return QTR_OK;
+}
+
+static int check_place_index(qtr_handle* h, const qtr_place_index* ix) {
+  if (!ix) {
+    snprintf(h->err, sizeof(h->err), "place index is NULL");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (ix->owner != h) {
+    snprintf(h->err, sizeof(h->err), "place index belongs to another handle");
+    return QTR_ERR_BAD_ARG;
+  }
+  return QTR_OK;
+}
+
+// the slot's scratch for entries of `stride` floats and searches over up to `cap` entries (it only ever grows; the slot's
+// earlier place calls were complete when they returned, so nothing reads the old arena)
+static int place_scratch_ensure(qtr_handle* h, Slot& s, int stride, int cap) {
+  PlaceScratch& sc = s.place;
+  if (!sc.pin) QTR_HIP_TRY(h, hipHostMalloc((void**)&sc.pin, sizeof(qtr_place_match) * QTR_PLACE_MAX_K));
+  if (sc.arena && stride <= sc.stride && cap <= sc.cap) return QTR_OK;
+  stride = std::max(stride, sc.stride);
+  cap = std::max(std::max(cap, sc.cap), 1);
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o_keys = up((size_t)stride * 4), o_shifts = o_keys + up((size_t)cap * 8), o_out = o_shifts + up((size_t)cap * 4),
+               total = o_out + up(sizeof(qtr_place_match) * QTR_PLACE_MAX_K);
+  if (sc.arena) {
+    QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
+    (void)hipFree(sc.arena);
+    sc.arena = nullptr;
+    sc.stride = sc.cap = 0;
+  }
+  if (hipMalloc(&sc.arena, total) != hipSuccess) {
+    (void)hipGetLastError();
+    sc.arena = nullptr;
+    snprintf(h->err, sizeof(h->err), "place index: no device memory for %zu bytes of scratch", total);
+    return QTR_ERR_HIP;
+  }
+  char* a = (char*)sc.arena;
+  sc.q = (float*)a;
+  sc.keys = (u64*)(a + o_keys);
+  sc.shifts = (int*)(a + o_shifts);
+  sc.out = (qtr_place_match*)(a + o_out);
+  sc.stride = stride;
+  sc.cap = cap;
+  return QTR_OK;
+}
+
+int qtr_place_index_create(qtr_handle* h, const qtr_place_params* params, int capacity, qtr_place_index** out) {
+  if (out) *out = nullptr;
+  if (!h || !out) return QTR_ERR_BAD_ARG;
+  qtr_place_params p;
+  qtr_default_place_params(&p);
+  if (params) p = *params;
+  QTR_TRY(check_place_params(h, &p));
+  if (capacity < 1) {
+    snprintf(h->err, sizeof(h->err), "place index: capacity %d", capacity);
+    return QTR_ERR_BAD_ARG;
+  }
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  qtr_place_index* ix = new (std::nothrow) qtr_place_index();
+  if (!ix) return QTR_ERR_CAPACITY;
+  ix->stride = place_stride(p.num_rings, p.num_sectors);
+  const size_t bytes = (size_t)capacity * ix->stride * 4;
+  if (hipMalloc((void**)&ix->dev, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    delete ix;
+    snprintf(h->err, sizeof(h->err), "place index: no device memory for %zu bytes", bytes);
+    return QTR_ERR_HIP;
+  }
+  ix->owner = h;
+  ix->info.params = p;
+  ix->info.size = 0;
+  ix->info.capacity = capacity;
+  ix->info.device_bytes = (unsigned long long)bytes;
+  {
+    std::lock_guard<std::mutex> lk(h->kf_mu);
+    h->place_indexes.push_back(ix);
+  }
+  *out = ix;
+  return QTR_OK;
+}
+
+void qtr_place_index_destroy(qtr_handle* h, qtr_place_index* ix) {
+  if (!h || !ix || ix->owner != h) return;
+  {
+    std::lock_guard<std::mutex> lk(h->kf_mu);
+    auto it = std::find(h->place_indexes.begin(), h->place_indexes.end(), ix);
+    if (it == h->place_indexes.end()) return;
+    h->place_indexes.erase(it);
+  }
+  (void)hipSetDevice(h->device);
+  if (ix->dev) (void)hipFree(ix->dev);
+  delete ix;
+}
+
+int qtr_place_index_get_info(const qtr_place_index* ix, qtr_place_index_info* info) {
+  if (!ix || !info) return QTR_ERR_BAD_ARG;
+  *info = ix->info;
+  return QTR_OK;
+}
+
+int qtr_place_describe(qtr_handle* h, int slot, const qtr_place_params* params, const float* xyz4, int n, float* desc, int mem) {
+  Slot* sp = get_slot(h, slot);  // (a host cloud is staged in the slot's input arena)
+  if (!sp || !desc || n < 0 || (n > 0 && !xyz4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) return QTR_ERR_BAD_ARG;
+  Slot& s = *sp;
+  qtr_place_params p;
+  qtr_default_place_params(&p);
+  if (params) p = *params;
+  QTR_TRY(check_place_params(h, &p));
+  if (mem == QTR_MEM_HOST && n > h->lim.max_points) {
+    snprintf(h->err, sizeof(h->err), "cloud exceeds max_points=%d", h->lim.max_points);
+    return QTR_ERR_CAPACITY;
+  }
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  QTR_TRY(place_scratch_ensure(h, s, place_stride(p.num_rings, p.num_sectors), 1));
+  const float4* d_pts = (const float4*)xyz4;
+  if (mem == QTR_MEM_HOST && n > 0) {
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, xyz4, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
+    d_pts = s.in_src;
+  }
+  QTR_HIP_TRY(h, place_describe_enqueue(d_pts, n, p, s.place.q, s.stream));
+  QTR_HIP_TRY(h, hipMemcpyAsync(desc, s.place.q, (size_t)p.num_rings * p.num_sectors * 4,
+                                mem == QTR_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s.stream));
+  QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
+  return QTR_OK;
+}
+
+// the checks every add shares; on QTR_OK *entry is where the next entry goes
+static int place_add_begin(qtr_handle* h, qtr_place_index* ix, float** entry) {
+  QTR_TRY(check_place_index(h, ix));
+  if (ix->info.size >= ix->info.capacity) {
+    snprintf(h->err, sizeof(h->err), "place index is full (capacity %d)", ix->info.capacity);
+    return QTR_ERR_CAPACITY;
+  }
+  *entry = ix->dev + (size_t)ix->info.size * ix->stride;
+  return QTR_OK;
+}
+
+int qtr_place_index_add(qtr_handle* h, int slot, qtr_place_index* ix, const qtr_keyframe* kf, int* id_out) {
+  Slot* sp = peek_slot(h, slot);  // (nothing of the slot's clouds is touched: a registration on it can still be refined)
+  if (!sp || !ix || !kf) return QTR_ERR_BAD_ARG;
+  if (kf->owner != h) {
+    snprintf(h->err, sizeof(h->err), "keyframe belongs to another handle");
+    return QTR_ERR_BAD_ARG;
+  }
+  float* entry = nullptr;
+  QTR_TRY(place_add_begin(h, ix, &entry));
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  QTR_HIP_TRY(h, place_describe_enqueue((const float4*)((const char*)kf->dev + KF_HDR_BYTES), kf->info.n_voxels, ix->info.params,
+                                        entry, sp->stream));
+  QTR_HIP_TRY(h, hipStreamSynchronize(sp->stream));
+  if (id_out) *id_out = ix->info.size;
+  ix->info.size += 1;
+  return QTR_OK;
+}
+
+int qtr_place_index_add_desc(qtr_handle* h, int slot, qtr_place_index* ix, const float* desc, int mem, int* id_out) {
+  Slot* sp = peek_slot(h, slot);
+  if (!sp || !ix || !desc || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) return QTR_ERR_BAD_ARG;
+  float* entry = nullptr;
+  QTR_TRY(place_add_begin(h, ix, &entry));
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  const qtr_place_params& p = ix->info.params;
+  QTR_HIP_TRY(h, hipMemcpyAsync(entry, desc, (size_t)p.num_rings * p.num_sectors * 4,
+                                mem == QTR_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, sp->stream));
+  QTR_HIP_TRY(h, place_colnorm_enqueue(entry, p, sp->stream));
+  QTR_HIP_TRY(h, hipStreamSynchronize(sp->stream));
+  if (id_out) *id_out = ix->info.size;
+  ix->info.size += 1;
+  return QTR_OK;
+}
+
+long long qtr_place_index_fetch(qtr_handle* h, const qtr_place_index* ix, int id, int what, void* dst, size_t bytes) {
+  if (!h || !ix || ix->owner != h || id < 0 || id >= ix->info.size) return -1;
+  if (hipSetDevice(h->device) != hipSuccess) return -1;
+  const size_t cells = (size_t)ix->info.params.num_rings * ix->info.params.num_sectors;
+  size_t off = 0, have = 0;
+  switch (what) {
+    case QTR_PLACE_DESC: off = 0; have = cells * 4; break;
+    case QTR_PLACE_COLNORM2: off = cells * 4; have = (size_t)ix->info.params.num_sectors * 4; break;
+    default: return -1;
+  }
+  const size_t m = have < bytes ? have : bytes;
+  const char* src = (const char*)(ix->dev + (size_t)id * ix->stride) + off;
+  if (dst && m > 0 && hipMemcpy(dst, src, m, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  return (long long)have;
+}
+
+// the checks both queries share; on QTR_OK [*lo, *lo + *n) is the clamped range (*n may be 0)
+static int place_query_begin(qtr_handle* h, const qtr_place_index* ix, int id_lo, int id_hi, int k, int* lo, int* n) {
+  QTR_TRY(check_place_index(h, ix));
+  if (k < 1 || k > QTR_PLACE_MAX_K) {
+    snprintf(h->err, sizeof(h->err), "place query: k = %d (1 .. %d)", k, QTR_PLACE_MAX_K);
+    return QTR_ERR_BAD_ARG;
+  }
+  const int a = std::max(id_lo, 0), b = std::min(id_hi, ix->info.size);
+  *lo = a;
+  *n = b > a ? b - a : 0;
+  return QTR_OK;
+}
+// the search over [lo, lo + n), n >= 1, with the query's entry in the slot's scratch; the records come back through pinned
+// memory behind ONE wait
+static int place_query_finish(qtr_handle* h, Slot& s, const qtr_place_index* ix, int lo, int n, int k, qtr_place_match* out,
+                              int* n_out) {
+  const int kk = std::min(k, n);
+  QTR_HIP_TRY(h, place_search_enqueue(ix->dev, ix->info.params, lo, n, kk, s.place, s.stream));
+  QTR_HIP_TRY(h, hipMemcpyAsync(s.place.pin, s.place.out, sizeof(qtr_place_match) * kk, hipMemcpyDeviceToHost, s.stream));
+  QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
+  memcpy(out, s.place.pin, sizeof(qtr_place_match) * kk);
+  *n_out = kk;
+  return QTR_OK;
+}
+
+int qtr_place_query(qtr_handle* h, int slot, const qtr_place_index* ix, const qtr_keyframe* query, int id_lo, int id_hi, int k,
+                    qtr_place_match* out, int* n_out) {
+  if (n_out) *n_out = 0;
+  Slot* sp = peek_slot(h, slot);
+  if (!sp || !ix || !query || !out || !n_out) return QTR_ERR_BAD_ARG;
+  if (query->owner != h) {
+    snprintf(h->err, sizeof(h->err), "keyframe belongs to another handle");
+    return QTR_ERR_BAD_ARG;
+  }
+  int lo = 0, n = 0;
+  QTR_TRY(place_query_begin(h, ix, id_lo, id_hi, k, &lo, &n));
+  if (n == 0) return QTR_OK;
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  QTR_TRY(place_scratch_ensure(h, *sp, ix->stride, ix->info.capacity));
+  QTR_HIP_TRY(h, place_describe_enqueue((const float4*)((const char*)query->dev + KF_HDR_BYTES), query->info.n_voxels,
+                                        ix->info.params, sp->place.q, sp->stream));
+  return place_query_finish(h, *sp, ix, lo, n, k, out, n_out);
+}
+
+int qtr_place_query_desc(qtr_handle* h, int slot, const qtr_place_index* ix, const float* desc, int mem, int id_lo, int id_hi,
+                         int k, qtr_place_match* out, int* n_out) {
+  if (n_out) *n_out = 0;
+  Slot* sp = peek_slot(h, slot);
+  if (!sp || !ix || !desc || !out || !n_out || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) return QTR_ERR_BAD_ARG;
+  int lo = 0, n = 0;
+  QTR_TRY(place_query_begin(h, ix, id_lo, id_hi, k, &lo, &n));
+  if (n == 0) return QTR_OK;
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  QTR_TRY(place_scratch_ensure(h, *sp, ix->stride, ix->info.capacity));
+  const qtr_place_params& p = ix->info.params;
+  QTR_HIP_TRY(h, hipMemcpyAsync(sp->place.q, desc, (size_t)p.num_rings * p.num_sectors * 4,
+                                mem == QTR_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, sp->stream));
+  QTR_HIP_TRY(h, place_colnorm_enqueue(sp->place.q, p, sp->stream));
+  return place_query_finish(h, *sp, ix, lo, n, k, out, n_out);
 }
 
 // a pair of keyframes against the handle and the call's front-end knobs

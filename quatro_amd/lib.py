@@ -107,7 +107,21 @@ class KfPairDesc(C.Structure):
                 ("final_inliers", C.c_void_p), ("cap", C.c_int)]
 
 
+class PlaceParams(C.Structure):
+    _fields_ = [("num_rings", C.c_int), ("num_sectors", C.c_int), ("max_range", C.c_float), ("height_offset", C.c_float)]
+
+
+class PlaceMatch(C.Structure):
+    _fields_ = [("id", C.c_int), ("shift", C.c_int), ("distance", C.c_float), ("yaw", C.c_float)]
+
+
+class PlaceIndexInfo(C.Structure):
+    _fields_ = [("params", PlaceParams), ("size", C.c_int), ("capacity", C.c_int), ("device_bytes", C.c_ulonglong)]
+
+
 KF_VOX, KF_NORMALS, KF_FPFH, KF_MEAN = 1, 2, 3, 4
+PLACE_DESC, PLACE_COLNORM2 = 1, 2
+PLACE_MAX_K = 64
 
 EXPORTS = [
     "qtr_create", "qtr_destroy", "qtr_last_error", "qtr_default_limits", "qtr_default_params", "qtr_demo_params",
@@ -117,6 +131,9 @@ EXPORTS = [
     "qtr_default_icp_params", "qtr_icp", "qtr_refine_pair", "qtr_submit_batch_refine", "qtr_gicp",
     "qtr_keyframe_create", "qtr_keyframe_get_info", "qtr_keyframe_fetch", "qtr_keyframe_destroy", "qtr_register_keyframes",
     "qtr_submit_batch_keyframes",
+    "qtr_default_place_params", "qtr_place_index_create", "qtr_place_index_destroy", "qtr_place_index_get_info",
+    "qtr_place_describe", "qtr_place_index_add", "qtr_place_index_add_desc", "qtr_place_index_fetch", "qtr_place_query",
+    "qtr_place_query_desc",
 ]
 
 _lib = None
@@ -288,6 +305,21 @@ def load(path: str | None = None):
     lib.qtr_submit_batch_keyframes.argtypes = [C.c_void_p, C.POINTER(KfPairDesc), C.c_int, C.POINTER(FrontendParams),
                                                C.POINTER(Params), C.POINTER(IcpParams), C.POINTER(Result),
                                                C.POINTER(IcpResult)]
+    lib.qtr_default_place_params.restype = None
+    lib.qtr_default_place_params.argtypes = [C.POINTER(PlaceParams)]
+    lib.qtr_place_index_create.argtypes = [C.c_void_p, C.POINTER(PlaceParams), C.c_int, C.POINTER(C.c_void_p)]
+    lib.qtr_place_index_destroy.restype = None
+    lib.qtr_place_index_destroy.argtypes = [C.c_void_p, C.c_void_p]
+    lib.qtr_place_index_get_info.argtypes = [C.c_void_p, C.POINTER(PlaceIndexInfo)]
+    lib.qtr_place_describe.argtypes = [C.c_void_p, C.c_int, C.POINTER(PlaceParams), C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    lib.qtr_place_index_add.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    lib.qtr_place_index_add_desc.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    lib.qtr_place_index_fetch.restype = C.c_longlong
+    lib.qtr_place_index_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    lib.qtr_place_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.POINTER(PlaceMatch), C.POINTER(C.c_int)]
+    lib.qtr_place_query_desc.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(PlaceMatch), C.POINTER(C.c_int)]
     _libs[LIB_PATH] = lib
     if path is None:
         _lib = lib
@@ -333,6 +365,15 @@ def default_icp_params(**kw) -> IcpParams:
     """pcl::IterativeClosestPoint-style knobs (qtr_default_icp_params), fields overridden by keyword."""
     p = IcpParams()
     load().qtr_default_icp_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def default_place_params(**kw) -> PlaceParams:
+    """Scan Context's usual shape (qtr_default_place_params: 20 rings x 60 sectors, 80 m, +2 m), fields overridden by keyword."""
+    p = PlaceParams()
+    load().qtr_default_place_params(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p
@@ -394,6 +435,95 @@ class Keyframe:
         if self._kf and getattr(self._handle, "_h", None):
             self._handle._lib.qtr_keyframe_destroy(self._handle._h, self._kf)
         self._kf = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class PlaceIndex:
+    """A Scan Context place index on the device (qtr_place_index): made by Handle.place_index, freed by close() / the context
+    manager — or by the handle's close() at the latest.  Queries only read it (any number of slots at once); add / add_desc
+    write it and must not overlap a query or each other."""
+
+    def __init__(self, handle: "Handle", ptr: int):
+        self._handle, self._ix = handle, C.c_void_p(ptr)
+        self.params = PlaceParams()
+        info = self.info()
+        self.params = PlaceParams(*[getattr(info["params"], n) for n, _ in PlaceParams._fields_])
+        self.shape = (self.params.num_rings, self.params.num_sectors)
+
+    def info(self) -> dict:
+        i = PlaceIndexInfo()
+        self._handle._check(self._handle._lib.qtr_place_index_get_info(self._ix, C.byref(i)))
+        return {"params": i.params, "size": i.size, "capacity": i.capacity, "device_bytes": i.device_bytes}
+
+    def __len__(self) -> int:
+        return self.info()["size"]
+
+    def _desc(self, desc):
+        if isinstance(desc, np.ndarray):
+            desc = np.ascontiguousarray(desc, dtype=np.float32)
+        assert tuple(desc.shape) == self.shape, f"descriptor must be {self.shape}"
+        return desc
+
+    def describe(self, xyz4, slot: int = 0) -> np.ndarray:
+        """qtr_place_describe with this index's parameters: [num_rings, num_sectors] float32 (see Handle.place_describe)."""
+        return self._handle.place_describe(xyz4, self.params, slot)
+
+    def add(self, kf: Keyframe, slot: int = 0) -> int:
+        """qtr_place_index_add: the keyframe's descriptor becomes the next entry; returns its id."""
+        h, out = self._handle, C.c_int(-1)
+        h._check(h._lib.qtr_place_index_add(h._h, slot, self._ix, kf._kf, C.byref(out)))
+        return out.value
+
+    def add_desc(self, desc, slot: int = 0) -> int:
+        """qtr_place_index_add_desc: a descriptor made earlier (numpy, or a contiguous torch device tensor)."""
+        h, out = self._handle, C.c_int(-1)
+        ptr, mem = _ptr(self._desc(desc))
+        h._check(h._lib.qtr_place_index_add_desc(h._h, slot, self._ix, ptr, mem, C.byref(out)))
+        return out.value
+
+    def fetch(self, id: int, what: int = PLACE_DESC) -> np.ndarray:
+        """PLACE_DESC -> [num_rings, num_sectors], PLACE_COLNORM2 -> [num_sectors] float32 of entry `id`."""
+        h = self._handle
+        nbytes = h._lib.qtr_place_index_fetch(h._h, self._ix, int(id), what, None, 0)
+        if nbytes < 0:
+            raise QuatroHipError(-1, "qtr_place_index_fetch failed")
+        out = np.zeros(nbytes // 4, dtype=np.float32)
+        if h._lib.qtr_place_index_fetch(h._h, self._ix, int(id), what, out.ctypes.data, nbytes) < 0:
+            raise QuatroHipError(-1, "qtr_place_index_fetch failed")
+        return out.reshape(self.shape) if what == PLACE_DESC else out
+
+    @staticmethod
+    def _matches(out, n: int) -> list:
+        return [{"id": out[i].id, "shift": out[i].shift, "distance": np.float32(out[i].distance), "yaw": float(out[i].yaw)}
+                for i in range(n)]
+
+    def query(self, kf: Keyframe, k: int = 10, id_lo: int = 0, id_hi: int | None = None, slot: int = 0) -> list:
+        """qtr_place_query: the min(k, candidates) entries of [id_lo, id_hi) most similar to the keyframe, as dicts
+        id / shift / distance / yaw in ascending (distance, id) order."""
+        h, n = self._handle, C.c_int(0)
+        out = (PlaceMatch * PLACE_MAX_K)()
+        hi = 2 ** 31 - 1 if id_hi is None else int(id_hi)
+        h._check(h._lib.qtr_place_query(h._h, slot, self._ix, kf._kf, int(id_lo), hi, int(k), out, C.byref(n)))
+        return self._matches(out, n.value)
+
+    def query_desc(self, desc, k: int = 10, id_lo: int = 0, id_hi: int | None = None, slot: int = 0) -> list:
+        """qtr_place_query_desc: the same for a descriptor."""
+        h, n = self._handle, C.c_int(0)
+        out = (PlaceMatch * PLACE_MAX_K)()
+        hi = 2 ** 31 - 1 if id_hi is None else int(id_hi)
+        ptr, mem = _ptr(self._desc(desc))
+        h._check(h._lib.qtr_place_query_desc(h._h, slot, self._ix, ptr, mem, int(id_lo), hi, int(k), out, C.byref(n)))
+        return self._matches(out, n.value)
+
+    def close(self):
+        if self._ix and getattr(self._handle, "_h", None):
+            self._handle._lib.qtr_place_index_destroy(self._handle._h, self._ix)
+        self._ix = C.c_void_p()
 
     def __enter__(self):
         return self
@@ -795,6 +925,30 @@ class Handle:
         if icp is None:
             return out
         return out, [_icp_dict(refined[i]) for i in range(B)]
+
+    # ---- place index: which keyframes to register against
+    def place_index(self, capacity: int, params: PlaceParams | None = None) -> PlaceIndex:
+        """qtr_place_index_create: room for `capacity` Scan Context descriptors on the device."""
+        ix = C.c_void_p()
+        self._check(self._lib.qtr_place_index_create(self._h, None if params is None else C.byref(params), int(capacity),
+                                                     C.byref(ix)))
+        return PlaceIndex(self, ix.value)
+
+    def place_describe(self, xyz4, params: PlaceParams | None = None, slot: int = 0):
+        """qtr_place_describe: the [num_rings, num_sectors] descriptor of a host cloud ([n, 4] float32 -> numpy) or of a
+        contiguous torch device tensor (-> a torch tensor on the same device)."""
+        p = params or default_place_params()
+        if isinstance(xyz4, np.ndarray):
+            xyz4 = _f4(xyz4)
+            out = np.zeros((p.num_rings, p.num_sectors), dtype=np.float32)
+        else:
+            import torch
+            out = torch.zeros((p.num_rings, p.num_sectors), dtype=torch.float32, device=xyz4.device)
+        ptr, mem = _ptr(xyz4)
+        optr, _ = _ptr(out)
+        self._check(self._lib.qtr_place_describe(self._h, slot, C.byref(p), ptr if xyz4.shape[0] else None, int(xyz4.shape[0]),
+                                                 optr, mem))
+        return out
 
     def set_batch_preprocess(self, pw: "PwParams | None" = None, ip: "IpParams | None" = None, on: bool = True):
         """Raw sweeps through register_batch: Patchwork ground removal + range-image segmentation in front of the voxel
