@@ -15,8 +15,21 @@ namespace {
 // cells of side >= max_d from the origin: a point within max_d of q lies in one of the 27 cells around q's
 struct Cells {
   double side = 1;
-  std::unordered_map<int64_t, std::vector<int>> at;
-  static int64_t key(int64_t x, int64_t y, int64_t z) { return ((x + 1048576) * 2097152 + (y + 1048576)) * 2097152 + (z + 1048576); }
+  // (three whole indices per key, so a scene may lie any number of cells from the origin: map coordinates do)
+  struct Key {
+    int64_t x, y, z;
+    bool operator==(const Key& o) const { return x == o.x && y == o.y && z == o.z; }
+  };
+  struct Hash {
+    size_t operator()(const Key& k) const {
+      uint64_t h = (uint64_t)k.x * 0x9E3779B97F4A7C15ull;
+      h = (h ^ (h >> 29) ^ (uint64_t)k.y) * 0xBF58476D1CE4E5B9ull;
+      h = (h ^ (h >> 32) ^ (uint64_t)k.z) * 0x94D049BB133111EBull;
+      return (size_t)(h ^ (h >> 31));
+    }
+  };
+  std::unordered_map<Key, std::vector<int>, Hash> at;
+  static Key key(int64_t x, int64_t y, int64_t z) { return Key{x, y, z}; }
   double cell(double x) const { return std::floor(x / side); }
 };
 }  // namespace
@@ -42,8 +55,6 @@ extern "C" int gicp_ref_run(const float* src4, int ns, const float* src_nrm4, co
   for (int j = 0; j < nt; ++j) {  // the finite target points, ascending inside every cell
     const float* t = tgt4 + 4 * j;
     if (!qtr_icp_finite3(t[0], t[1], t[2])) continue;
-    // (scenes within 1e6 cells of the origin: the tests' are; beyond it neither side of the search is entered)
-    if (!(std::fabs(g.cell(t[0])) < 1e6 + 2 && std::fabs(g.cell(t[1])) < 1e6 + 2 && std::fabs(g.cell(t[2])) < 1e6 + 2)) continue;
     g.at[Cells::key((int64_t)g.cell(t[0]), (int64_t)g.cell(t[1]), (int64_t)g.cell(t[2]))].push_back(j);
   }
   if (ns > 0 && !g.at.empty()) st.reason = QTR_ICP_RUNNING;
@@ -59,7 +70,7 @@ extern "C" int gicp_ref_run(const float* src4, int ns, const float* src_nrm4, co
       if (qtr_icp_finite3(p[0], p[1], p[2]) && qtr_icp_normal_ok(a[0], a[1], a[2])) {
         qtr_icp_transform(st.T, p[0], p[1], p[2], q);
         const double f[3] = {g.cell(q[0]), g.cell(q[1]), g.cell(q[2])};
-        if (std::fabs(f[0]) < 1e6 && std::fabs(f[1]) < 1e6 && std::fabs(f[2]) < 1e6)  // (also false for NaN)
+        if (std::fabs(f[0]) < 1e15 && std::fabs(f[1]) < 1e15 && std::fabs(f[2]) < 1e15)  // (also false for NaN)
           for (int64_t dx = -1; dx <= 1; ++dx)
             for (int64_t dy = -1; dy <= 1; ++dy)
               for (int64_t dz = -1; dz <= 1; ++dz) {

@@ -13,6 +13,9 @@ import torch  # noqa: F401,E402
 from oracle import oracle as qo  # noqa: E402
 from quatro_amd import lib as ql  # noqa: E402
 from quatro_amd import synth  # noqa: E402
+import gicp_restate  # noqa: E402
+import icp_brute  # noqa: E402
+import icp_restate  # noqa: E402
 from test_gpu_parity import _random_graph_bitmap  # noqa: E402
 
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 0
@@ -37,7 +40,7 @@ qo.set_threads(qo.max_threads())
 hb = None  # a second handle with eight slots, for the batched cases
 # FUZZ_KINDS=batch,solve: only these kinds (a sweep of the batched entry's mixed-size groups alone finds what one case in twelve of
 # the full mix takes an hour to reach)
-KINDS = ["solve", "solve", "clique", "pair", "match", "match", "patchwork", "segment", "gnc3", "cote", "batch", "scout"]
+KINDS = ["solve", "solve", "clique", "pair", "match", "match", "patchwork", "segment", "gnc3", "cote", "batch", "scout", "icp", "icp"]
 if os.environ.get("FUZZ_KINDS"):
     KINDS = [k for k in os.environ["FUZZ_KINDS"].split(",") if k in KINDS]
 bad, n_cases, t_end = 0, 0, time.time() + budget
@@ -289,6 +292,50 @@ while time.time() < t_end:
             if not (np.array_equal(a["labels"], b["labels"]) and np.array_equal(a["valid"], b["valid"]) and
                     np.array_equal(a["outliers"], b["outliers"])):
                 report(kind, f"pair={pid} keep={keep} {lidar} {mode} {mp}", "labels/valid/outliers")
+        elif kind == "icp":
+            # one evaluation of the ICP loop at a perturbed guess: random clouds (the box scene, or a voxelised synthetic
+            # scan pair thinned at random), sizes on the 64 / 256 boundaries, max_d log-uniform over 0.02 .. 50 m (cells
+            # enlarged under the cap up to one-cell grids), every method; the restatement against the exhaustive search
+            # (CPU, also in the dry mode), then the device against both
+            max_d = float(np.exp(rng.uniform(np.log(0.02), np.log(50.0))))
+            method = int(rng.integers(0, 3))
+            sizes = [1, 2, 63, 64, 65, 255, 256, 257, 511, 513, 1000, 4097, 0]  # (0: the whole cloud)
+            n_s, n_t = int(rng.choice(sizes)), int(rng.choice(sizes))
+            sd = int(rng.integers(1 << 20))
+            if rng.random() < 0.5:
+                vs, sn, vt, tn, G0 = icp_brute.box_pair(n_s or 5100, n_t or 5100, sd)
+                scene = "box"
+            else:
+                pid = int(rng.integers(0, 50))
+                s, t, Tgt = synth.kitti64_pair(pid)
+                vs, vt = qo.voxelize(s, 0.3), qo.voxelize(t, 0.3)
+                if n_s:
+                    vs = vs[np.sort(rng.choice(vs.shape[0], min(n_s, vs.shape[0]), replace=False))]
+                if n_t:
+                    vt = vt[np.sort(rng.choice(vt.shape[0], min(n_t, vt.shape[0]), replace=False))]
+                sn, tn = qo.fpfh(vs, 0.5, 0.5)[0], qo.fpfh(vt, 0.5, 0.5)[0]
+                G0 = Tgt
+                scene = f"pair {pid}"
+            G0 = G0 @ icp_brute.rigid(icp_brute.rot(*rng.normal(0, 0.01, 3)), rng.normal(0, 0.2, 3))
+            desc = f"{scene} ns={vs.shape[0]} nt={vt.shape[0]} max_d={max_d:.4g} method={method} seed={sd}"
+            want = icp_brute.nearest(vs, vt, G0, max_d, tn, sn, method)
+            if method == 2:
+                o = gicp_restate.run(vs, sn, vt, tn, G0, max_d=max_d, max_iter=1, corr_iter=0)
+            else:
+                o = icp_restate.run(vs, vt, tn, G0, max_d=max_d, method=method, max_iter=1, corr_iter=0)
+            if not np.array_equal(o["corr"], want) or o["n_corr"] != int((want >= 0).sum()):
+                report(kind, desc, f"restatement vs exhaustive search: {int((o['corr'] != want).sum())} of {want.size} differ")
+            if not DRY:
+                prm = ql.default_icp_params(method=method, max_iterations=1, max_correspondence_distance=max_d)
+                g = h.gicp(vs, vt, sn, tn, G0, prm) if method == 2 else h.icp(vs, vt, tn, G0, prm)
+                corr = h.debug_fetch(ql.DBG_ICP_CORR, np.int32)
+                if not np.array_equal(corr, want):
+                    report(kind, desc, f"device vs exhaustive search: {int((corr != want).sum())} of {want.size} differ")
+                elif not (np.array_equal(g["T"].view(np.uint64), o["T"].view(np.uint64)) and
+                          all(g[k] == o[k] for k in ("iterations", "stop_reason", "n_corr", "valid", "converged")) and
+                          np.array([g["fitness"], g["rmse"]]).tobytes() == np.array([o["fitness"], o["rmse"]]).tobytes()):
+                    report(kind, desc, f"device vs restatement: n_corr {g['n_corr']} vs {o['n_corr']}, stop "
+                                       f"{g['stop_reason']} vs {o['stop_reason']}")
         elif kind == "gnc3":
             M = int(rng.choice([1, 2, 3, 64, 65, 500, 4000]))
             X = rng.uniform(-10, 10, (M, 3))

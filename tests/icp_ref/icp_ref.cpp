@@ -12,8 +12,21 @@
 namespace {
 struct Grid {
   double mn[3] = {0, 0, 0}, cell = 1;
-  std::unordered_map<int64_t, std::vector<int>> cells;
-  static int64_t key(int64_t x, int64_t y, int64_t z) { return (x * 2097152 + y) * 2097152 + z; }
+  // (three whole indices per key: a packed key wraps where a query lies millions of cells from the box)
+  struct Key {
+    int64_t x, y, z;
+    bool operator==(const Key& o) const { return x == o.x && y == o.y && z == o.z; }
+  };
+  struct Hash {
+    size_t operator()(const Key& k) const {
+      uint64_t h = (uint64_t)k.x * 0x9E3779B97F4A7C15ull;
+      h = (h ^ (h >> 29) ^ (uint64_t)k.y) * 0xBF58476D1CE4E5B9ull;
+      h = (h ^ (h >> 32) ^ (uint64_t)k.z) * 0x94D049BB133111EBull;
+      return (size_t)(h ^ (h >> 31));
+    }
+  };
+  std::unordered_map<Key, std::vector<int>, Hash> cells;
+  static Key key(int64_t x, int64_t y, int64_t z) { return Key{x, y, z}; }
 };
 }  // namespace
 
