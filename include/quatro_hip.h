@@ -551,6 +551,28 @@ QTR_API int qtr_submit_batch_keyframes(qtr_handle* h, const qtr_kf_pair_desc* pa
                                        const qtr_params* prm, const qtr_icp_params* icp, qtr_result* results,
                                        qtr_icp_result* refined);
 
+/* Submap keyframes: K keyframes fused under K poses into ONE keyframe, on the device.  Loop closing in LiDAR SLAM registers a
+ * query against the 2n + 1 keyframes around a candidate, moved into one frame by their odometry poses (the reference's
+ * historyKeyframeSearchNum, include/utility.h:127-131), not against one sweep.  The members' stored voxels (QTR_KF_VOX)
+ * are read where they are, each record moved by its member's pose with the arithmetic of include/qtr_submap_math.h
+ * (binary64 products and sums in a fixed association, one rounding to binary32, w copied) and written in member order —
+ * stored voxel order within a member — into the slot's raw-cloud buffer; the one-cloud front end and the pack of
+ * qtr_keyframe_create follow.  *out is the keyframe qtr_keyframe_create(h, slot, cat, N, fp, QTR_MEM_HOST, ..) returns for
+ * that concatenation `cat` of N = sum of the members' n_voxels records: every fetchable item bit-identical, every info
+ * field equal (n_points = N).  It is an ordinary keyframe: registration, the place index, fetch and destroy take it.
+ *   poses   K x 16 doubles, row-major 4 x 4 per member, rows 0 - 2 used; NULL: identities.
+ *   fp      the SUBMAP's knobs; the members' own leaf and radii play no part (only their voxels are read).
+ * QTR_ERR_BAD_ARG: K < 1, K > QTR_SUBMAP_MAX_KEYFRAMES, a NULL member or one of another handle, NULL fp or out, a non-finite
+ * entry in rows 0 - 2 of a pose.  QTR_ERR_CAPACITY: N (summed in 64 bits) exceeds qtr_limits.max_points.  Both are found
+ * before anything is enqueued; *out = NULL on every failure.  The front end's own errors and messages are
+ * qtr_keyframe_create's (max_voxels, the long-list arena, the pass-through).  A member may appear more than once.  A set-up
+ * call like qtr_keyframe_create: it returns after the pack has completed.  Members are only read: several slots, from
+ * different host threads, may merge from the same members at once. */
+#define QTR_SUBMAP_MAX_KEYFRAMES 64
+QTR_API int qtr_keyframe_merge(qtr_handle* h, int slot, const qtr_keyframe* const* kfs,
+                               const double* poses /* K x 16, NULL = identities */, int K,
+                               const qtr_frontend_params* fp, qtr_keyframe** out);
+
 /* Place index: WHICH keyframes are worth registering against.  One Scan Context descriptor (Kim & Kim, IROS 2018) per added
  * keyframe — a num_rings x num_sectors polar image of the maximum height, row-major float32, plus the squared norm of
  * every column — kept in device memory, and an exhaustive search: every entry of an id range is compared with the query

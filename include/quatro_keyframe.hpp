@@ -3,10 +3,12 @@
 // registers one query against many candidates (register_one_to_many), odometry reuses scan k's keyframe as the source of
 // pair (k, k + 1) — the reference's FPFHManager::is_odometry_test_ (include/fpfh_manager.hpp:111-118) without carrying
 // descriptors through host vectors.  Results are bit-identical to the raw-scan path (qtr_register_pair).
+// Keyframe::merge fuses keyframes under their poses into one submap keyframe, which every call here takes like any other.
 // Host code only; link with -lquatro_hip.
 #ifndef QUATRO_KEYFRAME_H
 #define QUATRO_KEYFRAME_H
 
+#include <stdexcept>
 #include <utility>
 #include <vector>
 
@@ -46,6 +48,26 @@ class Keyframe {
     qtr_keyframe_info i{};
     check(default_handle(), qtr_keyframe_get_info(kf_, &i));
     return i;
+  }
+  // A submap: the members' stored voxels, member k moved by poses[16 * k .. 16 * k + 15] (row-major 4 x 4, rows 0 - 2 used;
+  // poses empty: identities), fused on the device into one keyframe with the submap's own fp (qtr_keyframe_merge).  slot < 0:
+  // a leased slot.
+  static Keyframe merge(qtr_handle* handle, int slot, const std::vector<const Keyframe*>& members,
+                        const std::vector<double>& poses, const qtr_frontend_params& fp) {
+    if (!poses.empty() && poses.size() != 16 * members.size())
+      throw std::invalid_argument("[quatro_hip] Keyframe::merge: 16 doubles per member");
+    if (handle != default_handle()) throw std::invalid_argument("[quatro_hip] Keyframe::merge: not the process-wide handle");
+    std::vector<const qtr_keyframe*> kfs(members.size());
+    for (size_t k = 0; k < members.size(); ++k) kfs[k] = members[k] ? members[k]->get() : nullptr;
+    Keyframe out;
+    const double* p = poses.empty() ? nullptr : poses.data();
+    if (slot >= 0) {
+      check(handle, qtr_keyframe_merge(handle, slot, kfs.data(), p, static_cast<int>(kfs.size()), &fp, &out.kf_));
+    } else {
+      SlotLease lease;
+      check(handle, qtr_keyframe_merge(handle, lease.slot, kfs.data(), p, static_cast<int>(kfs.size()), &fp, &out.kf_));
+    }
+    return out;
   }
   // QTR_KF_VOX / _NORMALS / _FPFH / _MEAN as floats
   std::vector<float> fetch(int what) const {

@@ -544,20 +544,55 @@ def register_one_to_many(handle, query_kf, candidate_kfs, fp=None, params=None, 
     return out[0], out[1], best_candidate(out[0])
 
 
-def close_loop(handle, index, keyframes, query_kf, k, id_lo=0, id_hi=None, fp=None, params=None, icp=None):
+def make_submap(handle, keyframes, poses, center, half_width, fp=None, id_lo=0, id_hi=None, slot=0):
+    """The submap around keyframe `center`: the keyframes center - half_width .. center + half_width, clipped to
+    [id_lo, id_hi) (id_hi = None: len(keyframes)), fused into one Keyframe by Handle.merge_keyframes.  Member i travels
+    under inv(poses[center]) @ poses[i] (float64; poses[i]: 4 x 4, keyframe i's frame -> the map frame), so the submap lives
+    in the centre keyframe's frame and a registration against it yields what one against the centre keyframe would.  fp
+    belongs to the submap.  The caller closes the returned Keyframe."""
+    id_hi = len(keyframes) if id_hi is None else min(int(id_hi), len(keyframes))
+    lo, hi = max(int(center) - int(half_width), int(id_lo), 0), min(int(center) + int(half_width) + 1, id_hi)
+    if not lo <= center < hi:
+        raise ValueError(f"make_submap: centre {center} is outside the id range [{id_lo}, {id_hi})")
+    inv_c = np.linalg.inv(np.asarray(poses[center], dtype=np.float64))
+    rel = np.stack([inv_c @ np.asarray(poses[i], dtype=np.float64) for i in range(lo, hi)])
+    return handle.merge_keyframes([keyframes[i] for i in range(lo, hi)], rel, fp, slot)
+
+
+def close_loop(handle, index, keyframes, query_kf, k, id_lo=0, id_hi=None, fp=None, params=None, icp=None, poses=None,
+               submap_half_width=0):
     """Loop closing from the first link: index.query(query_kf) picks the k entries of [id_lo, id_hi) whose Scan Context
     descriptors are most similar (quatro_amd.lib.PlaceIndex), keyframes[id] are their keyframes, and register_one_to_many
     registers the query against exactly those, in the order the search returned them.  Returns a dict: "matches" (the
     search's dicts id / shift / distance / yaw), "records" (and "refined" with icp), "best" (best_candidate's index into
     them, -1 when no registration is valid) and "best_id" (the index entry of the winner, -1 likewise).  No candidate —
-    an empty id range — registers nothing.  Host-side glue over existing calls."""
+    an empty id range — registers nothing.  Host-side glue over existing calls.
+
+    submap_half_width = n > 0 (poses required: one 4 x 4 per keyframe, its frame -> the map frame): every match `id` is
+    registered as make_submap around id — the 2 n + 1 keyframes id - n .. id + n under their poses, clipped to the searched
+    id range [id_lo, id_hi) — id_hi = None: the index's size — so the query's own neighbourhood is never fused.  The submaps are temporary: destroyed when the job is done.
+    The transforms still map the query into keyframe id's frame."""
+    if submap_half_width > 0 and poses is None:
+        raise ValueError("close_loop: submap_half_width > 0 needs the keyframes' poses")
     matches = index.query(query_kf, k, id_lo, id_hi)
     out = {"matches": matches, "records": [], "best": -1, "best_id": -1}
     if icp is not None:
         out["refined"] = []
     if not matches:
         return out
-    got = register_one_to_many(handle, query_kf, [keyframes[m["id"]] for m in matches], fp, params, icp)
+    submaps = []
+    try:
+        if submap_half_width > 0:
+            hi = len(index) if id_hi is None else id_hi
+            for m in matches:
+                submaps.append(make_submap(handle, keyframes, poses, m["id"], submap_half_width, fp, id_lo, hi))
+            targets = submaps
+        else:
+            targets = [keyframes[m["id"]] for m in matches]
+        got = register_one_to_many(handle, query_kf, targets, fp, params, icp)
+    finally:
+        for sm in submaps:
+            sm.close()
     out["records"], out["best"] = got[0], got[-1]
     if icp is not None:
         out["refined"] = got[1]

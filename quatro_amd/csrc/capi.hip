@@ -62,6 +62,8 @@ struct Slot {
   int icp_ns = 0, icp_iters = 0; // source points and updates of the last ICP call (debug ids)
   float icp_ms[2] = {0, 0};      // its grid build and its iterations, milliseconds
   PlaceScratch place;            // place-index scratch (allocated / grown on the first query or add: place.hip)
+  KfGatherMember* merge_pin = nullptr;  // qtr_keyframe_merge: the member table in pinned host memory and its device copy
+  KfGatherMember* merge_dev = nullptr;  // (QTR_SUBMAP_MAX_KEYFRAMES records each, allocated on the slot's first merge)
 };
 
 // One lane of the batch driver (qtr_submit_batch): a contiguous group of slots stepped through the three launch
@@ -447,6 +449,8 @@ void qtr_destroy(qtr_handle* h) {
     icp_free(s.icp);
     if (s.place.arena) (void)hipFree(s.place.arena);
     if (s.place.pin) (void)hipHostFree(s.place.pin);
+    if (s.merge_pin) (void)hipHostFree(s.merge_pin);
+    if (s.merge_dev) (void)hipFree(s.merge_dev);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.stream2) (void)hipStreamDestroy(s.stream2);
   }
@@ -1987,14 +1991,13 @@ int qtr_feature_pair(qtr_handle* h, int slot, const float* src_raw4, int Ps, con
 // The one-cloud front end on cloud[0] of a slot: voxel grid -> mean -> FPFH chain with the matcher's per-descriptor
 // preparation, under front_device's rules (pass-through, radix-pass speculation, long_lists retry, capacity errors).  The
 // counters a whole-path call receives in its matcher's mail are read back here: nothing runs a matcher.
-static int front_one_device(qtr_handle* h, Slot& s, const float* raw4, int P, const qtr_frontend_params* fp, int mem,
-                            int* n_out, int* passed_out) {
-  int rc = QTR_OK;
+// What the one-cloud front end refuses before anything is enqueued.
+static int front_one_check(qtr_handle* h, bool have_cloud, int P, const qtr_frontend_params* fp) {
   if (fp->normal_radius > fp->fpfh_radius) {
     snprintf(h->err, sizeof(h->err), "[FPFHManager]: Normal should be lower than fpfh_radius!!!!");
     return QTR_ERR_BAD_ARG;
   }
-  if (P <= 0 || !raw4) {
+  if (P <= 0 || !have_cloud) {
     snprintf(h->err, sizeof(h->err), "Invalid or empty point cloud dataset given!");
     return QTR_ERR_BAD_ARG;
   }
@@ -2002,12 +2005,14 @@ static int front_one_device(qtr_handle* h, Slot& s, const float* raw4, int P, co
     snprintf(h->err, sizeof(h->err), "cloud exceeds max_points=%d", h->lim.max_points);
     return QTR_ERR_CAPACITY;
   }
-  QTR_HIP_TRY(h, hipSetDevice(h->device));
-  const float4* d_raw = (const float4*)raw4;
-  if (mem == QTR_MEM_HOST) {
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, raw4, (size_t)P * 16, hipMemcpyHostToDevice, s.stream));
-    d_raw = s.in_src;
-  }
+  return QTR_OK;
+}
+
+// The chain itself, on P points that are in device memory — or on their way there on the slot's stream (a staged host scan,
+// the gathered voxels of a merge): front_one_check passed and the device is set.
+static int front_one_chain(qtr_handle* h, Slot& s, const float4* d_raw, int P, const qtr_frontend_params* fp, int* n_out,
+                           int* passed_out) {
+  int rc = QTR_OK;
   auto fail_drained = [&](int code) {  // (see front_device: the scan is not handed back while a kernel may still read it)
     (void)hipStreamSynchronize(s.stream);
     return code;
@@ -2076,22 +2081,27 @@ static int front_one_device(qtr_handle* h, Slot& s, const float* raw4, int P, co
   }
   if (!h->long_lists && s.pinned_i32[CNT_NBR_OVERFLOW]) {  // (see front_device: the chain ran without k2_neighbors_big)
     h->long_lists = true;
-    return front_one_device(h, s, raw4, P, fp, mem, n_out, passed_out);
+    return front_one_chain(h, s, d_raw, P, fp, n_out, passed_out);  // (the input is where it was: nothing of the chain writes it)
   }
   *n_out = n;
   *passed_out = pass ? 1 : 0;
   return QTR_OK;
 }
 
-int qtr_keyframe_create(qtr_handle* h, int slot, const float* raw4, int P, const qtr_frontend_params* fp, int mem,
-                        qtr_keyframe** out) {
-  if (out) *out = nullptr;
-  Slot* sp = get_slot(h, slot);
-  if (!sp || !fp || !out) return QTR_ERR_BAD_ARG;
-  Slot& s = *sp;
-  s.times_pending = 0;
-  int n = 0, passed = 0;
-  QTR_TRY(front_one_device(h, s, raw4, P, fp, mem, &n, &passed));
+static int front_one_device(qtr_handle* h, Slot& s, const float* raw4, int P, const qtr_frontend_params* fp, int mem,
+                            int* n_out, int* passed_out) {
+  QTR_TRY(front_one_check(h, raw4 != nullptr, P, fp));
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  const float4* d_raw = (const float4*)raw4;
+  if (mem == QTR_MEM_HOST) {
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, raw4, (size_t)P * 16, hipMemcpyHostToDevice, s.stream));
+    d_raw = s.in_src;
+  }
+  return front_one_chain(h, s, d_raw, P, fp, n_out, passed_out);
+}
+
+// The front end's products on cloud[0] of the slot -> a keyframe of their size (the pack), complete on return.
+static int keyframe_pack(qtr_handle* h, Slot& s, const qtr_frontend_params* fp, int P, int n, int passed, qtr_keyframe** out) {
   qtr_keyframe* kf = new (std::nothrow) qtr_keyframe();
   if (!kf) return QTR_ERR_CAPACITY;
   const KfLayout lay = kf_layout(n);
@@ -2123,6 +2133,76 @@ int qtr_keyframe_create(qtr_handle* h, int slot, const float* raw4, int P, const
   }
   *out = kf;
   return QTR_OK;
+}
+
+int qtr_keyframe_create(qtr_handle* h, int slot, const float* raw4, int P, const qtr_frontend_params* fp, int mem,
+                        qtr_keyframe** out) {
+  if (out) *out = nullptr;
+  Slot* sp = get_slot(h, slot);
+  if (!sp || !fp || !out) return QTR_ERR_BAD_ARG;
+  Slot& s = *sp;
+  s.times_pending = 0;
+  int n = 0, passed = 0;
+  QTR_TRY(front_one_device(h, s, raw4, P, fp, mem, &n, &passed));
+  return keyframe_pack(h, s, fp, P, n, passed, out);
+}
+
+// K keyframes under K poses -> one keyframe: the members' stored voxels are gathered on the device into the slot's raw-cloud
+// buffer (k_kf_gather, one launch), and from there on the call is qtr_keyframe_create on a cloud that is already staged.
+int qtr_keyframe_merge(qtr_handle* h, int slot, const qtr_keyframe* const* kfs, const double* poses, int K,
+                       const qtr_frontend_params* fp, qtr_keyframe** out) {
+  if (out) *out = nullptr;
+  Slot* sp = get_slot(h, slot);
+  if (!sp || !fp || !out) return QTR_ERR_BAD_ARG;
+  Slot& s = *sp;
+  s.times_pending = 0;
+  if (K < 1 || K > QTR_SUBMAP_MAX_KEYFRAMES || !kfs) {
+    snprintf(h->err, sizeof(h->err), "keyframe merge: %d members (1 .. %d)", K, QTR_SUBMAP_MAX_KEYFRAMES);
+    return QTR_ERR_BAD_ARG;
+  }
+  long long N = 0;
+  int max_n = 0;
+  for (int k = 0; k < K; ++k) {
+    if (!kfs[k]) {
+      snprintf(h->err, sizeof(h->err), "keyframe merge: member %d is NULL", k);
+      return QTR_ERR_BAD_ARG;
+    }
+    if (kfs[k]->owner != h) {
+      snprintf(h->err, sizeof(h->err), "keyframe belongs to another handle");
+      return QTR_ERR_BAD_ARG;
+    }
+    if (poses && !qtr_submap_pose_finite(poses + 16 * k)) {
+      snprintf(h->err, sizeof(h->err), "keyframe merge: the pose of member %d has a non-finite entry in rows 0 - 2", k);
+      return QTR_ERR_BAD_ARG;
+    }
+    N += kfs[k]->info.n_voxels;
+    max_n = std::max(max_n, kfs[k]->info.n_voxels);
+  }
+  if (N > (long long)h->lim.max_points) {
+    snprintf(h->err, sizeof(h->err), "keyframe merge: the members hold %lld voxels, which exceeds max_points=%d", N,
+             h->lim.max_points);
+    return QTR_ERR_CAPACITY;
+  }
+  QTR_TRY(front_one_check(h, true, (int)N, fp));
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  if (!s.merge_pin) QTR_HIP_TRY(h, hipHostMalloc((void**)&s.merge_pin, sizeof(KfGatherMember) * QTR_SUBMAP_MAX_KEYFRAMES));
+  if (!s.merge_dev) QTR_HIP_TRY(h, hipMalloc((void**)&s.merge_dev, sizeof(KfGatherMember) * QTR_SUBMAP_MAX_KEYFRAMES));
+  // (the slot's last merge had completed when it returned: nothing reads the pinned table any more)
+  static const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  int prefix = 0;
+  for (int k = 0; k < K; ++k) {
+    KfGatherMember& m = s.merge_pin[k];
+    m.vox = (const float4*)((const char*)kfs[k]->dev + KF_HDR_BYTES);
+    m.n = kfs[k]->info.n_voxels;
+    m.prefix = prefix;
+    memcpy(m.T, poses ? poses + 16 * k : ident, sizeof(m.T));
+    prefix += m.n;
+  }
+  QTR_HIP_TRY(h, hipMemcpyAsync(s.merge_dev, s.merge_pin, sizeof(KfGatherMember) * (size_t)K, hipMemcpyHostToDevice, s.stream));
+  QTR_HIP_TRY(h, kf_gather_enqueue(s.merge_dev, K, max_n, s.in_src, s.stream));
+  int n = 0, passed = 0;
+  QTR_TRY(front_one_chain(h, s, s.in_src, (int)N, fp, &n, &passed));
+  return keyframe_pack(h, s, fp, (int)N, n, passed, out);
 }
 
 int qtr_keyframe_get_info(const qtr_keyframe* kf, qtr_keyframe_info* info) {

@@ -5,11 +5,14 @@
 //          qtr_submit_batch_keyframes) counters, and the matcher's per-descriptor preparation that k2_fpfh does on the
 //                                     whole path (|d|^2, hash, entry in the duplicate table), so that the matcher starts at
 //                                     its operand tables with prep_done = true
+//   merge (qtr_keyframe_merge)        K keyframes' voxels -> a slot's raw-cloud buffer, each member under its pose
+//                                     (k_kf_gather, include/qtr_submap_math.h); the one-cloud front end and the pack follow
 // Stored per voxel: 16 (point) + 16 (normal, curvature) + 132 (descriptor) + 4 (|d|^2) + 8 (descriptor hash) = 176 bytes.
 // Not stored: neighbour lists, SPFH, sort buffers, the cell table, the duplicate table (its size follows the handle's
 // max_voxels, not the scan: the load rebuilds it from the stored hashes) and the matcher's per-pair tables.
 #include "common.h"
 #include "frontend.h"
+#include "../../include/qtr_submap_math.h"
 
 #define KF_HDR_BYTES 256  // 16 counters (CNT_*), then the 4 floats of the sequential mean
 #define KF_ALIGN 256
@@ -178,5 +181,41 @@ hipError_t kf_load_enqueue_group(FrontBufs* const* F, int G, void* const* kf, co
   two.c[0] = two.c[1] = v[0];
   hipLaunchKernelGGL(k_kf_clear, dim3(min(1024, (max_slots + 1023) / 1024), 2, G), dim3(256), 0, st, (ViewExt<KfView>{dv, {0, 0, 0}}));
   hipLaunchKernelGGL((k_kf_copy<true, true>), dim3(kf_grid(maxn), 2, G), dim3(256), 0, st, (ViewExt<KfView>{dv, {0, 0, 0}}), two);
+  return hipGetLastError();
+}
+
+// ---- merge: the voxels of K keyframes, each under its pose, concatenated in member order -----------------------------------
+// One member of a merge.  The table of a whole merge (up to QTR_SUBMAP_MAX_KEYFRAMES records of 112 bytes: 7 kB) does not fit
+// the 4 kB of kernel arguments: it travels through pinned host memory into the slot's merge scratch (capi.hip).
+struct KfGatherMember {
+  const float4* vox;  // the member's stored voxels (its allocation + KF_HDR_BYTES)
+  int n;              // ... how many
+  int prefix;         // records of the members before it
+  double T[12];       // rows 0 - 2 of the member's pose
+};
+
+// grid (g, K): blockIdx.y = member, grid-stride in x over its voxels.  One 128-bit load, qtr_submap_point, one 128-bit store
+// per record; out holds prefix[K - 1] + n[K - 1] records (the host checked the sum against the buffer's size).
+__global__ __launch_bounds__(256) void k_kf_gather(ViewExt<KfGatherMember> x, float4* __restrict__ out) {
+  const KfGatherMember& M = x.ext[blockIdx.y];
+  const float4* __restrict__ in = M.vox;
+  const int n = M.n;
+  float4* __restrict__ dst = out + M.prefix;
+  double T[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) T[k] = M.T[k];
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const float4 p = in[i];
+    float4 q;
+    qtr_submap_point(T, p.x, p.y, p.z, &q.x, &q.y, &q.z);
+    q.w = p.w;
+    dst[i] = q;
+  }
+}
+
+// members: the table in DEVICE memory (K records); max_n: the largest member
+hipError_t kf_gather_enqueue(const KfGatherMember* members, int K, int max_n, float4* out, hipStream_t st) {
+  const int g = min(256, max(1, (max_n + 255) / 256));
+  hipLaunchKernelGGL(k_kf_gather, dim3(g, K, 1), dim3(256), 0, st, (ViewExt<KfGatherMember>{members, {0, 0, 0}}), out);
   return hipGetLastError();
 }

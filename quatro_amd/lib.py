@@ -122,6 +122,7 @@ class PlaceIndexInfo(C.Structure):
 KF_VOX, KF_NORMALS, KF_FPFH, KF_MEAN = 1, 2, 3, 4
 PLACE_DESC, PLACE_COLNORM2 = 1, 2
 PLACE_MAX_K = 64
+SUBMAP_MAX_KEYFRAMES = 64
 
 EXPORTS = [
     "qtr_create", "qtr_destroy", "qtr_last_error", "qtr_default_limits", "qtr_default_params", "qtr_demo_params",
@@ -130,7 +131,7 @@ EXPORTS = [
     "qtr_cote_estimate", "qtr_cote_estimate_ranges", "qtr_ip_default_params", "qtr_segment_cloud", "qtr_pw_default_params", "qtr_patchwork", "qtr_gnc_rotation3d", "qtr_exact_stats", "qtr_read_kitti_bin", "qtr_write_pcd_xyz", "qtr_read_pcd_xyz", "qtr_register_pair", "qtr_register_pair_corr", "qtr_feature_pair", "qtr_get_stage_times", "qtr_get_nn_dir_times", "qtr_set_stage_events", "qtr_set_nn_event_stride", "qtr_get_nn_totals", "qtr_debug_fetch", "qtr_debug_math", "qtr_submit_batch", "qtr_wait", "qtr_set_batch_preprocess", "qtr_comm_unique_id", "qtr_comm_init", "qtr_gather_results", "qtr_gather_results_v", "qtr_comm_destroy",
     "qtr_default_icp_params", "qtr_icp", "qtr_refine_pair", "qtr_submit_batch_refine", "qtr_gicp",
     "qtr_keyframe_create", "qtr_keyframe_get_info", "qtr_keyframe_fetch", "qtr_keyframe_destroy", "qtr_register_keyframes",
-    "qtr_submit_batch_keyframes",
+    "qtr_submit_batch_keyframes", "qtr_keyframe_merge",
     "qtr_default_place_params", "qtr_place_index_create", "qtr_place_index_destroy", "qtr_place_index_get_info",
     "qtr_place_describe", "qtr_place_index_add", "qtr_place_index_add_desc", "qtr_place_index_fetch", "qtr_place_query",
     "qtr_place_query_desc",
@@ -305,6 +306,8 @@ def load(path: str | None = None):
     lib.qtr_submit_batch_keyframes.argtypes = [C.c_void_p, C.POINTER(KfPairDesc), C.c_int, C.POINTER(FrontendParams),
                                                C.POINTER(Params), C.POINTER(IcpParams), C.POINTER(Result),
                                                C.POINTER(IcpResult)]
+    lib.qtr_keyframe_merge.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_int,
+                                       C.POINTER(FrontendParams), C.POINTER(C.c_void_p)]
     lib.qtr_default_place_params.restype = None
     lib.qtr_default_place_params.argtypes = [C.POINTER(PlaceParams)]
     lib.qtr_place_index_create.argtypes = [C.c_void_p, C.POINTER(PlaceParams), C.c_int, C.POINTER(C.c_void_p)]
@@ -876,6 +879,20 @@ class Handle:
         ptr, mem = _ptr(raw4)
         kf = C.c_void_p()
         self._check(self._lib.qtr_keyframe_create(self._h, slot, ptr, int(raw4.shape[0]), C.byref(fp), mem, C.byref(kf)))
+        return Keyframe(self, kf.value)
+
+    def merge_keyframes(self, kfs, poses=None, fp: FrontendParams | None = None, slot: int = 0) -> Keyframe:
+        """qtr_keyframe_merge: the keyframes' stored voxels, member k moved by poses[k] ([K, 4, 4] float64; None: identities),
+        concatenated on the device and run through the one-cloud front end with fp — the submap as an ordinary Keyframe."""
+        fp = fp or default_frontend_params()
+        K = len(kfs)
+        members = (C.c_void_p * max(K, 1))(*[k._kf.value for k in kfs])
+        p16 = None
+        if poses is not None:
+            p16 = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(K, 16))
+        kf = C.c_void_p()
+        self._check(self._lib.qtr_keyframe_merge(self._h, slot, members, None if p16 is None else p16.ctypes.data, K,
+                                                 C.byref(fp), C.byref(kf)))
         return Keyframe(self, kf.value)
 
     def register_keyframes(self, kf_src: Keyframe, kf_tgt: Keyframe, fp: FrontendParams | None = None,

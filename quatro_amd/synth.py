@@ -226,6 +226,51 @@ def kitti64_pair_16k(pair_id: int = 0):
     return kitti64_pair(pair_id, **KITTI16K)
 
 
+def kitti64_trajectory(seq_id: int = 0, n_scans: int = 11, step: float = 1.0, max_dyaw: float = 0.04, revisit_r: float | None = None,
+                       n_boxes: int = 100, n_poles: int = 60, n_clutter: int = 150, n_far: int = 300, sigma: float = 0.02,
+                       bump_a: float = 0.12, n_trees: int = 0, n_hedges: int = 0, far_r0: float = 50.0, leaf_p: float = 0.5,
+                       crown: float = 1.0, clear_r: float = 5.0):
+    """ONE scene scanned along a path: n_scans poses `step` metres apart on a smooth curve (the heading turns by at most
+    max_dyaw rad per step, the sensor looks along it; the middle pose sits at the world origin), then ONE revisit pose — at any
+    yaw, within revisit_r metres of the middle pose (None: 0.4 * step, so that the middle pose is the nearest one of the path:
+    its neighbours are `step` from it, hence at least 0.6 * step from the revisit).  Returns (scans, poses): n_scans + 1 clouds (float32 x, y, z, intensity)
+    and as many 4 x 4 float64 poses, scan frame -> world frame: a point p of scans[i] lies on the scene at poses[i] @ p, and
+    inv(poses[j]) @ poses[i] maps scan i into scan j's frame.  Deterministic in seq_id; **KITTI16K gives ~16 k voxels."""
+    rng = np.random.default_rng(SEED_BASE + 104729 * (seq_id + 1))
+    sc = _scene(rng, n_boxes, n_poles, n_clutter, n_far, far_r0, n_trees, n_hedges, leaf_p, crown)
+    lo, hi = sc[0], sc[1]
+    porous = sc[2] if len(sc) > 2 else None
+    bump_k = rng.normal(0.0, 2.0, size=(6, 3))
+    bump_ph = rng.uniform(0.0, 2 * np.pi, size=6)
+    heading = rng.uniform(-np.pi, np.pi) + np.concatenate([[0.0], np.cumsum(rng.uniform(-max_dyaw, max_dyaw, n_scans - 1))])
+    xy = np.zeros((n_scans, 2))
+    for i in range(1, n_scans):  # each step leaves along the heading of the pose it starts from
+        xy[i] = xy[i - 1] + step * np.array([np.cos(heading[i - 1]), np.sin(heading[i - 1])])
+    mid = n_scans // 2
+    xy -= xy[mid]
+    r_rev = (0.4 * step if revisit_r is None else revisit_r) * np.sqrt(rng.random())  # (area-uniform in the disc)
+    a_rev = rng.uniform(-np.pi, np.pi)
+    xy = np.concatenate([xy, [[r_rev * np.cos(a_rev), r_rev * np.sin(a_rev)]]])  # (xy[mid] is the origin)
+    yaws = np.concatenate([heading, [rng.uniform(-np.pi, np.pi)]])
+    if clear_r > 0.0:  # a disc around EVERY sensor pose stays free of objects (kitti64_pair's rule)
+        keep = np.ones(lo.shape[0], dtype=bool)
+        for c in xy:
+            dx = np.maximum(np.maximum(lo[:, 0] - c[0], c[0] - hi[:, 0]), 0.0)
+            dy = np.maximum(np.maximum(lo[:, 1] - c[1], c[1] - hi[:, 1]), 0.0)
+            keep &= np.hypot(dx, dy) > clear_r
+        lo, hi = lo[keep], hi[keep]
+        porous = porous[keep] if porous is not None else None
+    scans, poses = [], []
+    for c, yaw in zip(xy, yaws):
+        origin = np.array([c[0], c[1], 0.0])
+        scans.append(_scan(origin, float(yaw), lo, hi, rng, sigma, bump_k, bump_ph, bump_a, porous=porous))
+        T = np.eye(4)
+        T[:3, :3] = yaw_matrix(float(yaw))
+        T[:3, 3] = origin
+        poses.append(T)
+    return scans, np.stack(poses)
+
+
 def kitti64_raw_scan(scan_id: int = 0, **kw):
     """One raw KITTI-64-shaped sweep WITH its ground returns: (xyzi float32 in sweep order, is_ground bool)."""
     rng = np.random.default_rng(SEED_BASE + 7919 * (scan_id + 1))
