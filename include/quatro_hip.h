@@ -639,6 +639,57 @@ QTR_API int qtr_place_query(qtr_handle* h, int slot, const qtr_place_index* inde
 QTR_API int qtr_place_query_desc(qtr_handle* h, int slot, const qtr_place_index* index, const float* desc, int mem, int id_lo,
                                  int id_hi, int k, qtr_place_match* out, int* n_out);
 
+/* Evaluation of a registration: what a caller settles before (T) becomes an edge (T, Omega) of a pose graph — Open3D's
+ * evaluate_registration and get_information_matrix_from_point_clouds, plus the Hessian of the point-to-plane cost at T
+ * (the point-to-point information matrix has full rank for any three non-collinear points: it cannot show a corridor or a
+ * single plane; the point-to-plane Hessian can).  The arithmetic is include/qtr_eval_math.h; one kernel launch per call.
+ *   considered:     the finite source points (n_source of them)
+ *   correspondence: the ICP's — the NEAREST finite target point within max_correspondence_distance of R p + t (binary64
+ *                   distances, ties to the lowest target index).  A non-finite target normal does not drop it: it only
+ *                   keeps it out of the plane sums (n_plane, plane_rmse, hessian_plane)
+ *   overlap         n_corr / n_source (Open3D's fitness); inlier_rmse = sqrt(sum_d2 / n_corr); sum_d2 and n_corr are the
+ *                   numbers one point-to-point ICP iteration from T forms
+ *   information     row-major 6x6, rotation first: sum G^T G, G = [ -[t]x | I ] on the target point of every correspondence
+ *   hessian_plane   row-major 6x6: sum J^T J, J = [ q x n | n ]; all zero with n_plane = 0 without target normals
+ * Both matrices are exactly symmetric.  valid = n_corr > 0.  The evaluation has an arena of its own per slot (allocated on
+ * the first call, grown on demand): the ICP arena, its QTR_DBG_ICP_* items and a registration's state are left alone.
+ * QTR_ERR_BAD_ARG, before anything is enqueued: a NULL keyframe or one of another handle, B outside 1 .. QTR_EVAL_MAX_PAIRS,
+ * a NULL T or one with a non-finite entry in rows 0 - 2, a distance that is not finite and positive.  Sizes above
+ * qtr_limits.max_voxels per cloud: QTR_ERR_CAPACITY.  Empty clouds or no finite target point: QTR_OK, valid = 0. */
+#define QTR_EVAL_MAX_PAIRS 64
+typedef struct qtr_eval_params {
+  double max_correspondence_distance; /* 1.0 m, like the ICP's */
+  int reserved[2];
+} qtr_eval_params;
+typedef struct qtr_eval_result {
+  int status, valid, n_source, n_corr, n_plane, reserved;
+  double T[16]; /* the transform evaluated */
+  double overlap, sum_d2, inlier_rmse, plane_rmse, information[36], hessian_plane[36];
+} qtr_eval_result;
+typedef struct qtr_eval_kf_pair {
+  const qtr_keyframe* source;
+  const qtr_keyframe* target;
+  double T[16];
+} qtr_eval_kf_pair;
+QTR_API void qtr_default_eval_params(qtr_eval_params* p);
+/* src4 (n_s) / tgt4 (n_t): 16-byte records; tgt_normals4: n_t records nx,ny,nz,* or NULL (no plane sums).  T: row-major
+ * 4x4, maps source into target.  mem: where the clouds live. */
+QTR_API int qtr_evaluate(qtr_handle* h, int slot, const float* src4, int n_s, const float* tgt4, int n_t,
+                         const float* tgt_normals4, const double T[16], const qtr_eval_params* prm, qtr_eval_result* res, int mem);
+/* The slot's last registration, on its voxelised clouds and the target's normals where they lie (qtr_refine_pair's rules:
+ * QTR_ERR_BAD_ARG when the slot's last call was not a registration, and after a batch job).  T NULL = that call's T.  Leaves
+ * the registration's state untouched: a qtr_refine_pair may follow it, and it may follow a qtr_refine_pair. */
+QTR_API int qtr_evaluate_pair(qtr_handle* h, int slot, const double T[16], const qtr_eval_params* prm, qtr_eval_result* res);
+/* Two keyframes, read where they lie (the voxels of both, the normals of the target); no registration needs to precede it
+ * and the slot's clouds are not written. */
+QTR_API int qtr_evaluate_keyframes(qtr_handle* h, int slot, const qtr_keyframe* source, const qtr_keyframe* target,
+                                   const double T[16], const qtr_eval_params* prm, qtr_eval_result* res);
+/* B pairs (1 .. QTR_EVAL_MAX_PAIRS) in one grouped launch chain on `slot`, two host waits in all; results[b] is
+ * bit-identical to qtr_evaluate_keyframes on pair b.  A keyframe may appear in any number of pairs.  An argument error
+ * refuses the whole batch. */
+QTR_API int qtr_evaluate_keyframes_batch(qtr_handle* h, int slot, const qtr_eval_kf_pair* pairs, int B,
+                                         const qtr_eval_params* prm, qtr_eval_result* results);
+
 /* Inspection of intermediates of the LAST call on a slot (tests / parity debugging).  Copies up to
  * `bytes` bytes to host memory `dst`; returns the number of bytes the item holds, or <0 on error. */
 #define QTR_DBG_GRAPH_BITMAP 1   /* uint64[L][ceil(L/64)] adjacency, original labels */
@@ -664,6 +715,8 @@ QTR_API int qtr_place_query_desc(qtr_handle* h, int slot, const qtr_place_index*
 #define QTR_DBG_ICP_CORR 15      /* int32[n_s] target index of every source point in the last ICP iteration (-1: none) */
 #define QTR_DBG_ICP_TRACE 16     /* double[iterations][18] per update of the last ICP call: T after it (16), MSE, count */
 #define QTR_DBG_ICP_TIMES 17     /* float[2] last ICP call: grid build, iterations (device milliseconds) */
+#define QTR_DBG_EVAL_CORR 18     /* int32[n_s] target index of every source point of the last evaluation (a batch: its
+                                    first pair); -1: none */
 QTR_API long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t bytes);
 
 /* Evaluates the shared deterministic math (include/qtr_math.h) ON THE DEVICE, for the test that pins

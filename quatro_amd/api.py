@@ -544,6 +544,18 @@ def register_one_to_many(handle, query_kf, candidate_kfs, fp=None, params=None, 
     return out[0], out[1], best_candidate(out[0])
 
 
+def evaluate_one_to_many(handle, query_kf, target_kfs, transforms, eval_params=None, slot=0):
+    """Evaluates the query keyframe (the source) against K target keyframes under K transforms (4 x 4, query -> target
+    frame) as ONE grouped job (Handle.evaluate_keyframes_batch; more than EVAL_MAX_PAIRS targets: several).  Returns one
+    record dict per target: overlap, inlier_rmse, information, hessian_plane, ..."""
+    assert len(target_kfs) == len(transforms)
+    pairs = [(query_kf, t, T) for t, T in zip(target_kfs, transforms)]
+    out = []
+    for a in range(0, len(pairs), _ql.EVAL_MAX_PAIRS):
+        out += handle.evaluate_keyframes_batch(pairs[a:a + _ql.EVAL_MAX_PAIRS], eval_params, slot)
+    return out
+
+
 def make_submap(handle, keyframes, poses, center, half_width, fp=None, id_lo=0, id_hi=None, slot=0):
     """The submap around keyframe `center`: the keyframes center - half_width .. center + half_width, clipped to
     [id_lo, id_hi) (id_hi = None: len(keyframes)), fused into one Keyframe by Handle.merge_keyframes.  Member i travels
@@ -560,7 +572,7 @@ def make_submap(handle, keyframes, poses, center, half_width, fp=None, id_lo=0, 
 
 
 def close_loop(handle, index, keyframes, query_kf, k, id_lo=0, id_hi=None, fp=None, params=None, icp=None, poses=None,
-               submap_half_width=0):
+               submap_half_width=0, evaluate=None, min_overlap=None):
     """Loop closing from the first link: index.query(query_kf) picks the k entries of [id_lo, id_hi) whose Scan Context
     descriptors are most similar (quatro_amd.lib.PlaceIndex), keyframes[id] are their keyframes, and register_one_to_many
     registers the query against exactly those, in the order the search returned them.  Returns a dict: "matches" (the
@@ -571,13 +583,22 @@ def close_loop(handle, index, keyframes, query_kf, k, id_lo=0, id_hi=None, fp=No
     submap_half_width = n > 0 (poses required: one 4 x 4 per keyframe, its frame -> the map frame): every match `id` is
     registered as make_submap around id — the 2 n + 1 keyframes id - n .. id + n under their poses, clipped to the searched
     id range [id_lo, id_hi) — id_hi = None: the index's size — so the query's own neighbourhood is never fused.  The submaps are temporary: destroyed when the job is done.
-    The transforms still map the query into keyframe id's frame."""
+    The transforms still map the query into keyframe id's frame.
+
+    evaluate = an EvalParams (or True: the defaults): every valid record is evaluated (evaluate_one_to_many) at its refined T
+    with icp, else at its registration T — against the submap where there is one — and the result gets "evaluations": one
+    record per candidate, None where the registration was not valid.  min_overlap = x (implies evaluate): "best" / "best_id"
+    are chosen among the records whose overlap reaches x, -1 when none does."""
+    if min_overlap is not None and evaluate is None:
+        evaluate = True
     if submap_half_width > 0 and poses is None:
         raise ValueError("close_loop: submap_half_width > 0 needs the keyframes' poses")
     matches = index.query(query_kf, k, id_lo, id_hi)
     out = {"matches": matches, "records": [], "best": -1, "best_id": -1}
     if icp is not None:
         out["refined"] = []
+    if evaluate is not None:
+        out["evaluations"] = []
     if not matches:
         return out
     submaps = []
@@ -590,12 +611,23 @@ def close_loop(handle, index, keyframes, query_kf, k, id_lo=0, id_hi=None, fp=No
         else:
             targets = [keyframes[m["id"]] for m in matches]
         got = register_one_to_many(handle, query_kf, targets, fp, params, icp)
+        if evaluate is not None:
+            at = [i for i, r in enumerate(got[0]) if r.get("valid")]
+            Ts = [got[1][i]["T"] if icp is not None and got[1][i].get("status") == 0 else got[0][i]["T"] for i in at]
+            ev = evaluate_one_to_many(handle, query_kf, [targets[i] for i in at], Ts, None if evaluate is True else evaluate)
+            out["evaluations"] = [None] * len(targets)
+            for i, e in zip(at, ev):
+                out["evaluations"][i] = e
     finally:
         for sm in submaps:
             sm.close()
     out["records"], out["best"] = got[0], got[-1]
     if icp is not None:
         out["refined"] = got[1]
+    if min_overlap is not None:
+        ev = out["evaluations"]
+        out["best"] = best_candidate([r if ev[i] is not None and ev[i]["overlap"] >= min_overlap else {}
+                                      for i, r in enumerate(out["records"])])
     if out["best"] >= 0:
         out["best_id"] = matches[out["best"]]["id"]
     return out

@@ -21,7 +21,7 @@ TEST_LIB = os.path.join(HERE, "libquatro_hip_testengines.so")
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))) + [
     os.path.join("..", "..", "include", "qtr_math.h"), os.path.join("..", "..", "include", "qtr_icp_math.h"),
     os.path.join("..", "..", "include", "qtr_place_math.h"),
-    os.path.join("..", "..", "include", "qtr_submap_math.h"),
+    os.path.join("..", "..", "include", "qtr_submap_math.h"), os.path.join("..", "..", "include", "qtr_eval_math.h"),
     os.path.join("..", "..", "include", "quatro_hip.h")]
 
 

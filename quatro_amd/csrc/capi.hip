@@ -57,6 +57,7 @@ struct Slot {
   int last_n = 0;  // points of the last qtr_fpfh
   int last_ns = 0, last_nt = 0;
   IcpBufs icp;                   // ICP arena (allocated on first use: icp.hip)
+  EvalBufs eval;                 // evaluation arena (allocated on first use, grown on demand: eval.hip)
   int reg_ready = 0;             // 1: the last call on this slot was a registration (qtr_refine_pair may use its clouds)
   double reg_T[16] = {};         // ... and its transform
   int icp_ns = 0, icp_iters = 0; // source points and updates of the last ICP call (debug ids)
@@ -447,6 +448,7 @@ void qtr_destroy(qtr_handle* h) {
     if (s.pw_arena) (void)hipFree(s.pw_arena);
     if (s.ex_arena) (void)hipFree(s.ex_arena);
     icp_free(s.icp);
+    eval_free(s.eval);
     if (s.place.arena) (void)hipFree(s.place.arena);
     if (s.place.pin) (void)hipHostFree(s.place.pin);
     if (s.merge_pin) (void)hipHostFree(s.merge_pin);
@@ -3816,6 +3818,285 @@ int qtr_refine_pair(qtr_handle* h, int slot, const double guess[16], const qtr_i
   return res->status = rc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// ---- registration evaluation (eval.hip) -------------------------------------------------------------------------------
+void qtr_default_eval_params(qtr_eval_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->max_correspondence_distance = 1.0;
+}
+
+static int check_eval_params(qtr_handle* h, const qtr_eval_params* p) {
+  if (!p || !icp_finite(p->max_correspondence_distance) || !(p->max_correspondence_distance > 0)) {
+    snprintf(h->err, sizeof(h->err), "evaluation: max_correspondence_distance must be finite and positive");
+    return QTR_ERR_BAD_ARG;
+  }
+  return QTR_OK;
+}
+static int check_eval_T(qtr_handle* h, const double* T) {
+  if (!T || !qtr_submap_pose_finite(T)) {
+    snprintf(h->err, sizeof(h->err), "evaluation: T is NULL or has a non-finite entry in rows 0 - 2");
+    return QTR_ERR_BAD_ARG;
+  }
+  return QTR_OK;
+}
+
+static_assert(QTR_EVAL_MAX_PAIRS == QTR_EVAL_MAX_BATCH, "the arena's fixed part holds a whole batch");
+struct EvalPair {
+  const float4 *src, *tgt, *nrm;  // device pointers (nrm may be null)
+  int ns, nt;
+  const double* T;
+};
+
+static void eval_result_from(qtr_eval_result* res, const QtrEvalRecord& r) {
+  res->valid = r.valid;
+  res->n_source = r.n_source;
+  res->n_corr = r.n_corr;
+  res->n_plane = r.n_plane;
+  res->overlap = r.overlap;
+  res->sum_d2 = r.sum_d2;
+  res->inlier_rmse = r.inlier_rmse;
+  res->plane_rmse = r.plane_rmse;
+  memcpy(res->information, r.information, sizeof(r.information));
+  memcpy(res->hessian_plane, r.hessian_plane, sizeof(r.hessian_plane));
+}
+
+// B evaluations on device-resident clouds, validated by the caller.  Two host waits whatever B is: the target boxes (they
+// size the cell tables) and the records.  grouped = false (B == 1): the single-pair kernels with the view by value.
+static int eval_device(qtr_handle* h, Slot& s, const EvalPair* P, int B, double max_d, bool grouped, qtr_eval_result* out) {
+  QtrEvalRecord empty;
+  {
+    double S0[QTR_EVAL_NT] = {};
+    qtr_eval_finish(S0, &empty);  // (what a pair without a considered source point reports)
+  }
+  size_t var = 0;
+  int max_nt = 0, max_nchunk = 0;
+  for (int b = 0; b < B; ++b) {
+    memset(&out[b], 0, sizeof(out[b]));
+    out[b].status = QTR_OK;
+    for (int k = 0; k < 16; ++k) out[b].T[k] = P[b].T[k];
+    eval_result_from(&out[b], empty);
+    const int nchunk = qtr_div_up(P[b].ns, QTR_ICP_CHUNK);
+    var += eval_up((size_t)nchunk * QTR_EVAL_NT * 8) + 2 * eval_up((size_t)P[b].nt * 16) + eval_up((size_t)P[b].nt * 8) +
+           eval_up((size_t)P[b].ns * 4);
+    max_nt = std::max(max_nt, P[b].nt);
+    max_nchunk = std::max(max_nchunk, nchunk);
+  }
+  if (max_nchunk == 0) return QTR_OK;
+  EvalBufs& E = s.eval;
+  QTR_HIP_TRY(h, eval_reserve(E, var));
+  char* p = E.d_var;
+  auto take = [&](size_t n) {
+    char* r = p;
+    p += eval_up(n);
+    return r;
+  };
+  for (int b = 0; b < B; ++b) {
+    IcpView& v = E.h_views[b];
+    memset((void*)&v, 0, sizeof(v));
+    v.src = P[b].src;
+    v.tgt = P[b].tgt;
+    v.nrm = P[b].nrm;
+    v.ns = P[b].ns;
+    v.nt = P[b].nt;
+    v.partials = (double*)take((size_t)qtr_div_up(v.ns, QTR_ICP_CHUNK) * QTR_EVAL_NT * 8);
+    v.spts = (float4*)take((size_t)v.nt * 16);
+    v.snrm = (float4*)take((size_t)v.nt * 16);
+    v.place = (int*)take((size_t)v.nt * 8);
+    v.corr = (int*)take((size_t)v.ns * 4);
+    v.bbox = E.d_boxes + 8 * b;
+    v.st = E.d_state + b;
+    v.ticket = E.d_tickets + 16 * b;
+    v.trace = (double*)(E.d_rec + b);
+    v.cfg.max_d2 = max_d * max_d;
+    qtr_icp_init(&E.h_init[b], P[b].T);
+    for (int a = 0; a < 3; ++a) {
+      E.h_boxes[8 * b + a] = 0x7fffffff;
+      E.h_boxes[8 * b + 3 + a] = (int)0x80000000;
+    }
+  }
+  E.last_corr = E.h_views[0].corr;
+  E.last_ns = 0;
+  const hipStream_t st = s.stream;
+  const size_t view_block = (sizeof(IcpView) + sizeof(QtrIcpState)) * QTR_EVAL_MAX_BATCH;
+  const ViewExt<IcpView> x{E.d_views, {0, 0, 0}};
+  // first wait: the boxes of the finite target points
+  if (!grouped) {
+    QTR_HIP_TRY(h, hipMemcpyAsync(E.d_boxes, E.h_boxes, 24, hipMemcpyHostToDevice, st));
+    if (P[0].nt > 0) hipLaunchKernelGGL(k_icp_bbox, dim3(qtr_div_up(P[0].nt, 256)), dim3(256), 0, st, E.h_views[0]);
+  } else {
+    QTR_HIP_TRY(h, hipMemcpyAsync(E.d_views, E.h_views, view_block, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_icp_box_init_group, dim3(1, B), dim3(64), 0, st, x);
+    if (max_nt > 0) hipLaunchKernelGGL(k_eval_bbox_group, dim3(qtr_div_up(max_nt, 256), B), dim3(256), 0, st, x);
+  }
+  QTR_HIP_TRY(h, hipGetLastError());
+  QTR_HIP_TRY(h, hipMemcpyAsync(E.h_boxes, E.d_boxes, (size_t)B * 32, hipMemcpyDeviceToHost, st));
+  QTR_HIP_TRY(h, hipStreamSynchronize(st));
+  size_t cell_ints = 0;
+  int max_ncell = 0;
+  for (int b = 0; b < B; ++b) {
+    IcpView& v = E.h_views[b];
+    if (!icp_grid_of(v, E.h_boxes + 8 * b, max_d, QTR_EVAL_CELLS)) {  // no finite target point: nothing is searched
+      v.ncell = 0;
+      v.dims[0] = v.dims[1] = v.dims[2] = 0;
+      v.mn[0] = v.mn[1] = v.mn[2] = 0.0;
+      v.cell = 1.0;
+    }
+    cell_ints += 2 * ((size_t)v.ncell + 1);
+    max_ncell = std::max(max_ncell, v.ncell);
+  }
+  QTR_HIP_TRY(h, eval_reserve_cells(E, cell_ints));
+  int* c = E.cells;
+  for (int b = 0; b < B; ++b) {
+    IcpView& v = E.h_views[b];
+    v.cell_cnt = c;
+    v.cell_start = c + v.ncell + 1;
+    c += 2 * ((size_t)v.ncell + 1);
+  }
+  // second wait: the records
+  if (!grouped) {
+    const IcpView& v = E.h_views[0];
+    QTR_HIP_TRY(h, hipMemsetAsync(v.cell_cnt, 0, (size_t)(v.ncell + 1) * 4, st));
+    if (v.nt > 0) {
+      hipLaunchKernelGGL(k_icp_count, dim3(qtr_div_up(v.nt, 256)), dim3(256), 0, st, v);
+      QTR_HIP_TRY(h, exclusive_scan_i32(v.cell_cnt, v.cell_start, v.ncell, st));
+      hipLaunchKernelGGL(k_icp_place, dim3(qtr_div_up(v.nt, 256)), dim3(256), 0, st, v);
+    }
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, v, E.h_init[0]);
+    hipLaunchKernelGGL(k_eval, dim3(max_nchunk), dim3(256), 0, st, v);
+  } else {
+    QTR_HIP_TRY(h, hipMemcpyAsync(E.d_views, E.h_views, view_block, hipMemcpyHostToDevice, st));
+    QTR_HIP_TRY(h, icp_grid_enqueue_group(E.d_views, E.d_init, B, std::max(max_nt, 1), max_ncell, st));
+    hipLaunchKernelGGL(k_eval_group, dim3(max_nchunk, B), dim3(256), 0, st, x);
+  }
+  QTR_HIP_TRY(h, hipGetLastError());
+  QTR_HIP_TRY(h, hipMemcpyAsync(E.h_rec, E.d_rec, (size_t)B * sizeof(QtrEvalRecord), hipMemcpyDeviceToHost, st));
+  QTR_HIP_TRY(h, hipStreamSynchronize(st));
+  for (int b = 0; b < B; ++b)
+    if (P[b].ns > 0) eval_result_from(&out[b], E.h_rec[b]);
+  E.last_ns = P[0].ns;
+  return QTR_OK;
+}
+
+int qtr_evaluate(qtr_handle* h, int slot, const float* src4, int n_s, const float* tgt4, int n_t, const float* tgt_normals4,
+                 const double T[16], const qtr_eval_params* prm, qtr_eval_result* res, int mem) {
+  Slot* sp = get_slot(h, slot);
+  if (!sp || !res) return QTR_ERR_BAD_ARG;
+  memset(res, 0, sizeof(*res));
+  Slot& s = *sp;
+  int rc = check_eval_params(h, prm);
+  if (rc == QTR_OK) rc = check_eval_T(h, T);
+  if (rc != QTR_OK) return res->status = rc;
+  if (n_s < 0 || n_t < 0 || (n_s > 0 && !src4) || (n_t > 0 && !tgt4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) {
+    snprintf(h->err, sizeof(h->err), "bad evaluation arguments");
+    return res->status = QTR_ERR_BAD_ARG;
+  }
+  if (n_s > h->lim.max_voxels || n_t > h->lim.max_voxels) {
+    snprintf(h->err, sizeof(h->err), "evaluation: cloud exceeds max_voxels=%d", h->lim.max_voxels);
+    return res->status = QTR_ERR_CAPACITY;
+  }
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  EvalPair P{(const float4*)src4, (const float4*)tgt4, (const float4*)tgt_normals4, n_s, n_t, T};
+  if (mem == QTR_MEM_HOST) {  // (staging: the raw-scan buffers, max_points >= max_voxels points each)
+    if (n_s > 0) QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, src4, (size_t)n_s * 16, hipMemcpyHostToDevice, s.stream));
+    if (n_t > 0) QTR_HIP_TRY(h, hipMemcpyAsync(s.in_tgt, tgt4, (size_t)n_t * 16, hipMemcpyHostToDevice, s.stream));
+    P.src = s.in_src;
+    P.tgt = s.in_tgt;
+    if (tgt_normals4 && n_t > 0) {
+      QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[1].normals, tgt_normals4, (size_t)n_t * 16, hipMemcpyHostToDevice, s.stream));
+      P.nrm = s.fb.cloud[1].normals;
+    }
+  }
+  rc = eval_device(h, s, &P, 1, prm->max_correspondence_distance, false, res);
+  return res->status = rc;
+}
+
+int qtr_evaluate_pair(qtr_handle* h, int slot, const double T[16], const qtr_eval_params* prm, qtr_eval_result* res) {
+  Slot* sp = peek_slot(h, slot);  // (an evaluation leaves the registration's clouds and the ICP arena as they are)
+  if (!sp || !res) return QTR_ERR_BAD_ARG;
+  memset(res, 0, sizeof(*res));
+  Slot& s = *sp;
+  int rc = check_eval_params(h, prm);
+  if (rc != QTR_OK) return res->status = rc;
+  if (!s.reg_ready) {
+    snprintf(h->err, sizeof(h->err), "qtr_evaluate_pair: the slot's last call was not a registration");
+    return res->status = QTR_ERR_BAD_ARG;
+  }
+  if (T && (rc = check_eval_T(h, T)) != QTR_OK) return res->status = rc;
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  const EvalPair P{s.fb.cloud[0].vox, s.fb.cloud[1].vox, s.fb.cloud[1].normals, s.last_ns, s.last_nt, T ? T : s.reg_T};
+  rc = eval_device(h, s, &P, 1, prm->max_correspondence_distance, false, res);
+  return res->status = rc;
+}
+
+// the pairs of a keyframe evaluation against the handle, before anything is enqueued
+static int eval_kf_pairs(qtr_handle* h, const qtr_eval_kf_pair* pairs, int B, EvalPair* P) {
+  for (int b = 0; b < B; ++b) {
+    const qtr_keyframe *a = pairs[b].source, *t = pairs[b].target;
+    if (!a || !t) {
+      snprintf(h->err, sizeof(h->err), "evaluation: keyframe of pair %d is NULL", b);
+      return QTR_ERR_BAD_ARG;
+    }
+    if (a->owner != h || t->owner != h) {
+      snprintf(h->err, sizeof(h->err), "keyframe belongs to another handle");
+      return QTR_ERR_BAD_ARG;
+    }
+    QTR_TRY(check_eval_T(h, pairs[b].T));
+    if (a->info.n_voxels > h->lim.max_voxels || t->info.n_voxels > h->lim.max_voxels) {
+      snprintf(h->err, sizeof(h->err), "evaluation: keyframe of pair %d exceeds max_voxels=%d", b, h->lim.max_voxels);
+      return QTR_ERR_CAPACITY;
+    }
+    const KfLayout lt = kf_layout(t->info.n_voxels);
+    P[b].src = (const float4*)((const char*)a->dev + KF_HDR_BYTES);
+    P[b].tgt = (const float4*)((const char*)t->dev + lt.vox);
+    P[b].nrm = (const float4*)((const char*)t->dev + lt.normals);
+    P[b].ns = a->info.n_voxels;
+    P[b].nt = t->info.n_voxels;
+    P[b].T = pairs[b].T;
+  }
+  return QTR_OK;
+}
+
+int qtr_evaluate_keyframes(qtr_handle* h, int slot, const qtr_keyframe* source, const qtr_keyframe* target, const double T[16],
+                           const qtr_eval_params* prm, qtr_eval_result* res) {
+  Slot* sp = peek_slot(h, slot);  // (the keyframes are read where they lie: the slot's clouds stay what they were)
+  if (!sp || !res) return QTR_ERR_BAD_ARG;
+  memset(res, 0, sizeof(*res));
+  int rc = check_eval_params(h, prm);
+  if (rc == QTR_OK) rc = check_eval_T(h, T);
+  if (rc != QTR_OK) return res->status = rc;
+  qtr_eval_kf_pair pr;
+  pr.source = source;
+  pr.target = target;
+  memcpy(pr.T, T, sizeof(pr.T));
+  EvalPair P;
+  if ((rc = eval_kf_pairs(h, &pr, 1, &P)) != QTR_OK) return res->status = rc;
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  rc = eval_device(h, *sp, &P, 1, prm->max_correspondence_distance, false, res);
+  return res->status = rc;
+}
+
+int qtr_evaluate_keyframes_batch(qtr_handle* h, int slot, const qtr_eval_kf_pair* pairs, int B, const qtr_eval_params* prm,
+                                 qtr_eval_result* results) {
+  Slot* sp = peek_slot(h, slot);
+  if (!sp) return QTR_ERR_BAD_ARG;
+  if (B < 1 || B > QTR_EVAL_MAX_PAIRS || !pairs || !results) {
+    snprintf(h->err, sizeof(h->err), "evaluation batch: %d pairs (1 .. %d), pairs and results not NULL", B, QTR_EVAL_MAX_PAIRS);
+    return QTR_ERR_BAD_ARG;
+  }
+  memset(results, 0, sizeof(*results) * (size_t)B);
+  int rc = check_eval_params(h, prm);
+  EvalPair P[QTR_EVAL_MAX_PAIRS];
+  if (rc == QTR_OK) rc = eval_kf_pairs(h, pairs, B, P);
+  if (rc == QTR_OK) {
+    QTR_HIP_TRY(h, hipSetDevice(h->device));
+    rc = eval_device(h, *sp, P, B, prm->max_correspondence_distance, true, results);
+  }
+  if (rc != QTR_OK)
+    for (int b = 0; b < B; ++b) results[b].status = rc;
+  return rc;
+}
+
 long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t bytes) {
   Slot* sp = peek_slot(h, slot);
   if (!sp) return -1;
@@ -3856,6 +4137,7 @@ long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t b
     case QTR_DBG_ICP_CORR: src = s.icp.v.corr; have = s.icp.v.corr ? (size_t)s.icp_ns * 4 : 0; break;
     case QTR_DBG_ICP_TRACE: src = s.icp.v.trace; have = s.icp.v.trace ? (size_t)s.icp_iters * 18 * 8 : 0; break;
     case QTR_DBG_ICP_TIMES: src = s.icp_ms; have = sizeof(s.icp_ms); break;
+    case QTR_DBG_EVAL_CORR: src = s.eval.last_corr; have = s.eval.last_corr ? (size_t)s.eval.last_ns * 4 : 0; break;
     default: return -1;
   }
   const size_t n = have < bytes ? have : bytes;

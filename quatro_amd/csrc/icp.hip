@@ -42,7 +42,7 @@ struct IcpView {
   double* partials;       // [nchunk][QTR_ICP_NT]
   unsigned* ticket;       // workgroups done in the current launch (reset by the last one)
   int* corr;              // [ns] target index of every source point in the last evaluated iteration (-1: none)
-  double* trace;          // [max_iterations][18]
+  double* trace;          // [max_iterations][18] (an evaluation, eval.hip: its QtrEvalRecord)
   int* mail;              // grouped launches: device view of the slot's host mailbox (frontend.h MAIL_ICP*), else null
   const float4* src_nrm;  // [ns] source normals, source frame (plane-to-plane) or null
 };
@@ -121,6 +121,44 @@ __global__ __launch_bounds__(256) void k_icp_init(IcpView v, QtrIcpState init) {
 
 __device__ __forceinline__ double icp_shfl_down(double x, int off) { return __shfl_down(x, off, 64); }
 
+// The nearest finite target point within reach of q on the view's cell grid: best = its index in the target cloud (-1:
+// none), bat = its place in spts / snrm, bd = its binary64 d^2; ties go to the lowest target index.  Shared by the ICP
+// iteration and the evaluation (eval.hip); the caller has checked v.ncell > 0 and set best = bat = -1.
+__device__ __forceinline__ void icp_nearest(const IcpView& v, const double* q, int& best, int& bat, double& bd) {
+  int lo[3], hi[3];
+  bool any = true;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double f = icp_cellf(q[a], v.mn[a], v.cell);  // (NaN / huge: compared as double before any int cast)
+    if (!(f >= -1.0 && f <= (double)v.dims[a])) {
+      any = false;
+      lo[a] = 0;
+      hi[a] = -1;
+    } else {
+      const int c = (int)f;
+      lo[a] = c - 1 < 0 ? 0 : c - 1;
+      hi[a] = c + 1 > v.dims[a] - 1 ? v.dims[a] - 1 : c + 1;
+    }
+  }
+  if (any) {
+    for (int cz = lo[2]; cz <= hi[2]; ++cz)
+      for (int cy = lo[1]; cy <= hi[1]; ++cy) {
+        const int row = v.dims[0] * (cy + v.dims[1] * cz);
+        const int s = v.cell_start[row + lo[0]], e = v.cell_start[row + hi[0] + 1];  // (cells of a row are contiguous)
+        for (int j = s; j < e; ++j) {
+          const float4 t = v.spts[j];
+          const double d2 = qtr_icp_d2(q, t.x, t.y, t.z);
+          const int idx = __float_as_int(t.w);
+          if (d2 <= v.cfg.max_d2 && (best < 0 || d2 < bd || (d2 == bd && idx < best))) {
+            best = idx;
+            bat = j;
+            bd = d2;
+          }
+        }
+      }
+  }
+}
+
 // One workgroup (chunk `blk` of `nblk`) of one iteration of one pair.  GICP: the plane-to-plane body (cfg.method == 2);
 // the other two methods share the instantiation they always had.
 template <bool GICP>
@@ -149,38 +187,7 @@ __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) 
     }
     if (use) {
       qtr_icp_transform(T, p.x, p.y, p.z, q);
-      int lo[3], hi[3];
-      bool any = true;
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const double f = icp_cellf(q[a], v.mn[a], v.cell);  // (NaN / huge: compared as double before any int cast)
-        if (!(f >= -1.0 && f <= (double)v.dims[a])) {
-          any = false;
-          lo[a] = 0;
-          hi[a] = -1;
-        } else {
-          const int c = (int)f;
-          lo[a] = c - 1 < 0 ? 0 : c - 1;
-          hi[a] = c + 1 > v.dims[a] - 1 ? v.dims[a] - 1 : c + 1;
-        }
-      }
-      if (any) {
-        for (int cz = lo[2]; cz <= hi[2]; ++cz)
-          for (int cy = lo[1]; cy <= hi[1]; ++cy) {
-            const int row = v.dims[0] * (cy + v.dims[1] * cz);
-            const int s = v.cell_start[row + lo[0]], e = v.cell_start[row + hi[0] + 1];  // (cells of a row are contiguous)
-            for (int j = s; j < e; ++j) {
-              const float4 t = v.spts[j];
-              const double d2 = qtr_icp_d2(q, t.x, t.y, t.z);
-              const int idx = __float_as_int(t.w);
-              if (d2 <= v.cfg.max_d2 && (best < 0 || d2 < bd || (d2 == bd && idx < best))) {
-                best = idx;
-                bat = j;
-                bd = d2;
-              }
-            }
-          }
-      }
+      icp_nearest(v, q, best, bat, bd);
     }
     if (GICP) {
       if (best >= 0) {

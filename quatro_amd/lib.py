@@ -97,6 +97,21 @@ class IcpResult(C.Structure):
                 ("rmse", C.c_double)]
 
 
+class EvalParams(C.Structure):
+    _fields_ = [("max_correspondence_distance", C.c_double), ("reserved", C.c_int * 2)]
+
+
+class EvalResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("valid", C.c_int), ("n_source", C.c_int), ("n_corr", C.c_int), ("n_plane", C.c_int),
+                ("reserved", C.c_int), ("T", C.c_double * 16), ("overlap", C.c_double), ("sum_d2", C.c_double),
+                ("inlier_rmse", C.c_double), ("plane_rmse", C.c_double), ("information", C.c_double * 36),
+                ("hessian_plane", C.c_double * 36)]
+
+
+class EvalKfPair(C.Structure):
+    _fields_ = [("source", C.c_void_p), ("target", C.c_void_p), ("T", C.c_double * 16)]
+
+
 class KeyframeInfo(C.Structure):
     _fields_ = [("n_points", C.c_int), ("n_voxels", C.c_int), ("voxel_size", C.c_float), ("normal_radius", C.c_float),
                 ("fpfh_radius", C.c_float), ("passed_through", C.c_int), ("device_bytes", C.c_ulonglong)]
@@ -123,6 +138,8 @@ KF_VOX, KF_NORMALS, KF_FPFH, KF_MEAN = 1, 2, 3, 4
 PLACE_DESC, PLACE_COLNORM2 = 1, 2
 PLACE_MAX_K = 64
 SUBMAP_MAX_KEYFRAMES = 64
+EVAL_MAX_PAIRS = 64
+DBG_EVAL_CORR = 18
 
 EXPORTS = [
     "qtr_create", "qtr_destroy", "qtr_last_error", "qtr_default_limits", "qtr_default_params", "qtr_demo_params",
@@ -135,6 +152,8 @@ EXPORTS = [
     "qtr_default_place_params", "qtr_place_index_create", "qtr_place_index_destroy", "qtr_place_index_get_info",
     "qtr_place_describe", "qtr_place_index_add", "qtr_place_index_add_desc", "qtr_place_index_fetch", "qtr_place_query",
     "qtr_place_query_desc",
+    "qtr_default_eval_params", "qtr_evaluate", "qtr_evaluate_pair", "qtr_evaluate_keyframes",
+    "qtr_evaluate_keyframes_batch",
 ]
 
 _lib = None
@@ -309,6 +328,15 @@ def load(path: str | None = None):
     lib.qtr_keyframe_merge.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p, C.c_int,
                                        C.POINTER(FrontendParams), C.POINTER(C.c_void_p)]
     lib.qtr_default_place_params.restype = None
+    lib.qtr_default_eval_params.argtypes = [C.POINTER(EvalParams)]
+    lib.qtr_default_eval_params.restype = None
+    lib.qtr_evaluate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.POINTER(EvalParams), C.POINTER(EvalResult), C.c_int]
+    lib.qtr_evaluate_pair.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(EvalParams), C.POINTER(EvalResult)]
+    lib.qtr_evaluate_keyframes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(EvalParams),
+                                           C.POINTER(EvalResult)]
+    lib.qtr_evaluate_keyframes_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(EvalKfPair), C.c_int, C.POINTER(EvalParams),
+                                                 C.POINTER(EvalResult)]
     lib.qtr_default_place_params.argtypes = [C.POINTER(PlaceParams)]
     lib.qtr_place_index_create.argtypes = [C.c_void_p, C.POINTER(PlaceParams), C.c_int, C.POINTER(C.c_void_p)]
     lib.qtr_place_index_destroy.restype = None
@@ -371,6 +399,23 @@ def default_icp_params(**kw) -> IcpParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_eval_params(**kw) -> EvalParams:
+    """The evaluation's knob (qtr_default_eval_params: 1.0 m, like the ICP's), overridden by keyword."""
+    p = EvalParams()
+    load().qtr_default_eval_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def _eval_dict(res: EvalResult) -> dict:
+    return {"status": res.status, "valid": bool(res.valid), "n_source": res.n_source, "n_corr": res.n_corr,
+            "n_plane": res.n_plane, "T": np.array(res.T[:]).reshape(4, 4), "overlap": res.overlap, "sum_d2": res.sum_d2,
+            "inlier_rmse": res.inlier_rmse, "plane_rmse": res.plane_rmse,
+            "information": np.array(res.information[:]).reshape(6, 6),
+            "hessian_plane": np.array(res.hessian_plane[:]).reshape(6, 6)}
 
 
 def default_place_params(**kw) -> PlaceParams:
@@ -1119,6 +1164,64 @@ class Handle:
         rc = self._lib.qtr_refine_pair(self._h, slot, None if g is None else g.ctypes.data, C.byref(prm), C.byref(res))
         self._check(rc)
         return _icp_dict(res)
+
+    def evaluate(self, src4, tgt4, T, tgt_normals4=None, params: EvalParams | None = None, slot: int = 0) -> dict:
+        """Evaluates T (maps src4 into tgt4) on two clouds (qtr_evaluate): overlap, inlier RMSE, the 6x6 information matrix
+        and, with tgt_normals4, the point-to-plane Hessian.  Arrays as for icp (numpy on the host, or torch tensors all on
+        the device).  Returns the record as a dict, the matrices as 6x6 float64."""
+        prm = params or default_eval_params()
+        if isinstance(src4, np.ndarray) or isinstance(tgt4, np.ndarray):
+            src4, tgt4 = _f4(src4), _f4(tgt4)
+            tgt_normals4 = None if tgt_normals4 is None else _f4(tgt_normals4)
+            ps, pt, pn, mem = src4.ctypes.data, tgt4.ctypes.data, (None if tgt_normals4 is None else
+                                                                   tgt_normals4.ctypes.data), MEM_HOST
+        else:
+            (ps, m1), (pt, m2) = _ptr(src4), _ptr(tgt4)
+            pn, m3 = _ptr(tgt_normals4)
+            assert m1 == m2 == MEM_DEVICE and m3 in (None, MEM_DEVICE), "torch tensors must all be on the device"
+            assert src4.dtype == tgt4.dtype and src4.shape[-1] == 4 and tgt4.shape[-1] == 4
+            mem = MEM_DEVICE
+        g = _guess16(T)
+        res = EvalResult()
+        rc = self._lib.qtr_evaluate(self._h, slot, ps, int(src4.shape[0]), pt, int(tgt4.shape[0]), pn,
+                                    None if g is None else g.ctypes.data, C.byref(prm), C.byref(res), mem)
+        self._check(rc)
+        return _eval_dict(res)
+
+    def evaluate_pair(self, T=None, params: EvalParams | None = None, slot: int = 0) -> dict:
+        """Evaluates the slot's last registration on its voxelised clouds (qtr_evaluate_pair); T None = its own T."""
+        prm = params or default_eval_params()
+        g = _guess16(T)
+        res = EvalResult()
+        rc = self._lib.qtr_evaluate_pair(self._h, slot, None if g is None else g.ctypes.data, C.byref(prm), C.byref(res))
+        self._check(rc)
+        return _eval_dict(res)
+
+    def evaluate_keyframes(self, kf_src: Keyframe, kf_tgt: Keyframe, T, params: EvalParams | None = None,
+                           slot: int = 0) -> dict:
+        """Evaluates T between two keyframes, read where they lie (qtr_evaluate_keyframes)."""
+        prm = params or default_eval_params()
+        g = _guess16(T)
+        res = EvalResult()
+        rc = self._lib.qtr_evaluate_keyframes(self._h, slot, None if kf_src is None else kf_src._kf,
+                                              None if kf_tgt is None else kf_tgt._kf,
+                                              None if g is None else g.ctypes.data, C.byref(prm), C.byref(res))
+        self._check(rc)
+        return _eval_dict(res)
+
+    def evaluate_keyframes_batch(self, pairs, params: EvalParams | None = None, slot: int = 0) -> list:
+        """pairs: (source Keyframe, target Keyframe, T) triples, 1 .. EVAL_MAX_PAIRS of them, evaluated in one grouped
+        launch chain (qtr_evaluate_keyframes_batch).  Returns one record dict per pair."""
+        prm = params or default_eval_params()
+        B = len(pairs)
+        arr = (EvalKfPair * max(B, 1))()
+        for i, (a, b, T) in enumerate(pairs[:len(arr)]):
+            arr[i].source = None if a is None else a._kf.value
+            arr[i].target = None if b is None else b._kf.value
+            arr[i].T[:] = list(np.asarray(T, dtype=np.float64).reshape(16))
+        res = (EvalResult * max(B, 1))()
+        self._check(self._lib.qtr_evaluate_keyframes_batch(self._h, slot, arr, B, C.byref(prm), res))
+        return [_eval_dict(res[i]) for i in range(B)]
 
     def debug_fetch(self, what: int, dtype, slot: int = 0) -> np.ndarray:
         nbytes = self._lib.qtr_debug_fetch(self._h, slot, what, None, 0)
