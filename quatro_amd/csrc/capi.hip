@@ -2585,9 +2585,6 @@ static void batch_fail_pair(qtr_handle* h, int pair, int status) {
 
 // ICP pieces the refine phase shares with qtr_icp / qtr_refine_pair (defined with them, below)
 static int check_icp_params(qtr_handle* h, const qtr_icp_params* p);
-static void icp_result_from(qtr_icp_result* res, const QtrIcpState& st);
-static QtrIcpCfg icp_cfg_of(const qtr_icp_params* prm);
-static bool icp_grid_of(IcpView& v, const int* bbox, double max_d, int cap_cells);
 static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const float4* d_tgt, int nt, const float4* d_nrm,
                       const float4* d_src_nrm, const double* guess, const qtr_icp_params* prm, qtr_icp_result* res);
 
@@ -3522,57 +3519,6 @@ static int check_icp_params(qtr_handle* h, const qtr_icp_params* p) {
   return QTR_OK;
 }
 
-static QtrIcpCfg icp_cfg_of(const qtr_icp_params* prm) {
-  QtrIcpCfg c;
-  c.max_d2 = prm->max_correspondence_distance * prm->max_correspondence_distance;
-  c.trans_eps = prm->transformation_epsilon;
-  c.fit_eps = prm->euclidean_fitness_epsilon;
-  c.max_iterations = prm->max_iterations;
-  c.method = prm->method;
-  c.min_corr = prm->min_correspondences > 0 ? prm->min_correspondences
-               : prm->method == QTR_ICP_POINT_TO_PLANE ? 6
-               : prm->method == QTR_ICP_PLANE_TO_PLANE ? 4  // (pcl GICP's min_number_correspondences_)
-                                                       : 3;
-  c.pad = 0;
-  return c;
-}
-
-// The cell grid of a target box (6 order-preserving encodings, k_icp_bbox): cells a little larger than the correspondence
-// distance (a rounding of the cell index cannot hide a point in reach); a grid of more than cap_cells cells takes larger
-// ones.  Any cell >= the distance finds the same nearest neighbour (ties go to the lowest index), so the grid's shape does
-// not change a result.  false: no finite target point.
-static bool icp_grid_of(IcpView& v, const int* bbox, double max_d, int cap_cells) {
-  if (bbox[0] > bbox[3]) return false;
-  double mx[3];
-  for (int a = 0; a < 3; ++a) {
-    v.mn[a] = (double)icp_dec(bbox[a]);
-    mx[a] = (double)icp_dec(bbox[3 + a]);
-  }
-  double cell = max_d * 1.001;
-  double nc = 0;
-  for (;;) {
-    nc = 1;
-    for (int a = 0; a < 3; ++a) nc *= floor((mx[a] - v.mn[a]) / cell) + 1.0;
-    if (nc <= (double)cap_cells) break;
-    cell *= 1.25;
-  }
-  v.cell = cell;
-  for (int a = 0; a < 3; ++a) v.dims[a] = (int)(floor((mx[a] - v.mn[a]) / cell) + 1.0);
-  v.ncell = v.dims[0] * v.dims[1] * v.dims[2];
-  return true;
-}
-
-static void icp_result_from(qtr_icp_result* res, const QtrIcpState& st) {
-  res->valid = st.valid;
-  res->converged = st.converged;
-  res->stop_reason = st.reason;
-  res->iterations = st.iterations;
-  res->n_corr = st.n_corr;
-  for (int k = 0; k < 16; ++k) res->T[k] = st.T[k];
-  res->fitness = st.fitness;
-  res->rmse = st.rmse;
-}
-
 // The loop on device-resident clouds: grid over the target, then the iterations, one launch each, with no host read-back
 // inside a block of h->icp_block launches (0: all max_iterations of them in one go).
 static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const float4* d_tgt, int nt, const float4* d_nrm,
@@ -3604,29 +3550,16 @@ static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const
   const hipStream_t st = s.stream;
   QTR_HIP_TRY(h, hipEventRecord(s.ev[0], st));
   // bounding box of the finite target points (one read-back per call: it sizes the cell table)
-  for (int a = 0; a < 3; ++a) {
-    B.h_bbox[a] = 0x7fffffff;
-    B.h_bbox[3 + a] = (int)0x80000000;
-  }
-  QTR_HIP_TRY(h, hipMemcpyAsync(v.bbox, B.h_bbox, 24, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_icp_bbox, dim3(qtr_div_up(nt, 256)), dim3(256), 0, st, v);
-  QTR_HIP_TRY(h, hipGetLastError());
+  QTR_HIP_TRY(h, icp_box_enqueue(v, B.h_bbox, st));
   QTR_HIP_TRY(h, hipMemcpyAsync(B.h_bbox, v.bbox, 24, hipMemcpyDeviceToHost, st));
   QTR_HIP_TRY(h, hipStreamSynchronize(st));
   if (!icp_grid_of(v, B.h_bbox, prm->max_correspondence_distance, QTR_ICP_CELL_CAP)) return QTR_OK;  // no finite target point
   QTR_HIP_TRY(h, icp_reserve_cells(B, v.ncell));
   v.cell_cnt = B.cells;
   v.cell_start = B.cells + B.cap_cells + 1;
-  QTR_HIP_TRY(h, hipMemsetAsync(v.cell_cnt, 0, (size_t)(v.ncell + 1) * 4, st));
-  hipLaunchKernelGGL(k_icp_count, dim3(qtr_div_up(nt, 256)), dim3(256), 0, st, v);
-  QTR_HIP_TRY(h, hipGetLastError());
-  QTR_HIP_TRY(h, exclusive_scan_i32(v.cell_cnt, v.cell_start, v.ncell, st));
-  hipLaunchKernelGGL(k_icp_place, dim3(qtr_div_up(nt, 256)), dim3(256), 0, st, v);
-  QTR_HIP_TRY(h, hipGetLastError());
   QtrIcpState st0;
   qtr_icp_init(&st0, guess);
-  hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, v, st0);
-  QTR_HIP_TRY(h, hipGetLastError());
+  QTR_HIP_TRY(h, icp_grid_enqueue(v, st0, st));
   QTR_HIP_TRY(h, hipEventRecord(s.ev[1], st));
   const int nchunk = qtr_div_up(ns, QTR_ICP_CHUNK);
   const int block = h->icp_block > 0 ? h->icp_block : prm->max_iterations;
@@ -3666,6 +3599,65 @@ static bool icp_guess_ok(const double* g) {
   return true;
 }
 
+// What qtr_icp, qtr_gicp and qtr_evaluate do with their two clouds (0: source, 1: target) before anything runs: the argument
+// and the capacity checks (bad_args, cloud: the entry's own words in the messages; guess may be null), then — run: the entry
+// has something to launch — host clouds into the raw-scan buffers (max_points >= max_voxels points each) and the host normal
+// sets the entry names into cloud[c].normals.  pts / nrm come back as device pointers.
+static int clouds_stage(qtr_handle* h, Slot& s, const char* bad_args, const char* cloud, const double* guess, int mem,
+                        const int n[2], const float4* pts[2], const float4* nrm[2], bool run) {
+  if (n[0] < 0 || n[1] < 0 || (n[0] > 0 && !pts[0]) || (n[1] > 0 && !pts[1]) ||
+      (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE) || (guess && !icp_guess_ok(guess))) {
+    snprintf(h->err, sizeof(h->err), "%s", bad_args);
+    return QTR_ERR_BAD_ARG;
+  }
+  if (n[0] > h->lim.max_voxels || n[1] > h->lim.max_voxels) {
+    snprintf(h->err, sizeof(h->err), "%s exceeds max_voxels=%d", cloud, h->lim.max_voxels);
+    return QTR_ERR_CAPACITY;
+  }
+  if (!run) return QTR_OK;
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  if (mem != QTR_MEM_HOST) return QTR_OK;
+  float4* const in[2] = {s.in_src, s.in_tgt};
+  for (int c = 0; c < 2; ++c) {
+    if (n[c] > 0) QTR_HIP_TRY(h, hipMemcpyAsync(in[c], pts[c], (size_t)n[c] * 16, hipMemcpyHostToDevice, s.stream));
+    pts[c] = in[c];
+  }
+  for (int c = 0; c < 2; ++c)
+    if (nrm[c] && n[c] > 0) {
+      QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[c].normals, nrm[c], (size_t)n[c] * 16, hipMemcpyHostToDevice, s.stream));
+      nrm[c] = s.fb.cloud[c].normals;
+    }
+  return QTR_OK;
+}
+
+// The normals of `count` device clouds at normal_radius, for a caller that did not bring them: the normal stage of the FPFH
+// chain (qtr_fpfh's dense mode) on copies of the clouds in the arenas cloud[first ..], all in one chain.  nrm[k] = the
+// arena's normals.
+static int normals_at_radius(qtr_handle* h, Slot& s, int first, int count, const float4* const* pts, const int* n,
+                             float normal_radius, const float4** nrm) {
+  for (int k = 0; k < count; ++k) {
+    CloudBufs& cb = s.fb.cloud[first + k];
+    QTR_HIP_TRY(h, hipMemcpyAsync(cb.vox, pts[k], (size_t)n[k] * 16, hipMemcpyDeviceToDevice, s.stream));
+    QTR_HIP_TRY(h, hipMemsetAsync(cb.counts, 0, 16 * sizeof(int), s.stream));
+    QTR_HIP_TRY(h, set_count_enqueue(cb, CNT_NVOX, n[k], s.stream));
+  }
+  QTR_TRY(ensure_long_arenas(h, s));
+  QTR_HIP_TRY(h, fpfh_enqueue(s.fb, first, count, n, normal_radius, normal_radius, s.stream, false, false, true));
+  for (int c = first; c < first + count; ++c)
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32 + 16 * c, s.fb.cloud[c].counts, 16 * sizeof(int), hipMemcpyDeviceToHost,
+                                  s.stream));
+  QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
+  for (int k = 0; k < count; ++k) {
+    if (s.pinned_i32[16 * (first + k) + CNT_NBR_CAPACITY]) {
+      snprintf(h->err, sizeof(h->err), "normals at normal_radius: radius-neighbour lists exceed the long-list arena "
+               "(qtr_limits.max_long_neighbors is %d)", h->lim.max_long_neighbors);
+      return QTR_ERR_CAPACITY;
+    }
+    nrm[k] = s.fb.cloud[first + k].normals;
+  }
+  return QTR_OK;
+}
+
 int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const float* tgt4, int n_t, const float* tgt_normals4,
             const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res, int mem) {
   Slot* sp = get_slot(h, slot);
@@ -3676,56 +3668,20 @@ int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const float* tg
   if (rc != QTR_OK) return res->status = rc;
   if (prm->method == QTR_ICP_PLANE_TO_PLANE)  // (the source normals at normal_radius)
     return qtr_gicp(h, slot, src4, n_s, nullptr, tgt4, n_t, tgt_normals4, guess, prm, res, mem);
-  if (n_s < 0 || n_t < 0 || (n_s > 0 && !src4) || (n_t > 0 && !tgt4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE) ||
-      (guess && !icp_guess_ok(guess))) {
-    snprintf(h->err, sizeof(h->err), "bad ICP arguments");
-    return res->status = QTR_ERR_BAD_ARG;
-  }
-  if (n_s > h->lim.max_voxels || n_t > h->lim.max_voxels) {
-    snprintf(h->err, sizeof(h->err), "ICP cloud exceeds max_voxels=%d", h->lim.max_voxels);
-    return res->status = QTR_ERR_CAPACITY;
-  }
-  const double* g = guess ? guess : kIcpIdentity;
-  if (n_s == 0 || n_t == 0) return icp_device(h, s, nullptr, n_s, nullptr, n_t, nullptr, nullptr, g, prm, res);
-  QTR_HIP_TRY(h, hipSetDevice(h->device));
-  const float4 *d_s = (const float4*)src4, *d_t = (const float4*)tgt4, *d_n = (const float4*)tgt_normals4;
-  const bool plane = prm->method == QTR_ICP_POINT_TO_PLANE;
-  if (mem == QTR_MEM_HOST) {  // (staging: the raw-scan buffers, max_points >= max_voxels points each)
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, src4, (size_t)n_s * 16, hipMemcpyHostToDevice, s.stream));
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_tgt, tgt4, (size_t)n_t * 16, hipMemcpyHostToDevice, s.stream));
-    d_s = s.in_src;
-    d_t = s.in_tgt;
-    if (plane && tgt_normals4) {
-      QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[1].normals, tgt_normals4, (size_t)n_t * 16, hipMemcpyHostToDevice, s.stream));
-      d_n = s.fb.cloud[1].normals;
-    }
-  }
-  if (plane && !tgt_normals4) {
-    // the target's normals at normal_radius: the normal stage of the FPFH chain (qtr_fpfh's dense mode) on a copy of the
-    // target in the first cloud's arena
-    CloudBufs& cb = s.fb.cloud[0];
-    QTR_HIP_TRY(h, hipMemcpyAsync(cb.vox, d_t, (size_t)n_t * 16, hipMemcpyDeviceToDevice, s.stream));
-    QTR_HIP_TRY(h, hipMemsetAsync(cb.counts, 0, 16 * sizeof(int), s.stream));
-    QTR_HIP_TRY(h, set_count_enqueue(cb, CNT_NVOX, n_t, s.stream));
-    QTR_TRY(ensure_long_arenas(h, s));
-    const int n1[1] = {n_t};
-    QTR_HIP_TRY(h, fpfh_enqueue(s.fb, 0, 1, n1, prm->normal_radius, prm->normal_radius, s.stream, false, false, true));
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32, cb.counts, 16 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
-    QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
-    if (s.pinned_i32[CNT_NBR_CAPACITY]) {
-      snprintf(h->err, sizeof(h->err), "normals at normal_radius: radius-neighbour lists exceed the long-list arena "
-               "(qtr_limits.max_long_neighbors is %d)", h->lim.max_long_neighbors);
-      return res->status = QTR_ERR_CAPACITY;
-    }
-    d_n = cb.normals;
-  }
-  rc = icp_device(h, s, d_s, n_s, d_t, n_t, d_n, nullptr, g, prm, res);
+  const bool plane = prm->method == QTR_ICP_POINT_TO_PLANE, run = n_s > 0 && n_t > 0;
+  const int n[2] = {n_s, n_t};
+  const float4* pts[2] = {(const float4*)src4, (const float4*)tgt4};
+  const float4* nrm[2] = {nullptr, plane ? (const float4*)tgt_normals4 : nullptr};
+  rc = clouds_stage(h, s, "bad ICP arguments", "ICP cloud", guess, mem, n, pts, nrm, run);
+  // the target's missing normals: on a copy of the target in the FIRST cloud's arena
+  if (rc == QTR_OK && run && plane && !nrm[1]) rc = normals_at_radius(h, s, 0, 1, pts + 1, n + 1, prm->normal_radius, nrm + 1);
+  if (rc == QTR_OK) rc = icp_device(h, s, pts[0], n_s, pts[1], n_t, nrm[1], nullptr, guess ? guess : kIcpIdentity, prm, res);
   return res->status = rc;
 }
 
 // Plane-to-plane on any two clouds.  The source lives in the first cloud's arena and the target in the second's (as after a
-// registration); a normal set the caller does not bring comes from the normal stage of the FPFH chain (qtr_fpfh's dense
-// mode) at normal_radius — both clouds in one chain when both are missing.
+// registration); a normal set the caller does not bring comes from normals_at_radius — both clouds in one chain when both
+// are missing.
 int qtr_gicp(qtr_handle* h, int slot, const float* src4, int n_s, const float* src_normals4, const float* tgt4, int n_t,
              const float* tgt_normals4, const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res, int mem) {
   Slot* sp = get_slot(h, slot);
@@ -3738,59 +3694,15 @@ int qtr_gicp(qtr_handle* h, int slot, const float* src4, int n_s, const float* s
     snprintf(h->err, sizeof(h->err), "qtr_gicp: method must be QTR_ICP_PLANE_TO_PLANE");
     return res->status = QTR_ERR_BAD_ARG;
   }
-  if (n_s < 0 || n_t < 0 || (n_s > 0 && !src4) || (n_t > 0 && !tgt4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE) ||
-      (guess && !icp_guess_ok(guess))) {
-    snprintf(h->err, sizeof(h->err), "bad ICP arguments");
-    return res->status = QTR_ERR_BAD_ARG;
-  }
-  if (n_s > h->lim.max_voxels || n_t > h->lim.max_voxels) {
-    snprintf(h->err, sizeof(h->err), "ICP cloud exceeds max_voxels=%d", h->lim.max_voxels);
-    return res->status = QTR_ERR_CAPACITY;
-  }
-  const double* g = guess ? guess : kIcpIdentity;
-  if (n_s == 0 || n_t == 0) return icp_device(h, s, nullptr, n_s, nullptr, n_t, nullptr, nullptr, g, prm, res);
-  QTR_HIP_TRY(h, hipSetDevice(h->device));
-  const float4* d_pts[2] = {(const float4*)src4, (const float4*)tgt4};
-  const float4* d_nrm[2] = {(const float4*)src_normals4, (const float4*)tgt_normals4};
+  const bool run = n_s > 0 && n_t > 0;
   const int n[2] = {n_s, n_t};
-  if (mem == QTR_MEM_HOST) {  // (staging: the raw-scan buffers, max_points >= max_voxels points each)
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, src4, (size_t)n_s * 16, hipMemcpyHostToDevice, s.stream));
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_tgt, tgt4, (size_t)n_t * 16, hipMemcpyHostToDevice, s.stream));
-    d_pts[0] = s.in_src;
-    d_pts[1] = s.in_tgt;
-    for (int c = 0; c < 2; ++c)
-      if (d_nrm[c]) {
-        QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[c].normals, d_nrm[c], (size_t)n[c] * 16, hipMemcpyHostToDevice, s.stream));
-        d_nrm[c] = s.fb.cloud[c].normals;
-      }
-  }
-  const int first = d_nrm[0] ? 1 : 0, last = d_nrm[1] ? 0 : 1;  // clouds first..last need their normals
-  if (first <= last) {
-    int nn[2] = {0, 0};
-    for (int c = first; c <= last; ++c) {
-      CloudBufs& cb = s.fb.cloud[c];
-      QTR_HIP_TRY(h, hipMemcpyAsync(cb.vox, d_pts[c], (size_t)n[c] * 16, hipMemcpyDeviceToDevice, s.stream));
-      QTR_HIP_TRY(h, hipMemsetAsync(cb.counts, 0, 16 * sizeof(int), s.stream));
-      QTR_HIP_TRY(h, set_count_enqueue(cb, CNT_NVOX, n[c], s.stream));
-      nn[c - first] = n[c];
-    }
-    QTR_TRY(ensure_long_arenas(h, s));
-    QTR_HIP_TRY(h, fpfh_enqueue(s.fb, first, last - first + 1, nn, prm->normal_radius, prm->normal_radius, s.stream, false,
-                                false, true));
-    for (int c = first; c <= last; ++c)
-      QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32 + 16 * c, s.fb.cloud[c].counts, 16 * sizeof(int), hipMemcpyDeviceToHost,
-                                    s.stream));
-    QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
-    for (int c = first; c <= last; ++c) {
-      if (s.pinned_i32[16 * c + CNT_NBR_CAPACITY]) {
-        snprintf(h->err, sizeof(h->err), "normals at normal_radius: radius-neighbour lists exceed the long-list arena "
-                 "(qtr_limits.max_long_neighbors is %d)", h->lim.max_long_neighbors);
-        return res->status = QTR_ERR_CAPACITY;
-      }
-      d_nrm[c] = s.fb.cloud[c].normals;
-    }
-  }
-  rc = icp_device(h, s, d_pts[0], n_s, d_pts[1], n_t, d_nrm[1], d_nrm[0], g, prm, res);
+  const float4* pts[2] = {(const float4*)src4, (const float4*)tgt4};
+  const float4* nrm[2] = {(const float4*)src_normals4, (const float4*)tgt_normals4};
+  rc = clouds_stage(h, s, "bad ICP arguments", "ICP cloud", guess, mem, n, pts, nrm, run);
+  const int first = nrm[0] ? 1 : 0, last = nrm[1] ? 0 : 1;  // clouds first..last need their normals
+  if (rc == QTR_OK && run && first <= last)
+    rc = normals_at_radius(h, s, first, last - first + 1, pts + first, n + first, prm->normal_radius, nrm + first);
+  if (rc == QTR_OK) rc = icp_device(h, s, pts[0], n_s, pts[1], n_t, nrm[1], nrm[0], guess ? guess : kIcpIdentity, prm, res);
   return res->status = rc;
 }
 
@@ -3848,19 +3760,6 @@ struct EvalPair {
   const double* T;
 };
 
-static void eval_result_from(qtr_eval_result* res, const QtrEvalRecord& r) {
-  res->valid = r.valid;
-  res->n_source = r.n_source;
-  res->n_corr = r.n_corr;
-  res->n_plane = r.n_plane;
-  res->overlap = r.overlap;
-  res->sum_d2 = r.sum_d2;
-  res->inlier_rmse = r.inlier_rmse;
-  res->plane_rmse = r.plane_rmse;
-  memcpy(res->information, r.information, sizeof(r.information));
-  memcpy(res->hessian_plane, r.hessian_plane, sizeof(r.hessian_plane));
-}
-
 // B evaluations on device-resident clouds, validated by the caller.  Two host waits whatever B is: the target boxes (they
 // size the cell tables) and the records.  grouped = false (B == 1): the single-pair kernels with the view by value.
 static int eval_device(qtr_handle* h, Slot& s, const EvalPair* P, int B, double max_d, bool grouped, qtr_eval_result* out) {
@@ -3910,10 +3809,6 @@ static int eval_device(qtr_handle* h, Slot& s, const EvalPair* P, int B, double 
     v.trace = (double*)(E.d_rec + b);
     v.cfg.max_d2 = max_d * max_d;
     qtr_icp_init(&E.h_init[b], P[b].T);
-    for (int a = 0; a < 3; ++a) {
-      E.h_boxes[8 * b + a] = 0x7fffffff;
-      E.h_boxes[8 * b + 3 + a] = (int)0x80000000;
-    }
   }
   E.last_corr = E.h_views[0].corr;
   E.last_ns = 0;
@@ -3922,8 +3817,7 @@ static int eval_device(qtr_handle* h, Slot& s, const EvalPair* P, int B, double 
   const ViewExt<IcpView> x{E.d_views, {0, 0, 0}};
   // first wait: the boxes of the finite target points
   if (!grouped) {
-    QTR_HIP_TRY(h, hipMemcpyAsync(E.d_boxes, E.h_boxes, 24, hipMemcpyHostToDevice, st));
-    if (P[0].nt > 0) hipLaunchKernelGGL(k_icp_bbox, dim3(qtr_div_up(P[0].nt, 256)), dim3(256), 0, st, E.h_views[0]);
+    QTR_HIP_TRY(h, icp_box_enqueue(E.h_views[0], E.h_boxes, st));
   } else {
     QTR_HIP_TRY(h, hipMemcpyAsync(E.d_views, E.h_views, view_block, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_icp_box_init_group, dim3(1, B), dim3(64), 0, st, x);
@@ -3936,12 +3830,7 @@ static int eval_device(qtr_handle* h, Slot& s, const EvalPair* P, int B, double 
   int max_ncell = 0;
   for (int b = 0; b < B; ++b) {
     IcpView& v = E.h_views[b];
-    if (!icp_grid_of(v, E.h_boxes + 8 * b, max_d, QTR_EVAL_CELLS)) {  // no finite target point: nothing is searched
-      v.ncell = 0;
-      v.dims[0] = v.dims[1] = v.dims[2] = 0;
-      v.mn[0] = v.mn[1] = v.mn[2] = 0.0;
-      v.cell = 1.0;
-    }
+    (void)icp_grid_of(v, E.h_boxes + 8 * b, max_d, QTR_EVAL_CELLS);  // (no finite target point: the empty grid)
     cell_ints += 2 * ((size_t)v.ncell + 1);
     max_ncell = std::max(max_ncell, v.ncell);
   }
@@ -3955,15 +3844,8 @@ static int eval_device(qtr_handle* h, Slot& s, const EvalPair* P, int B, double 
   }
   // second wait: the records
   if (!grouped) {
-    const IcpView& v = E.h_views[0];
-    QTR_HIP_TRY(h, hipMemsetAsync(v.cell_cnt, 0, (size_t)(v.ncell + 1) * 4, st));
-    if (v.nt > 0) {
-      hipLaunchKernelGGL(k_icp_count, dim3(qtr_div_up(v.nt, 256)), dim3(256), 0, st, v);
-      QTR_HIP_TRY(h, exclusive_scan_i32(v.cell_cnt, v.cell_start, v.ncell, st));
-      hipLaunchKernelGGL(k_icp_place, dim3(qtr_div_up(v.nt, 256)), dim3(256), 0, st, v);
-    }
-    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, v, E.h_init[0]);
-    hipLaunchKernelGGL(k_eval, dim3(max_nchunk), dim3(256), 0, st, v);
+    QTR_HIP_TRY(h, icp_grid_enqueue(E.h_views[0], E.h_init[0], st));
+    hipLaunchKernelGGL(k_eval, dim3(max_nchunk), dim3(256), 0, st, E.h_views[0]);
   } else {
     QTR_HIP_TRY(h, hipMemcpyAsync(E.d_views, E.h_views, view_block, hipMemcpyHostToDevice, st));
     QTR_HIP_TRY(h, icp_grid_enqueue_group(E.d_views, E.d_init, B, std::max(max_nt, 1), max_ncell, st));
@@ -3987,26 +3869,12 @@ int qtr_evaluate(qtr_handle* h, int slot, const float* src4, int n_s, const floa
   int rc = check_eval_params(h, prm);
   if (rc == QTR_OK) rc = check_eval_T(h, T);
   if (rc != QTR_OK) return res->status = rc;
-  if (n_s < 0 || n_t < 0 || (n_s > 0 && !src4) || (n_t > 0 && !tgt4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) {
-    snprintf(h->err, sizeof(h->err), "bad evaluation arguments");
-    return res->status = QTR_ERR_BAD_ARG;
-  }
-  if (n_s > h->lim.max_voxels || n_t > h->lim.max_voxels) {
-    snprintf(h->err, sizeof(h->err), "evaluation: cloud exceeds max_voxels=%d", h->lim.max_voxels);
-    return res->status = QTR_ERR_CAPACITY;
-  }
-  QTR_HIP_TRY(h, hipSetDevice(h->device));
-  EvalPair P{(const float4*)src4, (const float4*)tgt4, (const float4*)tgt_normals4, n_s, n_t, T};
-  if (mem == QTR_MEM_HOST) {  // (staging: the raw-scan buffers, max_points >= max_voxels points each)
-    if (n_s > 0) QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, src4, (size_t)n_s * 16, hipMemcpyHostToDevice, s.stream));
-    if (n_t > 0) QTR_HIP_TRY(h, hipMemcpyAsync(s.in_tgt, tgt4, (size_t)n_t * 16, hipMemcpyHostToDevice, s.stream));
-    P.src = s.in_src;
-    P.tgt = s.in_tgt;
-    if (tgt_normals4 && n_t > 0) {
-      QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[1].normals, tgt_normals4, (size_t)n_t * 16, hipMemcpyHostToDevice, s.stream));
-      P.nrm = s.fb.cloud[1].normals;
-    }
-  }
+  const int n[2] = {n_s, n_t};
+  const float4* pts[2] = {(const float4*)src4, (const float4*)tgt4};
+  const float4* nrm[2] = {nullptr, (const float4*)tgt_normals4};
+  rc = clouds_stage(h, s, "bad evaluation arguments", "evaluation: cloud", nullptr, mem, n, pts, nrm, true);
+  if (rc != QTR_OK) return res->status = rc;
+  const EvalPair P{pts[0], pts[1], nrm[1], n_s, n_t, T};
   rc = eval_device(h, s, &P, 1, prm->max_correspondence_distance, false, res);
   return res->status = rc;
 }

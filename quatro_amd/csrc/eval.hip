@@ -2,13 +2,14 @@
 // the source lies on the target under T (overlap, inlier RMSE), the 6x6 information matrix of the pose-graph edge and the
 // point-to-plane Hessian at T.  The arithmetic is include/qtr_eval_math.h.
 //
-// Per evaluation: the ICP's cell grid over the finite target points (k_icp_bbox / k_icp_count / scan / k_icp_place of
-// icp.hip, built into the slot's EVALUATION arena: the ICP arena and its state are not touched), then ONE launch of k_eval,
-// one workgroup per 256 source points.  Every thread transforms its point, runs the ICP's search (icp_nearest) and forms
-// its QTR_EVAL_NT terms; the workgroup folds them in the ICP's shape into one partial; the last workgroup to finish (atomic
-// ticket, as in d_icp_iter: nobody waits for anybody, no co-residency is assumed) adds the partials in chunk order, runs
-// qtr_eval_finish and writes the record.  An evaluation is described by an IcpView (st->T carries the transform, cfg.max_d2
-// the reach, `partials` is [nchunk][QTR_EVAL_NT], `trace` points at the QtrEvalRecord).
+// Per evaluation: the ICP's cell grid over the finite target points (icp_box_enqueue / icp_grid_enqueue of icp.hip: k_icp_bbox,
+// k_icp_count, scan, k_icp_place, k_icp_init; built into the slot's EVALUATION arena: the ICP arena and its state are not
+// touched), then ONE launch of k_eval, one workgroup per 256 source points.  Every thread transforms its point, runs the
+// ICP's search (icp_nearest) and forms its QTR_EVAL_NT terms; the workgroup folds them in the ICP's shape into one partial;
+// the last workgroup to finish (atomic ticket: icp_reduce_tail, d_icp_iter's; nobody waits for anybody, no co-residency is
+// assumed) adds the partials in chunk order, runs qtr_eval_finish and writes the record.  An evaluation is described by an
+// IcpView (st->T carries the transform, cfg.max_d2 the reach, `partials` is [nchunk][QTR_EVAL_NT], `trace` points at the
+// QtrEvalRecord).
 //
 // The batch (qtr_evaluate_keyframes_batch) is the same chain in grouped form, blockIdx.y = pair, every pair with a grid of
 // its own in the arena; a pair runs d_eval with its own chunk count, so its record is the single call's bit for bit.
@@ -20,14 +21,11 @@
 #define QTR_EVAL_CELLS (1 << 20)
 
 __device__ __forceinline__ void d_eval(const IcpView& v, int blk, int nblk) {
-  __shared__ double s_w[4][QTR_EVAL_NT];
   __shared__ double s_S[QTR_EVAL_NT];
-  __shared__ int s_last;
   double T[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) T[k] = v.st->T[k];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i = blk * QTR_ICP_CHUNK + tid;
+  const int i = blk * QTR_ICP_CHUNK + threadIdx.x;
   double e[QTR_EVAL_NT];
 #pragma unroll
   for (int k = 0; k < QTR_EVAL_NT; ++k) e[k] = 0.0;
@@ -51,41 +49,8 @@ __device__ __forceinline__ void d_eval(const IcpView& v, int blk, int nblk) {
     }
     v.corr[i] = best;
   }
-  // fixed-shape sum: the shfl_down fold inside each wave (qtr_icp_fold64), then (w0 + w1) + (w2 + w3)
-#pragma unroll
-  for (int k = 0; k < QTR_EVAL_NT; ++k) {
-    double x = e[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = x + icp_shfl_down(x, off);
-    if (lane == 0) s_w[wave][k] = x;
-  }
-  __syncthreads();
-  if (tid < QTR_EVAL_NT) {
-    const double w4[4] = {s_w[0][tid], s_w[1][tid], s_w[2][tid], s_w[3][tid]};
-    const double c = qtr_icp_chunk_sum(w4);
-    __hip_atomic_store((unsigned long long*)(v.partials + (size_t)blk * QTR_EVAL_NT + tid),
-                       (unsigned long long)__double_as_longlong(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned done = __hip_atomic_fetch_add(v.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = (done == (unsigned)nblk - 1) ? 1 : 0;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  if (tid < QTR_EVAL_NT) {
-    double acc = __longlong_as_double((long long)__hip_atomic_load((unsigned long long*)(v.partials + tid), __ATOMIC_RELAXED,
-                                                                   __HIP_MEMORY_SCOPE_AGENT));
-    for (int c = 1; c < nblk; ++c)
-      acc = acc + __longlong_as_double((long long)__hip_atomic_load(
-                      (unsigned long long*)(v.partials + (size_t)c * QTR_EVAL_NT + tid), __ATOMIC_RELAXED,
-                      __HIP_MEMORY_SCOPE_AGENT));
-    s_S[tid] = acc;
-  }
-  __syncthreads();
-  if (tid == 0) {
+  if (!icp_reduce_tail<QTR_EVAL_NT, QTR_EVAL_NT>(e, v.partials, v.ticket, blk, nblk, s_S)) return;
+  if (threadIdx.x == 0) {
     qtr_eval_finish(s_S, (QtrEvalRecord*)v.trace);
     __hip_atomic_store(v.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -100,29 +65,12 @@ __global__ __launch_bounds__(256) void k_eval_group(ViewExt<IcpView> x) {
   d_eval(v, (int)blockIdx.x, nblk);
 }
 
-// k_icp_bbox per pair, folded in LDS first.  (k_icp_bbox_group mails every box into its slot's mailbox; a batch of
+// d_icp_bbox_fold per pair and nothing else.  (k_icp_bbox_group mails every box into its slot's mailbox; a batch of
 // evaluations lives on ONE slot, so its boxes stay in the arena and travel in one copy.)
 __global__ __launch_bounds__(256) void k_eval_bbox_group(ViewExt<IcpView> x) {
   const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
-  __shared__ int s_bb[6];
   if ((int)blockIdx.x * 256 >= v.nt) return;
-  if (threadIdx.x < 6) s_bb[threadIdx.x] = threadIdx.x < 3 ? 0x7fffffff : (int)0x80000000;
-  __syncthreads();
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < v.nt) {
-    const float4 p = v.tgt[i];
-    if (qtr_icp_finite3(p.x, p.y, p.z)) {
-      atomicMin(s_bb + 0, icp_enc(p.x));
-      atomicMin(s_bb + 1, icp_enc(p.y));
-      atomicMin(s_bb + 2, icp_enc(p.z));
-      atomicMax(s_bb + 3, icp_enc(p.x));
-      atomicMax(s_bb + 4, icp_enc(p.y));
-      atomicMax(s_bb + 5, icp_enc(p.z));
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) atomicMin(v.bbox + threadIdx.x, s_bb[threadIdx.x]);
-  else if (threadIdx.x < 6) atomicMax(v.bbox + threadIdx.x, s_bb[threadIdx.x]);
+  d_icp_bbox_fold(v);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
@@ -215,4 +163,17 @@ static void eval_free(EvalBufs& E) {
   if (E.cells) (void)hipFree(E.cells);
   if (E.pin) (void)hipHostFree(E.pin);
   E = EvalBufs{};
+}
+
+static void eval_result_from(qtr_eval_result* res, const QtrEvalRecord& r) {
+  res->valid = r.valid;
+  res->n_source = r.n_source;
+  res->n_corr = r.n_corr;
+  res->n_plane = r.n_plane;
+  res->overlap = r.overlap;
+  res->sum_d2 = r.sum_d2;
+  res->inlier_rmse = r.inlier_rmse;
+  res->plane_rmse = r.plane_rmse;
+  memcpy(res->information, r.information, sizeof(r.information));
+  memcpy(res->hessian_plane, r.hessian_plane, sizeof(r.hessian_plane));
 }

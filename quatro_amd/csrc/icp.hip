@@ -3,16 +3,18 @@
 //
 // Per call: a uniform cell grid over the finite target points (cell side >= max_correspondence_distance, so the
 // nearest target within reach of any query lies in its 27 neighbouring cells), built by a counting sort into the
-// handle's own ICP arena (k_icp_bbox, k_icp_count, exclusive_scan_i32, k_icp_place).  The FPFH chain's cell table is not
-// used: its cells are the FPFH radius over the RAW scan's box and its counters must stay zero between registrations;
-// the ICP table has its own counters, cleared by the call that uses them.
+// handle's own ICP arena (icp_box_enqueue: k_icp_bbox; icp_grid_of on the host; icp_grid_enqueue: k_icp_count,
+// exclusive_scan_i32, k_icp_place, k_icp_init — the single evaluation of eval.hip runs the same two helpers).  The FPFH
+// chain's cell table is not used: its cells are the FPFH radius over the RAW scan's box and its counters must stay zero
+// between registrations; the ICP table has its own counters, cleared by the call that uses them.
 //
 // Per iteration: ONE launch of k_icp_iter (one workgroup per 256 source points).  Every thread transforms its point
 // with the current T, finds the nearest target (binary64 d^2, ties to the lowest target index, so the order inside a
 // cell does not matter) and forms its terms; the terms are summed in a fixed shape (include/qtr_icp_math.h) into one
-// partial per workgroup; the LAST workgroup to finish (atomic ticket) adds the partials in workgroup order, solves,
-// updates T and decides whether to stop.  Nobody waits for anybody, so no co-residency is assumed.  A launch that finds
-// the stop flag set returns at once, so the host can enqueue iterations without reading anything back.
+// partial per workgroup; the LAST workgroup to finish (atomic ticket) adds the partials in workgroup order
+// (icp_reduce_tail, which the evaluation shares), solves, updates T and decides whether to stop.  Nobody waits for
+// anybody, so no co-residency is assumed.  A launch that finds the stop flag set returns at once, so the host can enqueue
+// iterations without reading anything back.
 //
 // Batched refinement (qtr_submit_batch_refine): the same kernels in grouped form, blockIdx.y = pair of the lane's group,
 // the per-pair IcpViews in device memory (ViewExt).  Every pair runs the per-pair body the single-pair kernel runs
@@ -159,20 +161,63 @@ __device__ __forceinline__ void icp_nearest(const IcpView& v, const double* q, i
   }
 }
 
+// The reduction tail d_icp_iter and d_eval (eval.hip) share, called by every thread of a workgroup (chunk `blk` of `nblk`)
+// with its NT terms: the fixed-shape sum (the shfl_down fold inside each wave, qtr_icp_fold64, then (w0 + w1) + (w2 + w3))
+// into the chunk's partial at partials[blk * STRIDE], a fence, the ticket.  true: this is the LAST workgroup to arrive, and
+// s_S[0 .. NT) holds the partials added in chunk order; the caller resets the ticket when it is done.
+template <int NT, int STRIDE>
+__device__ __forceinline__ bool icp_reduce_tail(const double* x, double* partials, unsigned* ticket, int blk, int nblk,
+                                                double* s_S) {
+  __shared__ double s_w[4][STRIDE];
+  __shared__ int s_last;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int k = 0; k < NT; ++k) {
+    double a = x[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) a = a + icp_shfl_down(a, off);
+    if (lane == 0) s_w[wave][k] = a;
+  }
+  __syncthreads();
+  if (tid < NT) {
+    const double w4[4] = {s_w[0][tid], s_w[1][tid], s_w[2][tid], s_w[3][tid]};
+    const double c = qtr_icp_chunk_sum(w4);
+    __hip_atomic_store((unsigned long long*)(partials + (size_t)blk * STRIDE + tid),
+                       (unsigned long long)__double_as_longlong(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned done = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = (done == (unsigned)nblk - 1) ? 1 : 0;
+  }
+  __syncthreads();
+  if (!s_last) return false;
+  __threadfence();
+  if (tid < NT) {
+    double acc = __longlong_as_double((long long)__hip_atomic_load((unsigned long long*)(partials + tid), __ATOMIC_RELAXED,
+                                                                   __HIP_MEMORY_SCOPE_AGENT));
+    for (int c = 1; c < nblk; ++c)
+      acc = acc + __longlong_as_double((long long)__hip_atomic_load(
+                      (unsigned long long*)(partials + (size_t)c * STRIDE + tid), __ATOMIC_RELAXED,
+                      __HIP_MEMORY_SCOPE_AGENT));
+    s_S[tid] = acc;
+  }
+  __syncthreads();
+  return true;
+}
+
 // One workgroup (chunk `blk` of `nblk`) of one iteration of one pair.  GICP: the plane-to-plane body (cfg.method == 2);
 // the other two methods share the instantiation they always had.
 template <bool GICP>
 __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) {
-  __shared__ double s_w[4][QTR_ICP_NT];
   __shared__ double s_S[QTR_ICP_NT];
-  __shared__ int s_last;
   const QtrIcpState* st = v.st;
   if (st->stop) return;  // (uniform: written by an earlier launch)
   double T[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) T[k] = st->T[k];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i = blk * QTR_ICP_CHUNK + tid;
+  const int i = blk * QTR_ICP_CHUNK + threadIdx.x;
   double o[QTR_ICP_NT];
 #pragma unroll
   for (int k = 0; k < QTR_ICP_NT; ++k) o[k] = 0.0;
@@ -214,44 +259,9 @@ __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) 
       }
     }
   }
-  // fixed-shape sum: the shfl_down fold inside each wave (qtr_icp_fold64), then (w0 + w1) + (w2 + w3)
-#pragma unroll
-  for (int k = 0; k < QTR_ICP_T_CNT + 1; ++k) {
-    double x = o[k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) x = x + icp_shfl_down(x, off);
-    if (lane == 0) s_w[wave][k] = x;
-  }
-  __syncthreads();
-  if (tid < QTR_ICP_T_CNT + 1) {
-    const double w4[4] = {s_w[0][tid], s_w[1][tid], s_w[2][tid], s_w[3][tid]};
-    const double c = qtr_icp_chunk_sum(w4);
-    __hip_atomic_store((unsigned long long*)(v.partials + (size_t)blk * QTR_ICP_NT + tid),
-                       (unsigned long long)__double_as_longlong(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned done = __hip_atomic_fetch_add(v.ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = (done == (unsigned)nblk - 1) ? 1 : 0;
-  }
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  if (tid < QTR_ICP_NT) {
-    double acc = 0.0;
-    if (tid < QTR_ICP_T_CNT + 1) {
-      acc = __longlong_as_double((long long)__hip_atomic_load((unsigned long long*)(v.partials + tid), __ATOMIC_RELAXED,
-                                                              __HIP_MEMORY_SCOPE_AGENT));
-      for (int c = 1; c < nblk; ++c)
-        acc = acc + __longlong_as_double((long long)__hip_atomic_load(
-                        (unsigned long long*)(v.partials + (size_t)c * QTR_ICP_NT + tid), __ATOMIC_RELAXED,
-                        __HIP_MEMORY_SCOPE_AGENT));
-    }
-    s_S[tid] = acc;
-  }
-  __syncthreads();
-  if (tid == 0) {
+  if (!icp_reduce_tail<QTR_ICP_T_CNT + 1, QTR_ICP_NT>(o, v.partials, v.ticket, blk, nblk, s_S)) return;
+  if (threadIdx.x == 0) {
+    for (int k = QTR_ICP_T_CNT + 1; k < QTR_ICP_NT; ++k) s_S[k] = 0.0;  // (the padding terms)
     QtrIcpState s = *v.st;
     double* tr = (s.iterations < v.cfg.max_iterations) ? v.trace + (size_t)s.iterations * 18 : nullptr;
     qtr_icp_step(&v.cfg, s_S, &s, tr);
@@ -273,14 +283,10 @@ __global__ __launch_bounds__(64) void k_icp_box_init_group(ViewExt<IcpView> x) {
   if (threadIdx.x == 0) __hip_atomic_store(v.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// k_icp_bbox per pair, folded in LDS first; the pair's last workgroup (ticket) mails the box to the host
-// (MAIL_ICP_BOX, then MAIL_SEQ_ICP_BOX = seqs[pair]) and leaves the ticket at zero
-__global__ __launch_bounds__(256) void k_icp_bbox_group(ViewExt<IcpView> x, const int* __restrict__ seqs) {
-  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
-  const int nblk = (v.nt + 255) / 256;
-  if ((int)blockIdx.x >= nblk) return;
+// k_icp_bbox for the 256 target points of workgroup blockIdx.x of one pair, folded in LDS first and merged into v.bbox.
+// Called by every thread of the workgroup (the caller's early return for workgroups past the pair's end is block-uniform).
+__device__ __forceinline__ void d_icp_bbox_fold(const IcpView& v) {
   __shared__ int s_bb[6];
-  __shared__ int s_last;
   if (threadIdx.x < 6) s_bb[threadIdx.x] = threadIdx.x < 3 ? 0x7fffffff : (int)0x80000000;
   __syncthreads();
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -298,6 +304,16 @@ __global__ __launch_bounds__(256) void k_icp_bbox_group(ViewExt<IcpView> x, cons
   __syncthreads();
   if (threadIdx.x < 3) atomicMin(v.bbox + threadIdx.x, s_bb[threadIdx.x]);
   else if (threadIdx.x < 6) atomicMax(v.bbox + threadIdx.x, s_bb[threadIdx.x]);
+}
+
+// d_icp_bbox_fold per pair; the pair's last workgroup (ticket) mails the box to the host
+// (MAIL_ICP_BOX, then MAIL_SEQ_ICP_BOX = seqs[pair]) and leaves the ticket at zero
+__global__ __launch_bounds__(256) void k_icp_bbox_group(ViewExt<IcpView> x, const int* __restrict__ seqs) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  const int nblk = (v.nt + 255) / 256;
+  if ((int)blockIdx.x >= nblk) return;
+  __shared__ int s_last;
+  d_icp_bbox_fold(v);
   __threadfence();
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -443,6 +459,89 @@ static void icp_free(IcpBufs& B) {
   if (B.cells) (void)hipFree(B.cells);
   if (B.h_state) (void)hipHostFree(B.h_state);
   B = IcpBufs{};
+}
+
+static QtrIcpCfg icp_cfg_of(const qtr_icp_params* prm) {
+  QtrIcpCfg c;
+  c.max_d2 = prm->max_correspondence_distance * prm->max_correspondence_distance;
+  c.trans_eps = prm->transformation_epsilon;
+  c.fit_eps = prm->euclidean_fitness_epsilon;
+  c.max_iterations = prm->max_iterations;
+  c.method = prm->method;
+  c.min_corr = prm->min_correspondences > 0 ? prm->min_correspondences
+               : prm->method == QTR_ICP_POINT_TO_PLANE ? 6
+               : prm->method == QTR_ICP_PLANE_TO_PLANE ? 4  // (pcl GICP's min_number_correspondences_)
+                                                       : 3;
+  c.pad = 0;
+  return c;
+}
+
+// The cell grid of a target box (6 order-preserving encodings, k_icp_bbox): cells a little larger than the correspondence
+// distance (a rounding of the cell index cannot hide a point in reach); a grid of more than cap_cells cells takes larger
+// ones.  Any cell >= the distance finds the same nearest neighbour (ties go to the lowest index), so the grid's shape does
+// not change a result.  false: no finite target point; the view then carries the empty grid (ncell = 0), in which nothing
+// is searched.
+static bool icp_grid_of(IcpView& v, const int* bbox, double max_d, int cap_cells) {
+  if (bbox[0] > bbox[3]) {
+    v.ncell = v.dims[0] = v.dims[1] = v.dims[2] = 0;
+    v.mn[0] = v.mn[1] = v.mn[2] = 0.0;
+    v.cell = 1.0;
+    return false;
+  }
+  double mx[3];
+  for (int a = 0; a < 3; ++a) {
+    v.mn[a] = (double)icp_dec(bbox[a]);
+    mx[a] = (double)icp_dec(bbox[3 + a]);
+  }
+  double cell = max_d * 1.001;
+  double nc = 0;
+  for (;;) {
+    nc = 1;
+    for (int a = 0; a < 3; ++a) nc *= floor((mx[a] - v.mn[a]) / cell) + 1.0;
+    if (nc <= (double)cap_cells) break;
+    cell *= 1.25;
+  }
+  v.cell = cell;
+  for (int a = 0; a < 3; ++a) v.dims[a] = (int)(floor((mx[a] - v.mn[a]) / cell) + 1.0);
+  v.ncell = v.dims[0] * v.dims[1] * v.dims[2];
+  return true;
+}
+
+static void icp_result_from(qtr_icp_result* res, const QtrIcpState& st) {
+  res->valid = st.valid;
+  res->converged = st.converged;
+  res->stop_reason = st.reason;
+  res->iterations = st.iterations;
+  res->n_corr = st.n_corr;
+  for (int k = 0; k < 16; ++k) res->T[k] = st.T[k];
+  res->fitness = st.fitness;
+  res->rmse = st.rmse;
+}
+
+// ---- single-pair launches (icp_device and the single evaluations, capi.hip) ----------------------------------------------
+// the box of the finite target points into v.bbox; h_bbox: 6 pinned ints, which the caller reads the box back into
+static hipError_t icp_box_enqueue(const IcpView& v, int* h_bbox, hipStream_t st) {
+  for (int a = 0; a < 3; ++a) {
+    h_bbox[a] = 0x7fffffff;
+    h_bbox[3 + a] = (int)0x80000000;
+  }
+  const hipError_t e = hipMemcpyAsync(v.bbox, h_bbox, 24, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return e;
+  if (v.nt > 0) hipLaunchKernelGGL(k_icp_bbox, dim3(qtr_div_up(v.nt, 256)), dim3(256), 0, st, v);
+  return hipGetLastError();
+}
+
+// the cell grid of the view (it carries its grid now: icp_grid_of) and the initial state
+static hipError_t icp_grid_enqueue(const IcpView& v, const QtrIcpState& init, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(v.cell_cnt, 0, (size_t)(v.ncell + 1) * 4, st);
+  if (e != hipSuccess) return e;
+  if (v.nt > 0) {
+    hipLaunchKernelGGL(k_icp_count, dim3(qtr_div_up(v.nt, 256)), dim3(256), 0, st, v);
+    if ((e = exclusive_scan_i32(v.cell_cnt, v.cell_start, v.ncell, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_icp_place, dim3(qtr_div_up(v.nt, 256)), dim3(256), 0, st, v);
+  }
+  hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, v, init);
+  return hipGetLastError();
 }
 
 // ---- grouped launches (the lane's refine phase, capi.hip) ---------------------------------------------------------------
