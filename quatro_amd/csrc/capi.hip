@@ -67,12 +67,15 @@ struct Slot {
   KfGatherMember* merge_dev = nullptr;  // (QTR_SUBMAP_MAX_KEYFRAMES records each, allocated on the slot's first merge)
 };
 
+// What a batch lane is waiting for: the mail of the chain it enqueued last (lane_poll).
+enum LanePhase { LANE_IDLE = 0, LANE_VOXELS, LANE_MATCH, LANE_SOLVE, LANE_REFINE_BOXES, LANE_REFINE_ITER };
+
 // One lane of the batch driver (qtr_submit_batch): a contiguous group of slots stepped through the three launch
 // chains in lockstep on the first slot's streams.
 struct Lane {
   int first_slot = 0, cap = 0;  // slots [first_slot, first_slot + cap)
   ViewStage stage;              // views of the group (pinned host + device)
-  int phase = 0;                // 0 idle, 1 voxelise pending, 2 matching pending, 3 solver pending, 4-5 refine pending
+  LanePhase phase = LANE_IDLE;
   int first_pair = 0, count = 0;  // pairs [first_pair, first_pair + count) of the job are on this lane
   std::vector<int> active;      // indices g (0..count) of the pairs still alive after each chain's checks
   std::vector<int> ns, nt, L;   // per g
@@ -81,7 +84,7 @@ struct Lane {
   std::vector<const float4*> raw_s, raw_t;  // per g: the clouds the voxel grid read (device pointers) and their sizes
   std::vector<int> Ps, Pt;
   bool long_lists = false;      // the chunk's FPFH chain included k2_neighbors_big
-  // refine phase (qtr_submit_batch_refine): 4 target boxes pending, 5 iterations pending; ln.active = the refining pairs
+  // refine phases (qtr_submit_batch_refine): ln.active = the refining pairs
   std::vector<IcpView> iv;      // per position in ln.active: the pair's ICP view (its slot's arena, its clouds, its grid)
   const IcpView* ref_views = nullptr;  // the same views in the stage (device)
   int ref_it = 0, ref_nchunk = 1;      // iterations enqueued so far; the group's widest iteration launch
@@ -137,7 +140,7 @@ struct qtr_handle {
   qtr_pw_params pre_pw;     // segmentation in front of the voxel grid)
   qtr_ip_params pre_ip;
   std::atomic<bool> long_lists{false};  // some cloud of the whole-path entry points had a point with more than QTR_KMAX
-                            // neighbours: from then on their FPFH chains include k2_neighbors_big (see front_device); written
+                            // neighbours: from then on their FPFH chains include k2_neighbors_big (lists_verdict); written
                             // by whichever slot call meets such a cloud first (calls from several threads)
   // LIVE host threads that have run a back-end chain on this handle (InFlight): the block outlives the handle as long as a
   // thread still holds it, so a thread that ends after qtr_destroy can still take itself off the count
@@ -731,6 +734,16 @@ static void compute_times(Slot& s) {
   s.times_pending = 0;
 }
 
+// the stage times of a call that is ONE stage: the slot's events 0 -> 1, into `field` (null: none) and the total
+static void times_one_stage(Slot& s, float qtr_stage_times::*field) {
+  float ms = 0;
+  s.times_pending = 0;
+  s.times = qtr_stage_times{};
+  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) != hipSuccess) return;
+  s.times.total = ms;
+  if (field) s.times.*field = ms;
+}
+
 // The long-list arenas of a slot's two clouds, allocated on first need: voxel-grid centroids at the demo's leaf never have
 // more than QTR_KMAX neighbours, so most handles never pay for them.
 static int ensure_long_arenas(qtr_handle* h, Slot& s) {
@@ -783,6 +796,13 @@ static int check_params(qtr_handle* h, const qtr_params* prm) {
     return QTR_ERR_BAD_ARG;
   }
   return QTR_OK;
+}
+
+// the back end's bound on the correspondences it is handed
+static int check_max_corr(qtr_handle* h, int L) {
+  if (L <= h->lim.max_corr) return QTR_OK;
+  snprintf(h->err, sizeof(h->err), "L=%d exceeds max_corr=%d", L, h->lim.max_corr);
+  return QTR_ERR_CAPACITY;
 }
 
 // PMC_EXACT after the heuristic has finished (state `hs` = the device SolverState as the host last saw it): proves the
@@ -917,6 +937,58 @@ struct InFlight {
   }
 };
 
+// What follows the solver's mail for one pair (k_finalize left the record and the state in the slot's mailbox): more clique
+// rounds when the state says so (rare), PMC_EXACT's search and a second estimate when it found a larger clique.  Everything
+// is enqueued on `st`, and s.stream must BE `st` while this runs (wait_mail's liveness check and exact_phase look at it:
+// the batch lanes swap it); record_ev4: the end of each follow-up chain is the call's s.ev[4].
+static int solve_followup(qtr_handle* h, Slot& s, const float4* c_src, const float4* c_tgt, int L, const qtr_params* prm,
+                          hipStream_t st, bool record_ev4) {
+  if (L <= 0) return QTR_OK;
+  const SolverState* ms = (const SolverState*)(s.mail + MAIL_SOLVER + 64);
+  if (!ms->done) {
+    s.sb.mail_seq = ++s.seq;
+    QTR_HIP_TRY(h, solver_continue(s.sb, c_src, c_tgt, L, *prm, st, s.pinned_i32 + 128, ms->redo_cores));
+    if (record_ev4) QTR_HIP_TRY(h, hipEventRecord(s.ev[4], st));
+    QTR_TRY(wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq));
+  }
+  if (prm->inlier_selection_mode != QTR_INLIER_PMC_EXACT) return QTR_OK;
+  SolverState hs;
+  memcpy(&hs, ms, sizeof(hs));
+  bool improved = false;
+  QTR_TRY(exact_phase(h, s, L, hs, &improved, prm->max_clique_time_limit));
+  if (!improved) return QTR_OK;
+  s.sb.mail_seq = ++s.seq;  // estimate again from the larger clique
+  QTR_HIP_TRY(h, solver_refinalize(s.sb, c_src, c_tgt, L, *prm, st));
+  if (record_ev4) QTR_HIP_TRY(h, hipEventRecord(s.ev[4], st));
+  return wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq);
+}
+
+// the result record out of the slot's mailbox; the counts the front end wrote into *res stay
+static void result_from_mail(const Slot& s, qtr_result* res) {
+  const int keep_ns = res->n_src, keep_nt = res->n_tgt, keep_nc = res->n_corr;
+  memcpy(res, s.mail + MAIL_SOLVER, sizeof(qtr_result));
+  res->n_src = keep_ns;
+  res->n_tgt = keep_nt;
+  res->n_corr = keep_nc;
+}
+
+// The caller's n correspondences where the back end reads them: device pointers as they are, host clouds copied into the
+// slot's matched-cloud buffers on `st` (the lanes: lead.stream).  Whoever runs a front end on the slot stages BEHIND it:
+// its matcher writes m_src / m_tgt.
+static int corr_stage(qtr_handle* h, Slot& s, const float* src4, const float* tgt4, int n, int mem, hipStream_t st,
+                      const float4** cs, const float4** ct) {
+  *cs = (const float4*)src4;
+  *ct = (const float4*)tgt4;
+  if (mem != QTR_MEM_HOST) return QTR_OK;
+  if (n > 0) {
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.m_src, src4, (size_t)n * 16, hipMemcpyHostToDevice, st));
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.m_tgt, tgt4, (size_t)n * 16, hipMemcpyHostToDevice, st));
+  }
+  *cs = s.m_src;
+  *ct = s.m_tgt;
+  return QTR_OK;
+}
+
 // Runs the back end on device-resident matched clouds and brings the result record to the host.
 static int solve_device(qtr_handle* h, Slot& s, const float4* d_src, const float4* d_tgt, int L, const qtr_params* prm,
                         qtr_result* res, bool reset_done = false) {
@@ -929,32 +1001,9 @@ static int solve_device(qtr_handle* h, Slot& s, const float4* d_src, const float
   QTR_HIP_TRY(h, solver_enqueue(s.sb, d_src, d_tgt, L, *prm, s.stream, s.pinned_i32, h->stage_events ? s.ev[2] : nullptr,
                                 h->stage_events ? s.ev[3] : nullptr, reset_done));
   if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[4], s.stream));
-  QTR_TRY(wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq));  // k_finalize left the record and the state in the mailbox
-  if (L > 0 && !((const SolverState*)(s.mail + MAIL_SOLVER + 64))->done) {  // rare: more clique rounds needed
-    s.sb.mail_seq = ++s.seq;
-    QTR_HIP_TRY(h, solver_continue(s.sb, d_src, d_tgt, L, *prm, s.stream, s.pinned_i32 + 128,
-                                   ((const SolverState*)(s.mail + MAIL_SOLVER + 64))->redo_cores));
-    if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[4], s.stream));
-    QTR_TRY(wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq));
-  }
-  if (L > 0 && prm->inlier_selection_mode == QTR_INLIER_PMC_EXACT) {
-    SolverState hs;
-    memcpy(&hs, s.mail + MAIL_SOLVER + 64, sizeof(hs));
-    bool improved = false;
-    QTR_TRY(exact_phase(h, s, L, hs, &improved, prm->max_clique_time_limit));
-    if (improved) {  // estimate again from the larger clique
-      s.sb.mail_seq = ++s.seq;
-      QTR_HIP_TRY(h, solver_refinalize(s.sb, d_src, d_tgt, L, *prm, s.stream));
-      if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[4], s.stream));
-      QTR_TRY(wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq));
-    }
-  }
-  memcpy(s.pinned_res, s.mail + MAIL_SOLVER, sizeof(qtr_result));
-  const int keep_ns = res->n_src, keep_nt = res->n_tgt, keep_nc = res->n_corr;
-  *res = *s.pinned_res;
-  res->n_src = keep_ns;
-  res->n_tgt = keep_nt;
-  res->n_corr = keep_nc;
+  QTR_TRY(wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq));
+  QTR_TRY(solve_followup(h, s, d_src, d_tgt, L, prm, s.stream, h->stage_events != 0));
+  result_from_mail(s, res);
   return res->status;
 }
 
@@ -989,22 +1038,14 @@ int qtr_solve(qtr_handle* h, int slot, const float* src4, const float* tgt4, int
     snprintf(h->err, sizeof(h->err), "bad input clouds");
     return res->status = QTR_ERR_BAD_ARG;
   }
-  if (L > h->lim.max_corr) {
-    snprintf(h->err, sizeof(h->err), "L=%d exceeds max_corr=%d", L, h->lim.max_corr);
-    return res->status = QTR_ERR_CAPACITY;
-  }
+  if ((rc = check_max_corr(h, L)) != QTR_OK) return res->status = rc;
   QTR_HIP_TRY(h, hipSetDevice(h->device));
-  const float4 *d_src = (const float4*)src4, *d_tgt = (const float4*)tgt4;
+  const float4 *d_src = nullptr, *d_tgt = nullptr;
   // (an event record is a marker packet the queue has to retire before the next launch starts: with the stage events
   // off a call records none at all, and every field of qtr_stage_times reads 0)
   const bool ev_on = h->stage_events != 0;
   if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev[0], s.stream));
-  if (mem == QTR_MEM_HOST && L > 0) {
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.m_src, src4, (size_t)L * 16, hipMemcpyHostToDevice, s.stream));
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.m_tgt, tgt4, (size_t)L * 16, hipMemcpyHostToDevice, s.stream));
-    d_src = s.m_src;
-    d_tgt = s.m_tgt;
-  }
+  QTR_TRY(corr_stage(h, s, src4, tgt4, L, mem, s.stream, &d_src, &d_tgt));
   if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
   res->n_corr = L;
   rc = solve_device(h, s, d_src, d_tgt, L, prm, res);
@@ -1026,10 +1067,7 @@ int qtr_max_clique(qtr_handle* h, int slot, const unsigned long long* adj, int L
     snprintf(h->err, sizeof(h->err), "clique solver mode %d not supported", mode);
     return QTR_ERR_UNSUPPORTED;
   }
-  if (L > h->lim.max_corr) {
-    snprintf(h->err, sizeof(h->err), "L=%d exceeds max_corr=%d", L, h->lim.max_corr);
-    return QTR_ERR_CAPACITY;
-  }
+  QTR_TRY(check_max_corr(h, L));
   if (L == 0) return QTR_OK;
   QTR_HIP_TRY(h, hipSetDevice(h->device));
   const int W = (L + 63) / 64;
@@ -1348,10 +1386,7 @@ int qtr_patchwork(qtr_handle* h, int slot, const float* xyz4, int P, const qtr_p
   if (ground_xyzw && ng > 0) QTR_HIP_TRY(h, hipMemcpyAsync(ground_xyzw, s.pwb.out_g, (size_t)ng * 16, kout, s.stream));
   if (nonground_xyzw && nn > 0) QTR_HIP_TRY(h, hipMemcpyAsync(nonground_xyzw, s.pwb.out_n, (size_t)nn * 16, kout, s.stream));
   QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
-  float ms = 0;
-  s.times_pending = 0;
-  s.times = qtr_stage_times{};
-  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.times.total = ms;
+  times_one_stage(s, nullptr);
   return QTR_OK;
 }
 
@@ -1466,10 +1501,7 @@ int qtr_segment_cloud(qtr_handle* h, int slot, const float* xyz4, int P, const q
   if (outl_xyzi && no > 0) QTR_HIP_TRY(h, hipMemcpyAsync(outl_xyzi, s.seg.out_outl, (size_t)no * 16, kout, s.stream));
   if (labelmat) QTR_HIP_TRY(h, hipMemcpyAsync(labelmat, s.seg.labelmat, (size_t)NP * 4, hipMemcpyDeviceToHost, s.stream));
   QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
-  float ms = 0;
-  s.times_pending = 0;
-  s.times = qtr_stage_times{};
-  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.times.total = ms;
+  times_one_stage(s, nullptr);
   return QTR_OK;
 }
 
@@ -1549,18 +1581,16 @@ int qtr_voxelize(qtr_handle* h, int slot, const float* xyz4, int P, float leaf, 
   QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
   QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32, cb.counts, 16 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
   QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
-  int n = s.pinned_i32[CNT_NVOX];
-  if (n < 0 || s.pinned_i32[CNT_VOX_TAILERR]) {  // (see front_device; the sticky word: ANY tile gave up, not only the last)
+  const VoxVerdict v = vox_verdict(s.pinned_i32, P, h->lim.max_voxels);
+  if (v.reason == VOX_TIMEOUT || s.pinned_i32[CNT_VOX_TAILERR]) {  // (the sticky word: ANY tile gave up, not only the last)
     snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out");
     return QTR_ERR_HIP;
   }
-  const bool passthrough = s.pinned_i32[CNT_VOX_OVERFLOW] != 0;
-  const float4* d_out = cb.vox;
-  if (passthrough) {  // PCL: "Leaf size is too small" -> output = input
-    n = P;
-    d_out = d_in;
-  }
-  if (n > h->lim.max_voxels && !passthrough) {
+  // (a cloud that passed through goes out as it came in, whatever its size, and an empty result is no error here: the
+  // bound below is the caller's capacity)
+  const int n = v.n;
+  const float4* d_out = v.passed ? d_in : cb.vox;
+  if (v.reason == VOX_TOO_MANY) {
     snprintf(h->err, sizeof(h->err), "voxel count %d exceeds max_voxels=%d", n, h->lim.max_voxels);
     return QTR_ERR_CAPACITY;
   }
@@ -1573,10 +1603,7 @@ int qtr_voxelize(qtr_handle* h, int slot, const float* xyz4, int P, float leaf, 
                                 mem == QTR_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s.stream));
   QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
   *n_out = n;
-  float ms = 0;
-  s.times_pending = 0;
-  s.times = qtr_stage_times{};
-  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.times.voxelize = s.times.total = ms;
+  times_one_stage(s, &qtr_stage_times::voxelize);
   return QTR_OK;
 }
 
@@ -1621,10 +1648,7 @@ int qtr_fpfh(qtr_handle* h, int slot, const float* xyz4, int n, float r_normal, 
   if (normals4) QTR_HIP_TRY(h, hipMemcpyAsync(normals4, cb.normals, (size_t)n * 16, kout, s.stream));
   QTR_HIP_TRY(h, hipMemcpyAsync(desc33, cb.fpfh, (size_t)n * 33 * 4, kout, s.stream));
   QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
-  float ms = 0;
-  s.times_pending = 0;
-  s.times = qtr_stage_times{};
-  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.times.fpfh = s.times.total = ms;
+  times_one_stage(s, &qtr_stage_times::fpfh);
   return QTR_OK;
 }
 
@@ -1689,10 +1713,7 @@ int qtr_match(qtr_handle* h, int slot, const float* xyz4_s, int n_s, const float
   }
   if (L > 0) QTR_HIP_TRY(h, hipMemcpyAsync(corr2, s.fb.corr, (size_t)L * 8, kout, s.stream));
   QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
-  float ms = 0;
-  s.times_pending = 0;
-  s.times = qtr_stage_times{};
-  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.times.match = s.times.total = ms;
+  times_one_stage(s, &qtr_stage_times::match);
   fill_nn_times(s);
   return QTR_OK;
 }
@@ -1741,11 +1762,7 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
   {
     const float4* raws[2] = {d_s, d_t};
     const int Ps2[2] = {Ps, Pt};
-    // The voxel sort needs ceil(bits / 8) radix passes, bits = significant bits of the grid's cell index — known on the
-    // device only.  A launch that returns at once still costs ~5 us on this chain, so the driver launches what the
-    // previous pair on this slot needed (3 for a lidar scan at 0.3 m) and checks: if this pair needs more, the stage
-    // runs again with enough (first call on a slot: 4, which always suffices).
-    for (int attempt = 0;; ++attempt) {
+    for (int attempt = 0;; ++attempt) {  // (the voxel sort's radix passes are speculated: vox_passes_next)
       const int launched = s.fb.vox_passes;
       s.fb.mail_seq = ++s.seq;
       QTR_HIP_TRY(h, voxelize_enqueue(s.fb, 2, raws, Ps2, fp->voxel_size, s.stream, launched, fp->fpfh_radius * 1.001f));
@@ -1764,53 +1781,28 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
       if ((rc = wait_mail(h, s, MAIL_SEQ_VOX0, s.seq)) != QTR_OK || (rc = wait_mail(h, s, MAIL_SEQ_VOX1, s.seq)) != QTR_OK)
         return fail_drained(rc);
       const int bits = std::max(s.mail[MAIL_VOX0 + CNT_SORT_BITS], s.mail[MAIL_VOX1 + CNT_SORT_BITS]);
-      const int needed = std::min(4, std::max(1, (bits + 7) / 8));
-      if (needed > launched && attempt == 0) {  // under-launched: the centroids are garbage, run the stage again
-        s.fb.vox_passes = 4;
-        s.fb.vox_fewer = 0;
-        continue;
-      }
-      if (needed < launched) {  // step down only after a run of calls that agree (alternating scenes would thrash)
-        if (++s.fb.vox_fewer >= 4) {
-          s.fb.vox_passes = needed;
-          s.fb.vox_fewer = 0;
-        }
-      } else {
-        s.fb.vox_fewer = 0;
-      }
-      break;
+      if (!vox_passes_next(s.fb.vox_passes, s.fb.vox_fewer, bits, launched, attempt)) break;
     }
   }
-  int ns = s.mail[MAIL_VOX0 + CNT_NVOX], nt = s.mail[MAIL_VOX1 + CNT_NVOX];
-  bool passed_through = false;
-  if (ns < 0 || nt < 0) {  // k2_vox_centroids: a tile never published its count (bounded look-back): nothing usable was written
+  // (a cloud that passes through is BASELINE's dense mode — "no voxel downsample" — through the whole-path entry; an empty
+  // voxel result is not looked at on this path)
+  const VoxVerdict vs = vox_verdict(s.mail + MAIL_VOX0, Ps, h->lim.max_voxels),
+                   vt = vox_verdict(s.mail + MAIL_VOX1, Pt, h->lim.max_voxels);
+  const int ns = vs.n, nt = vt.n;
+  const bool passed_through = vs.passed || vt.passed;
+  if (vs.reason == VOX_TIMEOUT || vt.reason == VOX_TIMEOUT) {
     snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out");
     return fail_drained(QTR_ERR_HIP);
   }
-  {
-    // pcl::VoxelGrid::applyFilter: "Leaf size is too small for the input dataset. Integer indices would overflow" ->
-    // output = input.  So does `voxelize` of the reference (include/quatro.hpp:49-68 calls it unconditionally), and the
-    // demo goes on with the cloud as it is — BASELINE's dense mode ("no voxel downsample") through the whole-path entry.
-    const bool pass[2] = {s.mail[MAIL_VOX0 + CNT_VOX_OVERFLOW] != 0, s.mail[MAIL_VOX1 + CNT_VOX_OVERFLOW] != 0};
-    if (pass[0] || pass[1]) {
-      passed_through = true;
-      if ((pass[0] && Ps > h->lim.max_voxels) || (pass[1] && Pt > h->lim.max_voxels)) {
-        snprintf(h->err, sizeof(h->err), "voxel grid would overflow int32 (leaf too small): the cloud passes through as it "
-                 "is (pcl::VoxelGrid), and its %d / %d points exceed max_voxels=%d", Ps, Pt, h->lim.max_voxels);
-        return fail_drained(QTR_ERR_CAPACITY);
-      }
-      if (pass[0]) {
-        QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[0].vox, d_s, (size_t)Ps * 16, hipMemcpyDeviceToDevice, s.stream));
-        ns = Ps;
-      }
-      if (pass[1]) {
-        QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[1].vox, d_t, (size_t)Pt * 16, hipMemcpyDeviceToDevice, s.stream));
-        nt = Pt;
-      }
-      QTR_HIP_TRY(h, hipEventRecord(s.ev_vox, s.stream));  // (the second stream's means wait for the clouds)
-    }
+  if (vs.reason == VOX_PASS_TOO_LARGE || vt.reason == VOX_PASS_TOO_LARGE) {
+    snprintf(h->err, sizeof(h->err), "voxel grid would overflow int32 (leaf too small): the cloud passes through as it "
+             "is (pcl::VoxelGrid), and its %d / %d points exceed max_voxels=%d", Ps, Pt, h->lim.max_voxels);
+    return fail_drained(QTR_ERR_CAPACITY);
   }
-  if (ns > h->lim.max_voxels || nt > h->lim.max_voxels) {
+  if (vs.passed) QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[0].vox, d_s, (size_t)Ps * 16, hipMemcpyDeviceToDevice, s.stream));
+  if (vt.passed) QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[1].vox, d_t, (size_t)Pt * 16, hipMemcpyDeviceToDevice, s.stream));
+  if (passed_through) QTR_HIP_TRY(h, hipEventRecord(s.ev_vox, s.stream));  // (the second stream's means wait for the clouds)
+  if (vs.reason == VOX_TOO_MANY || vt.reason == VOX_TOO_MANY) {
     snprintf(h->err, sizeof(h->err), "voxel count (%d,%d) exceeds max_voxels=%d", ns, nt, h->lim.max_voxels);
     return fail_drained(QTR_ERR_CAPACITY);
   }
@@ -1842,32 +1834,24 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
   int L = 0;
   rc = match_device(h, s, ns, nt, fp, &L, true, true, corr_given);
   if (rc != QTR_OK) return rc;
-  if (s.mail[MAIL_CNT0 + CNT_VOX_TAILERR] || s.mail[MAIL_CNT1 + CNT_VOX_TAILERR]) {
-    // a MIDDLE tile of k2_vox_centroids gave up its look-back (its centroids were never written) although the last tile's
-    // came out whole and mailed a valid count: the counter lines the matcher's tail mails after that kernel carry the word
-    snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out in a tile (centroids incomplete)");
-    return QTR_ERR_HIP;
-  }
-  if (s.mail[MAIL_CNT0 + CNT_NBR_CAPACITY] || s.mail[MAIL_CNT1 + CNT_NBR_CAPACITY]) {
-    snprintf(h->err, sizeof(h->err), "radius-neighbour lists longer than %d entries (longest %d / %d) exceed the long-list "
-             "arena: qtr_limits.max_long_neighbors is %d", QTR_KMAX, s.mail[MAIL_CNT0 + CNT_KMAX],
-             s.mail[MAIL_CNT1 + CNT_KMAX], h->lim.max_long_neighbors);
-    return QTR_ERR_CAPACITY;
-  }
-  if (!h->long_lists && (s.mail[MAIL_CNT0 + CNT_NBR_OVERFLOW] || s.mail[MAIL_CNT1 + CNT_NBR_OVERFLOW])) {
-    // A point with more than QTR_KMAX neighbours, and the chain ran without k2_neighbors_big (voxel-grid centroids at
-    // the demo's leaf never have that many, so the launch is left out until a cloud needs it): descriptors and matches
-    // of this call are not usable.  From now on the handle's chains include it; this pair goes round again.
-    h->long_lists = true;
-    return front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem, for_solver, ns_out, nt_out, L_out, corr_given);
+  switch (lists_verdict(s.mail + MAIL_CNT0, s.mail + MAIL_CNT1, h->long_lists)) {  // (the matcher's tail mails the lines)
+    case LISTS_TILE_ERROR:
+      snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out in a tile (centroids incomplete)");
+      return QTR_ERR_HIP;
+    case LISTS_CAPACITY:
+      snprintf(h->err, sizeof(h->err), "radius-neighbour lists longer than %d entries (longest %d / %d) exceed the long-list "
+               "arena: qtr_limits.max_long_neighbors is %d", QTR_KMAX, s.mail[MAIL_CNT0 + CNT_KMAX],
+               s.mail[MAIL_CNT1 + CNT_KMAX], h->lim.max_long_neighbors);
+      return QTR_ERR_CAPACITY;
+    case LISTS_NEED_LONG:  // from now on the handle's chains include k2_neighbors_big; this pair goes round again
+      h->long_lists = true;
+      return front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem, for_solver, ns_out, nt_out, L_out, corr_given);
+    case LISTS_OK: break;
   }
   *L_out = L;
   if (corr_given) return QTR_OK;
   s.last_L = L;
-  if (L > h->lim.max_corr) {
-    snprintf(h->err, sizeof(h->err), "L=%d exceeds max_corr=%d", L, h->lim.max_corr);
-    return QTR_ERR_CAPACITY;
-  }
+  QTR_TRY(check_max_corr(h, L));
   QTR_HIP_TRY(h, gather_matched_enqueue(s.fb, L, s.m_src, s.m_tgt, s.stream));
   if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[7], s.stream));
   return QTR_OK;
@@ -1880,23 +1864,24 @@ static void mark_registration(Slot& s, int rc, const qtr_result* res) {
   for (int k = 0; k < 16; ++k) s.reg_T[k] = res->T[k];
 }
 
-// The whole path on one slot.  mem_in: where the scans live; mem_out: where the index lists go.  corr_src / corr_tgt
-// (device pointers, n_corr >= 0): the back end runs on THESE matched clouds instead of the matcher's output (the batched
-// entry's "scans + pre-matched correspondences" pairs); n_corr < 0: the matcher's own correspondences.
+// The whole path on one slot.  mem_in: where the scans live; mem_out: where the index lists go and where the caller's
+// correspondences are.  corr_src / corr_tgt (n_corr >= 0): the back end runs on THESE matched clouds instead of the
+// matcher's output (qtr_register_pair_corr, the batched entry's "scans + pre-matched correspondences" pairs), staged behind
+// the front end, and the record's n_corr is n_corr whatever happens; *n_matched (may be null) then receives the matcher's
+// count (-1: its tail gave up — its list is not used).  n_corr < 0: the matcher's own correspondences.
 static int register_pair_impl(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, const float* tgt_raw4, int Pt,
                               const qtr_frontend_params* fp, const qtr_params* prm, qtr_result* res, int* clique,
-                              int* final_inliers, int cap, int mem_in, int mem_out, const float4* corr_src,
-                              const float4* corr_tgt, int n_corr) {
+                              int* final_inliers, int cap, int mem_in, int mem_out, const float* corr_src,
+                              const float* corr_tgt, int n_corr, int* n_matched = nullptr) {
+  const bool given = n_corr >= 0;
   int L = 0;
-  int rc = front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem_in, true, &res->n_src, &res->n_tgt, &L, n_corr >= 0);
-  res->n_corr = L;
+  int rc = front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem_in, true, &res->n_src, &res->n_tgt, &L, given);
+  if (n_matched) *n_matched = L;
+  res->n_corr = given ? n_corr : L;
   if (rc != QTR_OK) return res->status = rc;
-  if (n_corr >= 0) {
-    res->n_corr = n_corr;
-    rc = solve_device(h, s, corr_src, corr_tgt, n_corr, prm, res, true);
-  } else {
-    rc = solve_device(h, s, s.m_src, s.m_tgt, L, prm, res, true);
-  }
+  const float4 *cs = s.m_src, *ct = s.m_tgt;
+  if (given) QTR_TRY(corr_stage(h, s, corr_src, corr_tgt, n_corr, mem_out, s.stream, &cs, &ct));
+  rc = solve_device(h, s, cs, ct, res->n_corr, prm, res, true);
   if (rc != QTR_OK && rc != QTR_ERR_CLIQUE_TOO_SMALL) return rc;
   s.times_pending = h->stage_events ? 2 : 4;
   const int rc2 = copy_out_lists(h, s, res, clique, nullptr, final_inliers, cap, mem_out);
@@ -1937,23 +1922,8 @@ int qtr_register_pair_corr(qtr_handle* h, int slot, const float* src_raw4, int P
     snprintf(h->err, sizeof(h->err), "n_corr=%d exceeds max_corr=%d", n_corr, h->lim.max_corr);
     return res->status = QTR_ERR_CAPACITY;
   }
-  int Lm = 0;
-  rc = front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem, true, &res->n_src, &res->n_tgt, &Lm, true);
-  if (n_matched) *n_matched = Lm;  // (-1: the matcher's tail gave up — its list is not used here)
-  res->n_corr = n_corr;
-  if (rc != QTR_OK) return res->status = rc;
-  const float4 *cs = (const float4*)corr_src4, *ct = (const float4*)corr_tgt4;
-  if (mem == QTR_MEM_HOST && n_corr > 0) {  // (the matcher's own matched clouds in m_src / m_tgt are not needed: behind it)
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.m_src, corr_src4, (size_t)n_corr * 16, hipMemcpyHostToDevice, s.stream));
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.m_tgt, corr_tgt4, (size_t)n_corr * 16, hipMemcpyHostToDevice, s.stream));
-    cs = s.m_src;
-    ct = s.m_tgt;
-  }
-  rc = solve_device(h, s, cs, ct, n_corr, prm, res, true);
-  if (rc != QTR_OK && rc != QTR_ERR_CLIQUE_TOO_SMALL) return rc;
-  s.times_pending = h->stage_events ? 2 : 4;
-  const int rc2 = copy_out_lists(h, s, res, clique, nullptr, final_inliers, cap, mem);
-  if (rc2 != QTR_OK) return res->status = rc2;
+  rc = register_pair_impl(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, prm, res, clique, final_inliers, cap, mem, mem, corr_src4,
+                          corr_tgt4, n_corr, n_matched);
   mark_registration(s, rc, res);
   return rc;
 }
@@ -1991,7 +1961,7 @@ int qtr_feature_pair(qtr_handle* h, int slot, const float* src_raw4, int Ps, con
 // ------------------------------------------------------------------------------------------------
 // keyframes (keyframe.hip): one scan's front end, kept on the device
 // The one-cloud front end on cloud[0] of a slot: voxel grid -> mean -> FPFH chain with the matcher's per-descriptor
-// preparation, under front_device's rules (pass-through, radix-pass speculation, long_lists retry, capacity errors).  The
+// preparation, decided by the verdicts front_device uses (front_verdict.h).  The
 // counters a whole-path call receives in its matcher's mail are read back here: nothing runs a matcher.
 // What the one-cloud front end refuses before anything is enqueued.
 static int front_one_check(qtr_handle* h, bool have_cloud, int P, const qtr_frontend_params* fp) {
@@ -2015,54 +1985,36 @@ static int front_one_check(qtr_handle* h, bool have_cloud, int P, const qtr_fron
 static int front_one_chain(qtr_handle* h, Slot& s, const float4* d_raw, int P, const qtr_frontend_params* fp, int* n_out,
                            int* passed_out) {
   int rc = QTR_OK;
-  auto fail_drained = [&](int code) {  // (see front_device: the scan is not handed back while a kernel may still read it)
+  auto fail_drained = [&](int code) {  // (the scan is not handed back while a kernel may still read it)
     (void)hipStreamSynchronize(s.stream);
     return code;
   };
-  for (int attempt = 0;; ++attempt) {  // the voxel sort's radix passes are speculated as in front_device
+  for (int attempt = 0;; ++attempt) {  // (the voxel sort's radix passes are speculated: vox_passes_next)
     const int launched = s.fb.vox_passes;
     s.fb.mail_seq = ++s.seq;
     QTR_HIP_TRY(h, voxelize_enqueue(s.fb, 1, &d_raw, &P, fp->voxel_size, s.stream, launched, fp->fpfh_radius * 1.001f));
     if ((rc = wait_mail(h, s, MAIL_SEQ_VOX0, s.seq)) != QTR_OK) return fail_drained(rc);
-    const int needed = std::min(4, std::max(1, (s.mail[MAIL_VOX0 + CNT_SORT_BITS] + 7) / 8));
-    if (needed > launched && attempt == 0) {
-      s.fb.vox_passes = 4;
-      s.fb.vox_fewer = 0;
-      continue;
-    }
-    if (needed < launched) {
-      if (++s.fb.vox_fewer >= 4) {
-        s.fb.vox_passes = needed;
-        s.fb.vox_fewer = 0;
-      }
-    } else {
-      s.fb.vox_fewer = 0;
-    }
-    break;
+    if (!vox_passes_next(s.fb.vox_passes, s.fb.vox_fewer, s.mail[MAIL_VOX0 + CNT_SORT_BITS], launched, attempt)) break;
   }
-  int n = s.mail[MAIL_VOX0 + CNT_NVOX];
-  if (n < 0) {
-    snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out");
-    return fail_drained(QTR_ERR_HIP);
-  }
-  const bool pass = s.mail[MAIL_VOX0 + CNT_VOX_OVERFLOW] != 0;
-  if (pass) {  // pcl::VoxelGrid: the cloud passes through as it is (see front_device)
-    if (P > h->lim.max_voxels) {
+  const VoxVerdict v = vox_verdict(s.mail + MAIL_VOX0, P, h->lim.max_voxels);
+  const int n = v.n;
+  switch (v.reason) {
+    case VOX_TIMEOUT:
+      snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out");
+      return fail_drained(QTR_ERR_HIP);
+    case VOX_PASS_TOO_LARGE:
       snprintf(h->err, sizeof(h->err), "voxel grid would overflow int32 (leaf too small): the cloud passes through as it "
                "is (pcl::VoxelGrid), and its %d points exceed max_voxels=%d", P, h->lim.max_voxels);
       return fail_drained(QTR_ERR_CAPACITY);
-    }
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[0].vox, d_raw, (size_t)P * 16, hipMemcpyDeviceToDevice, s.stream));
-    n = P;
+    case VOX_TOO_MANY:
+      snprintf(h->err, sizeof(h->err), "voxel count %d exceeds max_voxels=%d", n, h->lim.max_voxels);
+      return fail_drained(QTR_ERR_CAPACITY);
+    case VOX_EMPTY:
+      snprintf(h->err, sizeof(h->err), "Invalid or empty point cloud dataset given!");
+      return fail_drained(QTR_ERR_BAD_ARG);
+    case VOX_OK: break;
   }
-  if (n > h->lim.max_voxels) {
-    snprintf(h->err, sizeof(h->err), "voxel count %d exceeds max_voxels=%d", n, h->lim.max_voxels);
-    return fail_drained(QTR_ERR_CAPACITY);
-  }
-  if (n <= 0) {
-    snprintf(h->err, sizeof(h->err), "Invalid or empty point cloud dataset given!");
-    return fail_drained(QTR_ERR_BAD_ARG);
-  }
+  if (v.passed) QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[0].vox, d_raw, (size_t)P * 16, hipMemcpyDeviceToDevice, s.stream));
   s.last_ns = s.last_n = n;
   s.last_nt = 0;
   QTR_HIP_TRY(h, mean_enqueue(s.fb, 0, 1, &n, s.stream));
@@ -2072,21 +2024,21 @@ static int front_one_chain(qtr_handle* h, Slot& s, const float4* d_raw, int P, c
                               cell_table_cells(ncell, ncell)));
   QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32, s.fb.cloud[0].counts, 16 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
   QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
-  if (s.pinned_i32[CNT_VOX_TAILERR]) {
-    snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out in a tile (centroids incomplete)");
-    return QTR_ERR_HIP;
-  }
-  if (s.pinned_i32[CNT_NBR_CAPACITY]) {
-    snprintf(h->err, sizeof(h->err), "radius-neighbour lists longer than %d entries (longest %d) exceed the long-list "
-             "arena: qtr_limits.max_long_neighbors is %d", QTR_KMAX, s.pinned_i32[CNT_KMAX], h->lim.max_long_neighbors);
-    return QTR_ERR_CAPACITY;
-  }
-  if (!h->long_lists && s.pinned_i32[CNT_NBR_OVERFLOW]) {  // (see front_device: the chain ran without k2_neighbors_big)
-    h->long_lists = true;
-    return front_one_chain(h, s, d_raw, P, fp, n_out, passed_out);  // (the input is where it was: nothing of the chain writes it)
+  switch (lists_verdict(s.pinned_i32, nullptr, h->long_lists)) {
+    case LISTS_TILE_ERROR:
+      snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out in a tile (centroids incomplete)");
+      return QTR_ERR_HIP;
+    case LISTS_CAPACITY:
+      snprintf(h->err, sizeof(h->err), "radius-neighbour lists longer than %d entries (longest %d) exceed the long-list "
+               "arena: qtr_limits.max_long_neighbors is %d", QTR_KMAX, s.pinned_i32[CNT_KMAX], h->lim.max_long_neighbors);
+      return QTR_ERR_CAPACITY;
+    case LISTS_NEED_LONG:  // (the input is where it was: nothing of the chain writes it)
+      h->long_lists = true;
+      return front_one_chain(h, s, d_raw, P, fp, n_out, passed_out);
+    case LISTS_OK: break;
   }
   *n_out = n;
-  *passed_out = pass ? 1 : 0;
+  *passed_out = v.passed ? 1 : 0;
   return QTR_OK;
 }
 
@@ -2558,10 +2510,7 @@ int qtr_register_keyframes(qtr_handle* h, int slot, const qtr_keyframe* kf_src, 
   res->n_corr = L;
   if (rc != QTR_OK) return res->status = rc;
   s.last_L = L;
-  if (L > h->lim.max_corr) {
-    snprintf(h->err, sizeof(h->err), "L=%d exceeds max_corr=%d", L, h->lim.max_corr);
-    return res->status = QTR_ERR_CAPACITY;
-  }
+  if ((rc = check_max_corr(h, L)) != QTR_OK) return res->status = rc;
   QTR_HIP_TRY(h, gather_matched_enqueue(s.fb, L, s.m_src, s.m_tgt, s.stream));
   if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[7], s.stream));
   rc = solve_device(h, s, s.m_src, s.m_tgt, L, prm, res, true);
@@ -2615,7 +2564,7 @@ static void batch_abort(qtr_handle* h) {
     Slot& lead = h->slots[ln.first_slot];
     (void)hipStreamSynchronize(lead.stream);
     (void)hipStreamSynchronize(lead.stream2);
-    ln.phase = 0;
+    ln.phase = LANE_IDLE;
   }
   (void)hipGetLastError();
   for (int i = 0; i < J.B; ++i) {
@@ -2664,14 +2613,107 @@ static int lane_enqueue_solver(qtr_handle* h, Lane& ln, const std::vector<int>& 
   solver_set_hca_share((int)h->lanes.size());  // the lanes' solver chains overlap: each keeps to its share of the device
   QTR_HIP_TRY(h, solver_enqueue_group(SB.data(), (int)SB.size(), srcs.data(), tgts.data(), Ls.data(), J.prm, &ln.stage,
                                       lead.stream));
-  ln.phase = 3;
+  ln.phase = LANE_SOLVE;
+  return QTR_OK;
+}
+
+// The demo's STEP 2 and 3 on raw sweeps (reference examples/run_global_registration.cpp:136-160): per scan
+// PatchWork::estimate_ground -> non-ground points -> ImageProjection::segmentCloud -> valid segments.  Both stages hand a
+// count to the next one through the host, so a scan is a chain of four host-visible steps — run for ALL pairs of the
+// chunk side by side, every pair on its own slot's stream and arenas (target first, then source: the two scans of a pair
+// share the slot), the host advancing whichever slot's step has finished.  (Rounds 2-3 ran them pair after pair with a
+// blocking read-back per step: a chunk of sixteen raw pairs waited 64 times.)  The valid segments land in the slot's
+// staging buffers, which are the voxel grid's input; the lane's stream waits for the copies, not the host.
+struct PreScan {
+  int stage = 0;  // 0 start, 1 ground segmentation of scan c in flight, 2 range-image stage in flight, 3 done
+  int c = 1;      // scan being processed: 1 target, then 0 source
+  int status = QTR_OK;
+  int n[2] = {0, 0};  // valid points of source / target
+};
+static int lane_preprocess(qtr_handle* h, Lane& ln, std::vector<PreScan>& pre) {
+  BatchJob& J = h->job;
+  Slot& lead = h->slots[ln.first_slot];
+  int open = 0;
+  for (int g = 0; g < ln.count; ++g) {
+    const qtr_pair_desc& pd = J.pairs[ln.first_pair + g];
+    const bool usable = pair_has_scans(pd) && pd.src_raw4 && pd.tgt_raw4 && pd.n_src > 0 && pd.n_tgt > 0 &&
+                        pd.n_src <= h->lim.max_points && pd.n_tgt <= h->lim.max_points;
+    if (!usable) pre[(size_t)g].stage = 3;  // (refused by the checks below, or a pair without scans)
+    else ++open;
+  }
+  unsigned long spins = 0;
+  while (open > 0) {
+    bool moved = false;
+    for (int g = 0; g < ln.count; ++g) {
+      PreScan& q = pre[(size_t)g];
+      if (q.stage == 3) continue;
+      const qtr_pair_desc& pd = J.pairs[ln.first_pair + g];
+      Slot& s = h->slots[ln.first_slot + g];
+      int rc = QTR_OK;
+      if (q.stage == 0) {
+        rc = pw_begin(h, s, q.c ? pd.tgt_raw4 : pd.src_raw4, q.c ? pd.n_tgt : pd.n_src, &h->pre_pw, J.mem);
+        q.stage = 1;
+        moved = true;
+      } else {
+        const hipError_t e = hipEventQuery(s.ev[1]);
+        if (e == hipErrorNotReady) continue;
+        if (e != hipSuccess) {
+          snprintf(h->err, sizeof(h->err), "batch pre-processing: %s", hipGetErrorString(e));
+          return QTR_ERR_HIP;
+        }
+        moved = true;
+        if (q.stage == 1) {  // ground removed: its non-ground points go through the range image
+          int ng = 0, nn = 0;
+          pw_end(s, &ng, &nn);
+          rc = seg_begin(h, s, (const float*)s.pwb.out_n, nn, &h->pre_ip, QTR_MEM_DEVICE);
+          q.stage = 2;
+        } else {  // valid segments known: into the staging buffer; next scan, or done
+          const int nv = s.pinned_i32[0];
+          q.n[q.c] = nv;
+          if (nv > h->lim.max_points) rc = QTR_ERR_CAPACITY;
+          else if (nv > 0)
+            // (on the slot's own stream: the next scan's stages, which reuse the buffers this copy reads, queue up behind it)
+            QTR_HIP_TRY(h, hipMemcpyAsync(q.c ? s.in_tgt : s.in_src, s.seg.out_valid, (size_t)nv * 16, hipMemcpyDeviceToDevice,
+                                          s.stream));
+          if (rc == QTR_OK && q.c == 1) {
+            q.c = 0;
+            q.stage = 0;
+          } else {
+            if (rc == QTR_OK) {  // the group's chain (lane stream) reads the staging buffers: it waits for this slot
+              QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
+              QTR_HIP_TRY(h, hipStreamWaitEvent(lead.stream, s.ev[1], 0));
+            }
+            q.stage = 3;
+            --open;
+          }
+        }
+      }
+      if (rc == QTR_ERR_HIP) return rc;
+      if (rc != QTR_OK && q.stage != 3) {  // this pair's own failure (capacity, a scan the stage refuses)
+        q.status = rc;
+        q.stage = 3;
+        --open;
+      } else if (rc != QTR_OK) {
+        q.status = rc;
+      }
+    }
+    if (!moved) {
+      __builtin_ia32_pause();
+      if ((++spins & 0xffffff) == 0) {  // nothing moved for a long while: a lost device must not hang the host
+        for (int g = 0; g < ln.count; ++g)
+          if (pre[(size_t)g].stage != 3) QTR_HIP_TRY(h, hipStreamSynchronize(h->slots[ln.first_slot + g].stream));
+      }
+    } else {
+      spins = 0;
+    }
+  }
   return QTR_OK;
 }
 
 static int lane_start_chunk(qtr_handle* h, Lane& ln) {
   BatchJob& J = h->job;
   if (J.next >= J.B) {
-    ln.phase = 0;
+    ln.phase = LANE_IDLE;
     ln.count = 0;
     return QTR_OK;
   }
@@ -2696,96 +2738,8 @@ static int lane_start_chunk(qtr_handle* h, Lane& ln) {
   std::vector<int> Ps;
   std::vector<void*> kf_dev;                  // keyframe job: the device allocations, two per pair (Ps: their voxel counts)
   std::vector<unsigned long long> kf_seeds;
-  // The demo's STEP 2 and 3 on raw sweeps (reference examples/run_global_registration.cpp:136-160): per scan
-  // PatchWork::estimate_ground -> non-ground points -> ImageProjection::segmentCloud -> valid segments.  Both stages hand a
-  // count to the next one through the host, so a scan is a chain of four host-visible steps — run for ALL pairs of the
-  // chunk side by side, every pair on its own slot's stream and arenas (target first, then source: the two scans of a pair
-  // share the slot), the host advancing whichever slot's step has finished.  (Rounds 2-3 ran them pair after pair with a
-  // blocking read-back per step: a chunk of sixteen raw pairs waited 64 times.)  The valid segments land in the slot's
-  // staging buffers, which are the voxel grid's input; the lane's stream waits for the copies, not the host.
-  struct PreScan {
-    int stage = 0;  // 0 start, 1 ground segmentation of scan c in flight, 2 range-image stage in flight, 3 done
-    int c = 1;      // scan being processed: 1 target, then 0 source
-    int status = QTR_OK;
-    int n[2] = {0, 0};  // valid points of source / target
-  };
   std::vector<PreScan> pre((size_t)ln.count);
-  if (h->pre_on && !J.kf) {
-    int open = 0;
-    for (int g = 0; g < ln.count; ++g) {
-      const qtr_pair_desc& pd = J.pairs[ln.first_pair + g];
-      const bool usable = pair_has_scans(pd) && pd.src_raw4 && pd.tgt_raw4 && pd.n_src > 0 && pd.n_tgt > 0 &&
-                          pd.n_src <= h->lim.max_points && pd.n_tgt <= h->lim.max_points;
-      if (!usable) pre[(size_t)g].stage = 3;  // (refused by the checks below, or a pair without scans)
-      else ++open;
-    }
-    unsigned long spins = 0;
-    while (open > 0) {
-      bool moved = false;
-      for (int g = 0; g < ln.count; ++g) {
-        PreScan& q = pre[(size_t)g];
-        if (q.stage == 3) continue;
-        const qtr_pair_desc& pd = J.pairs[ln.first_pair + g];
-        Slot& s = h->slots[ln.first_slot + g];
-        int rc = QTR_OK;
-        if (q.stage == 0) {
-          rc = pw_begin(h, s, q.c ? pd.tgt_raw4 : pd.src_raw4, q.c ? pd.n_tgt : pd.n_src, &h->pre_pw, J.mem);
-          q.stage = 1;
-          moved = true;
-        } else {
-          const hipError_t e = hipEventQuery(s.ev[1]);
-          if (e == hipErrorNotReady) continue;
-          if (e != hipSuccess) {
-            snprintf(h->err, sizeof(h->err), "batch pre-processing: %s", hipGetErrorString(e));
-            return QTR_ERR_HIP;
-          }
-          moved = true;
-          if (q.stage == 1) {  // ground removed: its non-ground points go through the range image
-            int ng = 0, nn = 0;
-            pw_end(s, &ng, &nn);
-            rc = seg_begin(h, s, (const float*)s.pwb.out_n, nn, &h->pre_ip, QTR_MEM_DEVICE);
-            q.stage = 2;
-          } else {  // valid segments known: into the staging buffer; next scan, or done
-            const int nv = s.pinned_i32[0];
-            q.n[q.c] = nv;
-            if (nv > h->lim.max_points) rc = QTR_ERR_CAPACITY;
-            else if (nv > 0)
-              // (on the slot's own stream: the next scan's stages, which reuse the buffers this copy reads, queue up behind it)
-              QTR_HIP_TRY(h, hipMemcpyAsync(q.c ? s.in_tgt : s.in_src, s.seg.out_valid, (size_t)nv * 16, hipMemcpyDeviceToDevice,
-                                            s.stream));
-            if (rc == QTR_OK && q.c == 1) {
-              q.c = 0;
-              q.stage = 0;
-            } else {
-              if (rc == QTR_OK) {  // the group's chain (lane stream) reads the staging buffers: it waits for this slot
-                QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
-                QTR_HIP_TRY(h, hipStreamWaitEvent(lead.stream, s.ev[1], 0));
-              }
-              q.stage = 3;
-              --open;
-            }
-          }
-        }
-        if (rc == QTR_ERR_HIP) return rc;
-        if (rc != QTR_OK && q.stage != 3) {  // this pair's own failure (capacity, a scan the stage refuses)
-          q.status = rc;
-          q.stage = 3;
-          --open;
-        } else if (rc != QTR_OK) {
-          q.status = rc;
-        }
-      }
-      if (!moved) {
-        __builtin_ia32_pause();
-        if ((++spins & 0xffffff) == 0) {  // nothing moved for a long while: a lost device must not hang the host
-          for (int g = 0; g < ln.count; ++g)
-            if (pre[(size_t)g].stage != 3) QTR_HIP_TRY(h, hipStreamSynchronize(h->slots[ln.first_slot + g].stream));
-        }
-      } else {
-        spins = 0;
-      }
-    }
-  }
+  if (h->pre_on && !J.kf) QTR_TRY(lane_preprocess(h, ln, pre));
   for (int g = 0; g < ln.count; ++g) {
     const qtr_pair_desc& pd = J.pairs[ln.first_pair + g];
     Slot& s = h->slots[ln.first_slot + g];
@@ -2821,17 +2775,7 @@ static int lane_start_chunk(qtr_handle* h, Lane& ln) {
       ln.L[g] = pd.n_corr;
     }
     if (!scans) {  // correspondences only: nothing to do before the solver chain
-      if (J.mem == QTR_MEM_HOST) {
-        if (pd.n_corr > 0) {
-          QTR_HIP_TRY(h, hipMemcpyAsync(s.m_src, pd.src_corr4, (size_t)pd.n_corr * 16, hipMemcpyHostToDevice, lead.stream));
-          QTR_HIP_TRY(h, hipMemcpyAsync(s.m_tgt, pd.tgt_corr4, (size_t)pd.n_corr * 16, hipMemcpyHostToDevice, lead.stream));
-        }
-        ln.csrc[g] = s.m_src;
-        ln.ctgt[g] = s.m_tgt;
-      } else {
-        ln.csrc[g] = (const float4*)pd.src_corr4;
-        ln.ctgt[g] = (const float4*)pd.tgt_corr4;
-      }
+      QTR_TRY(corr_stage(h, s, pd.src_corr4, pd.tgt_corr4, pd.n_corr, J.mem, lead.stream, &ln.csrc[g], &ln.ctgt[g]));
       ln.corr_only.push_back(g);
       continue;
     }
@@ -2873,26 +2817,26 @@ static int lane_start_chunk(qtr_handle* h, Lane& ln) {
   }
   if (ln.active.empty()) return lane_enqueue_solver(h, ln, {});  // no scans in this chunk (or nothing valid at all)
   if (J.kf) {
-    // phase 1 is gone and phase 2 is a grouped load (blockIdx.z = pair) in front of the matcher, which finds the
+    // no voxel chain, and the matching chain is a grouped load (blockIdx.z = pair) in front of the matcher, which finds the
     // per-descriptor preparation done as after the whole path's k2_fpfh.  The lists' checks were made when the keyframes
     // were created and the load leaves their counter words clean: the chunk counts as one that ran k2_neighbors_big.
     QTR_HIP_TRY(h, kf_load_enqueue_group(F.data(), (int)F.size(), kf_dev.data(), Ps.data(), &ln.stage, lead.stream));
     ln.long_lists = true;
     QTR_HIP_TRY(h, match_enqueue_group(F.data(), (int)F.size(), Ps.data(), &J.fp, kf_seeds.data(), &ln.stage, lead.stream, true));
-    ln.phase = 2;
+    ln.phase = LANE_MATCH;
     return QTR_OK;
   }
   QTR_HIP_TRY(h, voxelize_enqueue_group(F.data(), (int)F.size(), raws.data(), Ps.data(), J.fp.voxel_size, &ln.stage,
                                         lead.stream, J.fp.fpfh_radius * 1.001f));
   QTR_HIP_TRY(h, hipEventRecord(lead.ev_vox, lead.stream));
-  ln.phase = 1;
+  ln.phase = LANE_VOXELS;
   return QTR_OK;
 }
 
 // Refine phase of the chunk (qtr_submit_batch_refine), while the chunk's slots still hold its clouds: the pairs of the
 // solver chain that ran the front end and registered (QTR_OK / QTR_ERR_CLIQUE_TOO_SMALL, mark_registration's rule) go
 // through the grouped ICP kernels (icp.hip), blockIdx.y = pair.  Three chains, each ending in the slots' mailboxes:
-//   target boxes (phase 4)  ->  host: every pair's cell grid  ->  grid build + iterations + states (phase 5)
+//   target boxes (LANE_REFINE_BOXES)  ->  host: every pair's cell grid  ->  grid build + iterations + states (LANE_REFINE_ITER)
 // With QTR_ICP_BLOCK = n the iterations go n launches per chain, and the lane stops enqueuing once every pair has stopped.
 static int lane_enqueue_refine(qtr_handle* h, Lane& ln) {
   BatchJob& J = h->job;
@@ -2940,7 +2884,7 @@ static int lane_enqueue_refine(qtr_handle* h, Lane& ln) {
     return QTR_ERR_HIP;
   }
   QTR_HIP_TRY(h, icp_box_enqueue_group(dv, G, max_nt, ds, lead.stream));
-  ln.phase = 4;
+  ln.phase = LANE_REFINE_BOXES;
   return QTR_OK;
 }
 
@@ -2960,11 +2904,11 @@ static int lane_enqueue_icp_block(qtr_handle* h, Lane& ln) {
   QTR_HIP_TRY(h, icp_iter_enqueue_group(ln.ref_views, (int)seqs.size(), ln.ref_nchunk, m, ds, lead.stream,
                                         J.icp.method == QTR_ICP_PLANE_TO_PLANE));
   ln.ref_it += m;
-  ln.phase = 5;
+  ln.phase = LANE_REFINE_ITER;
   return QTR_OK;
 }
 
-// phase 4: the boxes are in; every pair's grid (a pair without a finite target point is done: icp_device's early return)
+// LANE_REFINE_BOXES: the boxes are in; every pair's grid (a pair without a finite target point is done: icp_device's early return)
 static int lane_refine_grids(qtr_handle* h, Lane& ln) {
   BatchJob& J = h->job;
   Slot& lead = h->slots[ln.first_slot];
@@ -3009,7 +2953,7 @@ static int lane_refine_grids(qtr_handle* h, Lane& ln) {
   return lane_enqueue_icp_block(h, ln);
 }
 
-// phase 5: the states are in; another block, or the refined records and the next chunk
+// LANE_REFINE_ITER: the states are in; another block, or the refined records and the next chunk
 static int lane_refine_done(qtr_handle* h, Lane& ln) {
   BatchJob& J = h->job;
   std::vector<QtrIcpState> st(ln.active.size());
@@ -3035,221 +2979,156 @@ static int lane_refine_done(qtr_handle* h, Lane& ln) {
   return lane_start_chunk(h, ln);
 }
 
-// advances the lane by at most one chain; *progress is set when it did
-static int lane_poll(qtr_handle* h, Lane& ln, bool* progress) {
+// LANE_VOXELS: both clouds' voxel counters of every pair are in -> means beside the FPFH chain, the matching chain
+static int lane_after_voxels(qtr_handle* h, Lane& ln) {
   BatchJob& J = h->job;
-  if (ln.phase == 0) return QTR_OK;
   Slot& lead = h->slots[ln.first_slot];
-  if (ln.phase == 4 || ln.phase == 5) {
-    for (int g : ln.active) {
-      Slot& s = h->slots[ln.first_slot + g];
-      if (!mail_ready(s, ln.phase == 4 ? MAIL_SEQ_ICP_BOX : MAIL_SEQ_ICP, s.seq)) return QTR_OK;
-    }
-    *progress = true;
-    return ln.phase == 4 ? lane_refine_grids(h, ln) : lane_refine_done(h, ln);
-  }
-  if (ln.phase == 1) {
-    for (int g : ln.active) {
-      Slot& s = h->slots[ln.first_slot + g];
-      if (!mail_ready(s, MAIL_SEQ_VOX0, s.seq) || !mail_ready(s, MAIL_SEQ_VOX1, s.seq)) return QTR_OK;
-    }
-    *progress = true;
-    bool passed_through = false;
-    std::vector<int> keep;
-    std::vector<FrontBufs*> F;
-    std::vector<int> n2;
-    std::vector<unsigned long long> seeds;
-    for (int g : ln.active) {
-      Slot& s = h->slots[ln.first_slot + g];
-      qtr_result& r = J.results[ln.first_pair + g];
-      int ns = s.mail[MAIL_VOX0 + CNT_NVOX], nt = s.mail[MAIL_VOX1 + CNT_NVOX];
-      if (ns < 0 || nt < 0) {  // the centroid kernel's look-back timed out for this pair (see front_device)
-        batch_fail_pair(h, ln.first_pair + g, QTR_ERR_HIP);
-        continue;
-      }
-      // (a grid that would overflow int32 passes its cloud through, as pcl::VoxelGrid does: see front_device)
-      const bool pass_s = s.mail[MAIL_VOX0 + CNT_VOX_OVERFLOW] != 0, pass_t = s.mail[MAIL_VOX1 + CNT_VOX_OVERFLOW] != 0;
-      if (pass_s) ns = ln.Ps[g];
-      if (pass_t) nt = ln.Pt[g];
-      if (pass_s && ns <= h->lim.max_voxels) {
-        QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[0].vox, ln.raw_s[g], (size_t)ns * 16, hipMemcpyDeviceToDevice, lead.stream));
-        passed_through = true;
-      }
-      if (pass_t && nt <= h->lim.max_voxels) {
-        QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[1].vox, ln.raw_t[g], (size_t)nt * 16, hipMemcpyDeviceToDevice, lead.stream));
-        passed_through = true;
-      }
-      r.n_src = ns;
-      r.n_tgt = nt;
-      if (ns > h->lim.max_voxels || nt > h->lim.max_voxels || ns <= 0 || nt <= 0) {
-        batch_fail_pair(h, ln.first_pair + g, QTR_ERR_CAPACITY);
-        continue;
-      }
-      ln.ns[g] = ns;
-      ln.nt[g] = nt;
-      s.last_ns = ns;
-      s.last_nt = nt;
-      keep.push_back(g);
-      F.push_back(&s.fb);
-      n2.push_back(ns);
-      n2.push_back(nt);
-      seeds.push_back(J.pairs[ln.first_pair + g].seed);
-    }
-    ln.active.swap(keep);
-    if (ln.active.empty()) return lane_enqueue_solver(h, ln, {});
-    const int G = (int)F.size();
-    if (passed_through) QTR_HIP_TRY(h, hipEventRecord(lead.ev_vox, lead.stream));
-    QTR_HIP_TRY(h, hipStreamWaitEvent(lead.stream2, lead.ev_vox, 0));
-    QTR_HIP_TRY(h, mean_enqueue_group(F.data(), G, n2.data(), &ln.stage, lead.stream2));  // beside the FPFH chain
-    QTR_HIP_TRY(h, hipEventRecord(lead.ev[5], lead.stream2));
-    ln.long_lists = h->long_lists;
-    if (ln.long_lists)
-      for (int g : ln.active) QTR_TRY(ensure_long_arenas(h, h->slots[ln.first_slot + g]));
-    int max_ncell = 1;  // the largest neighbour grid of the group (0: some pair's does not fit the dense cell table)
-    for (int g : ln.active) {
-      const Slot& sg = h->slots[ln.first_slot + g];
-      const int nc2 = cell_table_cells(sg.mail[MAIL_VOX0 + CNT_NCELL], sg.mail[MAIL_VOX1 + CNT_NCELL]);
-      max_ncell = (max_ncell == 0 || nc2 == 0) ? 0 : std::max(max_ncell, nc2);
-    }
-    QTR_HIP_TRY(h, fpfh_enqueue_group(F.data(), G, n2.data(), J.fp.normal_radius, J.fp.fpfh_radius, &ln.stage, lead.stream,
-                                      ln.long_lists, true, max_ncell));
-    QTR_HIP_TRY(h, hipStreamWaitEvent(lead.stream, lead.ev[5], 0));
-    for (int g : ln.active) {
-      Slot& s = h->slots[ln.first_slot + g];
-      s.fb.mail_seq = ++s.seq;
-    }
-    QTR_HIP_TRY(h, match_enqueue_group(F.data(), G, n2.data(), &J.fp, seeds.data(), &ln.stage, lead.stream, true));
-    ln.phase = 2;
-    return QTR_OK;
-  }
-  if (ln.phase == 2) {
-    for (int g : ln.active) {
-      Slot& s = h->slots[ln.first_slot + g];
-      if (!mail_ready(s, MAIL_SEQ_MATCH, s.seq)) return QTR_OK;
-    }
-    *progress = true;
-    std::vector<int> keep;
-    bool drained = false;  // lead.stream has been synchronised by a fallback below
-    for (int g : ln.active) {
-      Slot& s = h->slots[ln.first_slot + g];
-      qtr_result& r = J.results[ln.first_pair + g];
-      const qtr_pair_desc& pd = J.pairs[ln.first_pair + g];
-      const bool given = pair_has_corr(pd);  // the back end runs on the caller's correspondences, not the matcher's
-      const int Lm = s.mail[MAIL_MATCH + MC_NCORR];
-      if (!given) r.n_corr = Lm;
-      if (Lm < 0 && !given) {  // the tail's look-back timed out (match.hip): nothing usable was written for this pair
-        r.n_corr = 0;
-        batch_fail_pair(h, ln.first_pair + g, QTR_ERR_HIP);
-        continue;
-      }
-      if (s.mail[MAIL_CNT0 + CNT_VOX_TAILERR] || s.mail[MAIL_CNT1 + CNT_VOX_TAILERR]) {  // (see front_device)
-        batch_fail_pair(h, ln.first_pair + g, QTR_ERR_HIP);
-        continue;
-      }
-      // (a pair that brought its correspondences does not read the matcher's list: its length is no reason to fail it)
-      if (s.mail[MAIL_CNT0 + CNT_NBR_CAPACITY] || s.mail[MAIL_CNT1 + CNT_NBR_CAPACITY] ||
-          (!given && Lm > h->lim.max_corr)) {
-        batch_fail_pair(h, ln.first_pair + g, QTR_ERR_CAPACITY);
-        continue;
-      }
-      if (!ln.long_lists && (s.mail[MAIL_CNT0 + CNT_NBR_OVERFLOW] || s.mail[MAIL_CNT1 + CNT_NBR_OVERFLOW])) {
-        // A point with more than QTR_KMAX neighbours and a chain without k2_neighbors_big (see front_device): this pair
-        // goes through the per-pair path on its own slot, and the handle's later chains include the launch.  The
-        // group's chain (lane stream) may still be writing this slot's lists — the mail is published before the
-        // kernel's last workgroup is done — so the lane stream is drained first; the pair is registered on the clouds
-        // the group's voxel grid read (the pre-processed sweeps when qtr_set_batch_preprocess is on, the staged copies
-        // of host scans: device pointers either way), and on the caller's correspondences when it brought some.
-        h->long_lists = true;
-        if (!drained) QTR_HIP_TRY(h, hipStreamSynchronize(lead.stream));
-        drained = true;
-        qtr_frontend_params f1 = J.fp;
-        f1.seed = pd.seed;
-        const float4 *cs = nullptr, *ct = nullptr;
-        if (given) {
-          cs = (const float4*)pd.src_corr4;
-          ct = (const float4*)pd.tgt_corr4;
-          if (J.mem == QTR_MEM_HOST) {  // (front_device overwrites m_src / m_tgt: the copy goes behind it, see below)
-            cs = s.m_src;
-            ct = s.m_tgt;
-          }
-        }
-        int rc1;
-        if (given && J.mem == QTR_MEM_HOST) {
-          // front end first, then the caller's correspondences into the (now free) matched-cloud buffers, then the back end
-          int L1 = 0;
-          rc1 = front_device(h, s, (const float*)ln.raw_s[g], ln.Ps[g], (const float*)ln.raw_t[g], ln.Pt[g], &f1,
-                             QTR_MEM_DEVICE, true, &r.n_src, &r.n_tgt, &L1, true);
-          if (rc1 == QTR_OK) {
-            if (pd.n_corr > 0) {
-              QTR_HIP_TRY(h, hipMemcpyAsync(s.m_src, pd.src_corr4, (size_t)pd.n_corr * 16, hipMemcpyHostToDevice, s.stream));
-              QTR_HIP_TRY(h, hipMemcpyAsync(s.m_tgt, pd.tgt_corr4, (size_t)pd.n_corr * 16, hipMemcpyHostToDevice, s.stream));
-            }
-            r.n_corr = pd.n_corr;
-            rc1 = solve_device(h, s, s.m_src, s.m_tgt, pd.n_corr, &J.prm, &r, true);
-            if (rc1 == QTR_OK || rc1 == QTR_ERR_CLIQUE_TOO_SMALL) {
-              const int rc2 = copy_out_lists(h, s, &r, pd.clique, nullptr, pd.final_inliers, pd.cap, J.mem);
-              if (rc2 != QTR_OK) r.status = rc1 = rc2;
-            }
-          } else {
-            r.status = rc1;
-          }
-        } else {
-          rc1 = register_pair_impl(h, s, (const float*)ln.raw_s[g], ln.Ps[g], (const float*)ln.raw_t[g], ln.Pt[g], &f1, &J.prm,
-                                   &r, pd.clique, pd.final_inliers, pd.cap, QTR_MEM_DEVICE, J.mem, cs, ct,
-                                   given ? pd.n_corr : -1);
-        }
-        if (rc1 == QTR_ERR_HIP) return rc1;
-        J.finished[ln.first_pair + g] = 1;
-        ++J.done;
-        if (J.refine && (r.status == QTR_OK || r.status == QTR_ERR_CLIQUE_TOO_SMALL)) {
-          // (the slot holds this pair's clouds as after qtr_register_pair: qtr_refine_pair's own path, on the slot's stream)
-          J.ref_state[ln.first_pair + g] = 1;
-          if (icp_device(h, s, s.fb.cloud[0].vox, s.last_ns, s.fb.cloud[1].vox, s.last_nt, s.fb.cloud[1].normals,
-                         s.fb.cloud[0].normals, r.T, &J.icp,
-                         &J.refined[ln.first_pair + g]) != QTR_OK)
-            return QTR_ERR_HIP;
-          J.ref_state[ln.first_pair + g] = 2;
-        }
-        continue;
-      }
-      if (!given) QTR_HIP_TRY(h, gather_matched_enqueue(s.fb, Lm, s.m_src, s.m_tgt, lead.stream));  // no-op after the fused tail
-      if (given) {
-        if (J.mem == QTR_MEM_HOST) {  // behind the matching chain on the lane's stream: the matched clouds are not needed
-          if (pd.n_corr > 0) {
-            QTR_HIP_TRY(h, hipMemcpyAsync(s.m_src, pd.src_corr4, (size_t)pd.n_corr * 16, hipMemcpyHostToDevice, lead.stream));
-            QTR_HIP_TRY(h, hipMemcpyAsync(s.m_tgt, pd.tgt_corr4, (size_t)pd.n_corr * 16, hipMemcpyHostToDevice, lead.stream));
-          }
-          ln.csrc[g] = s.m_src;
-          ln.ctgt[g] = s.m_tgt;
-        } else {
-          ln.csrc[g] = (const float4*)pd.src_corr4;
-          ln.ctgt[g] = (const float4*)pd.tgt_corr4;
-        }
-        ln.L[g] = pd.n_corr;
-      } else {
-        ln.csrc[g] = s.m_src;
-        ln.ctgt[g] = s.m_tgt;
-        ln.L[g] = Lm;
-      }
-      keep.push_back(g);
-    }
-    return lane_enqueue_solver(h, ln, keep);
-  }
-  // phase 3
+  bool passed_through = false;
+  std::vector<int> keep;
+  std::vector<FrontBufs*> F;
+  std::vector<int> n2;
+  std::vector<unsigned long long> seeds;
   for (int g : ln.active) {
     Slot& s = h->slots[ln.first_slot + g];
-    if (!mail_ready(s, MAIL_SEQ_SOLVE, s.seq)) return QTR_OK;
+    qtr_result& r = J.results[ln.first_pair + g];
+    const VoxVerdict vs = vox_verdict(s.mail + MAIL_VOX0, ln.Ps[g], h->lim.max_voxels),
+                     vt = vox_verdict(s.mail + MAIL_VOX1, ln.Pt[g], h->lim.max_voxels);
+    if (vs.reason == VOX_TIMEOUT || vt.reason == VOX_TIMEOUT) {
+      batch_fail_pair(h, ln.first_pair + g, QTR_ERR_HIP);
+      continue;
+    }
+    if (vs.passed && vs.reason == VOX_OK) {
+      QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[0].vox, ln.raw_s[g], (size_t)vs.n * 16, hipMemcpyDeviceToDevice, lead.stream));
+      passed_through = true;
+    }
+    if (vt.passed && vt.reason == VOX_OK) {
+      QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[1].vox, ln.raw_t[g], (size_t)vt.n * 16, hipMemcpyDeviceToDevice, lead.stream));
+      passed_through = true;
+    }
+    const int ns = r.n_src = vs.n, nt = r.n_tgt = vt.n;
+    if (vs.reason != VOX_OK || vt.reason != VOX_OK) {  // (too large either way, or empty)
+      batch_fail_pair(h, ln.first_pair + g, QTR_ERR_CAPACITY);
+      continue;
+    }
+    ln.ns[g] = ns;
+    ln.nt[g] = nt;
+    s.last_ns = ns;
+    s.last_nt = nt;
+    keep.push_back(g);
+    F.push_back(&s.fb);
+    n2.push_back(ns);
+    n2.push_back(nt);
+    seeds.push_back(J.pairs[ln.first_pair + g].seed);
   }
-  *progress = true;
+  ln.active.swap(keep);
+  if (ln.active.empty()) return lane_enqueue_solver(h, ln, {});
+  const int G = (int)F.size();
+  if (passed_through) QTR_HIP_TRY(h, hipEventRecord(lead.ev_vox, lead.stream));
+  QTR_HIP_TRY(h, hipStreamWaitEvent(lead.stream2, lead.ev_vox, 0));
+  QTR_HIP_TRY(h, mean_enqueue_group(F.data(), G, n2.data(), &ln.stage, lead.stream2));  // beside the FPFH chain
+  QTR_HIP_TRY(h, hipEventRecord(lead.ev[5], lead.stream2));
+  ln.long_lists = h->long_lists;
+  if (ln.long_lists)
+    for (int g : ln.active) QTR_TRY(ensure_long_arenas(h, h->slots[ln.first_slot + g]));
+  int max_ncell = 1;  // the largest neighbour grid of the group (0: some pair's does not fit the dense cell table)
+  for (int g : ln.active) {
+    const Slot& sg = h->slots[ln.first_slot + g];
+    const int nc2 = cell_table_cells(sg.mail[MAIL_VOX0 + CNT_NCELL], sg.mail[MAIL_VOX1 + CNT_NCELL]);
+    max_ncell = (max_ncell == 0 || nc2 == 0) ? 0 : std::max(max_ncell, nc2);
+  }
+  QTR_HIP_TRY(h, fpfh_enqueue_group(F.data(), G, n2.data(), J.fp.normal_radius, J.fp.fpfh_radius, &ln.stage, lead.stream,
+                                    ln.long_lists, true, max_ncell));
+  QTR_HIP_TRY(h, hipStreamWaitEvent(lead.stream, lead.ev[5], 0));
+  for (int g : ln.active) {
+    Slot& s = h->slots[ln.first_slot + g];
+    s.fb.mail_seq = ++s.seq;
+  }
+  QTR_HIP_TRY(h, match_enqueue_group(F.data(), G, n2.data(), &J.fp, seeds.data(), &ln.stage, lead.stream, true));
+  ln.phase = LANE_MATCH;
+  return QTR_OK;
+}
+
+// LANE_MATCH: the matcher's counters and the clouds' counter lines are in -> the solver chain on the survivors
+static int lane_after_match(qtr_handle* h, Lane& ln) {
+  BatchJob& J = h->job;
+  Slot& lead = h->slots[ln.first_slot];
+  std::vector<int> keep;
+  bool drained = false;  // lead.stream has been synchronised by a fallback below
+  for (int g : ln.active) {
+    Slot& s = h->slots[ln.first_slot + g];
+    qtr_result& r = J.results[ln.first_pair + g];
+    const qtr_pair_desc& pd = J.pairs[ln.first_pair + g];
+    const bool given = pair_has_corr(pd);  // the back end runs on the caller's correspondences, not the matcher's
+    const int Lm = s.mail[MAIL_MATCH + MC_NCORR];
+    const ListsVerdict lv = lists_verdict(s.mail + MAIL_CNT0, s.mail + MAIL_CNT1, ln.long_lists);
+    if (!given) r.n_corr = Lm;
+    if (Lm < 0 && !given) {  // the tail's look-back timed out (match.hip): nothing usable was written for this pair
+      r.n_corr = 0;
+      batch_fail_pair(h, ln.first_pair + g, QTR_ERR_HIP);
+      continue;
+    }
+    if (lv == LISTS_TILE_ERROR) {
+      batch_fail_pair(h, ln.first_pair + g, QTR_ERR_HIP);
+      continue;
+    }
+    // (a pair that brought its correspondences does not read the matcher's list: its length is no reason to fail it)
+    if (lv == LISTS_CAPACITY || (!given && Lm > h->lim.max_corr)) {
+      batch_fail_pair(h, ln.first_pair + g, QTR_ERR_CAPACITY);
+      continue;
+    }
+    if (lv == LISTS_NEED_LONG) {
+      // This pair goes through the per-pair path on its own slot, and the handle's later chains include the launch.  The
+      // group's chain (lane stream) may still be writing this slot's lists — the mail is published before the
+      // kernel's last workgroup is done — so the lane stream is drained first; the pair is registered on the clouds
+      // the group's voxel grid read (the pre-processed sweeps when qtr_set_batch_preprocess is on, the staged copies
+      // of host scans: device pointers either way), and on the caller's correspondences when it brought some.
+      h->long_lists = true;
+      if (!drained) QTR_HIP_TRY(h, hipStreamSynchronize(lead.stream));
+      drained = true;
+      qtr_frontend_params f1 = J.fp;
+      f1.seed = pd.seed;
+      const int rc1 = register_pair_impl(h, s, (const float*)ln.raw_s[g], ln.Ps[g], (const float*)ln.raw_t[g], ln.Pt[g], &f1,
+                                         &J.prm, &r, pd.clique, pd.final_inliers, pd.cap, QTR_MEM_DEVICE, J.mem, pd.src_corr4,
+                                         pd.tgt_corr4, given ? pd.n_corr : -1);
+      if (rc1 == QTR_ERR_HIP) return rc1;
+      J.finished[ln.first_pair + g] = 1;
+      ++J.done;
+      if (J.refine && (r.status == QTR_OK || r.status == QTR_ERR_CLIQUE_TOO_SMALL)) {
+        // (the slot holds this pair's clouds as after qtr_register_pair: qtr_refine_pair's own path, on the slot's stream)
+        J.ref_state[ln.first_pair + g] = 1;
+        if (icp_device(h, s, s.fb.cloud[0].vox, s.last_ns, s.fb.cloud[1].vox, s.last_nt, s.fb.cloud[1].normals,
+                       s.fb.cloud[0].normals, r.T, &J.icp,
+                       &J.refined[ln.first_pair + g]) != QTR_OK)
+          return QTR_ERR_HIP;
+        J.ref_state[ln.first_pair + g] = 2;
+      }
+      continue;
+    }
+    if (given) {  // (host correspondences: behind the matching chain on the lane's stream — the matched clouds are not needed)
+      QTR_TRY(corr_stage(h, s, pd.src_corr4, pd.tgt_corr4, pd.n_corr, J.mem, lead.stream, &ln.csrc[g], &ln.ctgt[g]));
+      ln.L[g] = pd.n_corr;
+    } else {
+      QTR_HIP_TRY(h, gather_matched_enqueue(s.fb, Lm, s.m_src, s.m_tgt, lead.stream));  // no-op after the fused tail
+      ln.csrc[g] = s.m_src;
+      ln.ctgt[g] = s.m_tgt;
+      ln.L[g] = Lm;
+    }
+    keep.push_back(g);
+  }
+  return lane_enqueue_solver(h, ln, keep);
+}
+
+// LANE_SOLVE: every pair's record and solver state are in -> follow-ups, the records, the lists; then refinement or the
+// next chunk
+static int lane_after_solve(qtr_handle* h, Lane& ln) {
+  BatchJob& J = h->job;
+  Slot& lead = h->slots[ln.first_slot];
   bool copies = false;
   for (int g : ln.active) {
     Slot& s = h->slots[ln.first_slot + g];
     const int pair = ln.first_pair + g;
     qtr_result& r = J.results[pair];
     const qtr_pair_desc& pd = J.pairs[pair];
-    const int L = ln.L[g];
-    const float4 *c_src = ln.csrc[g], *c_tgt = ln.ctgt[g];
-    int rc = QTR_OK;
     // Follow-up work of ONE pair of the group runs on the lane's stream (the lane's chain owns the slot's arenas), and
     // everything that waits for it — wait_mail's liveness check, exact_phase's enqueues — must look at THAT stream:
     // the slot's own stream is idle, so a wait that queries it gives up before the kernels have run.
@@ -3259,29 +3138,9 @@ static int lane_poll(qtr_handle* h, Lane& ln, bool* progress) {
       StreamSwap(Slot& s_, hipStream_t st) : s(s_), keep(s_.stream) { s.stream = st; }
       ~StreamSwap() { s.stream = keep; }
     } on_lane_stream(s, lead.stream);
-    if (L > 0 && !((const SolverState*)(s.mail + MAIL_SOLVER + 64))->done) {  // rare: more clique rounds needed
-      s.sb.mail_seq = ++s.seq;
-      QTR_HIP_TRY(h, solver_continue(s.sb, c_src, c_tgt, L, J.prm, lead.stream, s.pinned_i32 + 128,
-                                     ((const SolverState*)(s.mail + MAIL_SOLVER + 64))->redo_cores));
-      QTR_TRY(wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq));
-    }
-    if (L > 0 && J.prm.inlier_selection_mode == QTR_INLIER_PMC_EXACT) {
-      SolverState hs;
-      memcpy(&hs, s.mail + MAIL_SOLVER + 64, sizeof(hs));
-      bool improved = false;
-      rc = exact_phase(h, s, L, hs, &improved, J.prm.max_clique_time_limit);
-      if (rc != QTR_OK) return rc;
-      if (improved) {
-        s.sb.mail_seq = ++s.seq;
-        QTR_HIP_TRY(h, solver_refinalize(s.sb, c_src, c_tgt, L, J.prm, lead.stream));
-        QTR_TRY(wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq));
-      }
-    }
-    const int keep_ns = r.n_src, keep_nt = r.n_tgt, keep_nc = r.n_corr;
-    memcpy(&r, s.mail + MAIL_SOLVER, sizeof(qtr_result));
-    r.n_src = keep_ns;
-    r.n_tgt = keep_nt;
-    r.n_corr = keep_nc;
+    QTR_TRY(solve_followup(h, s, ln.csrc[g], ln.ctgt[g], ln.L[g], &J.prm, lead.stream, false));
+    result_from_mail(s, &r);
+    // (not copy_out_lists: an overflow marks the pair and the lane goes on, and the lane synchronises once)
     const hipMemcpyKind kind = (J.mem == QTR_MEM_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (pd.clique && r.n_clique > 0) {
       if (r.n_clique > pd.cap) r.status = QTR_ERR_CAPACITY;
@@ -3303,6 +3162,35 @@ static int lane_poll(qtr_handle* h, Lane& ln, bool* progress) {
   if (copies) QTR_HIP_TRY(h, hipStreamSynchronize(lead.stream));
   if (J.refine) return lane_enqueue_refine(h, ln);
   return lane_start_chunk(h, ln);
+}
+
+// the mailbox word that ends a phase's chain (the voxel stage mails one line per cloud: MAIL_SEQ_VOX0 as well)
+static int lane_mail_index(LanePhase phase) {
+  switch (phase) {
+    case LANE_VOXELS: return MAIL_SEQ_VOX1;
+    case LANE_MATCH: return MAIL_SEQ_MATCH;
+    case LANE_SOLVE: return MAIL_SEQ_SOLVE;
+    case LANE_REFINE_BOXES: return MAIL_SEQ_ICP_BOX;
+    default: return MAIL_SEQ_ICP;
+  }
+}
+
+// advances the lane by at most one chain, once every active slot's mail is in; *progress is set when it did
+static int lane_poll(qtr_handle* h, Lane& ln, bool* progress) {
+  if (ln.phase == LANE_IDLE) return QTR_OK;
+  for (int g : ln.active) {
+    const Slot& s = h->slots[ln.first_slot + g];
+    if (ln.phase == LANE_VOXELS && !mail_ready(s, MAIL_SEQ_VOX0, s.seq)) return QTR_OK;
+    if (!mail_ready(s, lane_mail_index(ln.phase), s.seq)) return QTR_OK;
+  }
+  *progress = true;
+  switch (ln.phase) {
+    case LANE_VOXELS: return lane_after_voxels(h, ln);
+    case LANE_MATCH: return lane_after_match(h, ln);
+    case LANE_SOLVE: return lane_after_solve(h, ln);
+    case LANE_REFINE_BOXES: return lane_refine_grids(h, ln);
+    default: return lane_refine_done(h, ln);
+  }
 }
 
 int qtr_set_batch_preprocess(qtr_handle* h, const qtr_pw_params* pw, const qtr_ip_params* ip) {
@@ -3446,7 +3334,7 @@ int qtr_wait(qtr_handle* h) {
   while (true) {
     bool any_active = false, progress = false;
     for (auto& ln : h->lanes) {
-      if (ln.phase == 0) continue;
+      if (ln.phase == LANE_IDLE) continue;
       any_active = true;
       rc = lane_poll(h, ln, &progress);
       if (rc != QTR_OK) break;
@@ -3459,22 +3347,17 @@ int qtr_wait(qtr_handle* h) {
     __builtin_ia32_pause();
     if ((++idle & 0xfffff) == 0) {  // nothing moved for a long while: has a launch failed, is the device gone?
       for (auto& ln : h->lanes) {
-        if (ln.phase == 0) continue;
+        if (ln.phase == LANE_IDLE) continue;
         Slot& lead = h->slots[ln.first_slot];
         const hipError_t q = hipStreamQuery(lead.stream);
         if (q == hipSuccess) {  // stream drained, yet a mailbox never arrived
           bool all = true;
           for (int g : ln.active) {
             Slot& s = h->slots[ln.first_slot + g];
-            const int idx = ln.phase == 1   ? MAIL_SEQ_VOX1
-                            : ln.phase == 2 ? MAIL_SEQ_MATCH
-                            : ln.phase == 3 ? MAIL_SEQ_SOLVE
-                            : ln.phase == 4 ? MAIL_SEQ_ICP_BOX
-                                            : MAIL_SEQ_ICP;
-            all = all && mail_ready(s, idx, s.seq);
+            all = all && mail_ready(s, lane_mail_index(ln.phase), s.seq);
           }
           if (!all) {
-            snprintf(h->err, sizeof(h->err), "batch lane drained its stream without publishing phase %d", ln.phase);
+            snprintf(h->err, sizeof(h->err), "batch lane drained its stream without publishing phase %d", (int)ln.phase);
             rc = QTR_ERR_HIP;
           }
         } else if (q != hipErrorNotReady) {

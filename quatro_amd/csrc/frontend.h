@@ -1,6 +1,7 @@
 // frontend.h — buffers and launchers of the front-end kernels (frontend.hip, match.hip).
 #pragma once
 #include "common.h"
+#include "front_verdict.h"  // the per-cloud device counters (CNT_*) and what the host decides from them
 
 #define QTR_KMAX 256        // entries of a point's radius-neighbour list kept in its own fixed-stride slot; a longer list
                             // lives in the cloud's long-list arena (nbr_big_*), its offset in word 0 of the slot
@@ -8,21 +9,12 @@
 #define RADIX_TILE 1024     // elements per radix-sort workgroup (four wavefronts, 256 keys each)
 #define NORM_BINS 192       // bins of width 1 over sqrt(|descriptor|^2) (<= sqrt(3 * 100^2) = 173.3)
 
-// per-cloud device counters (CloudBufs::counts, 16 ints)
 // the largest cloud the matcher takes: k_recheck_filter's per-wave lists hold (listed column << 20 | base row) in 32 bits —
 // 20 bits of base row (padded to whole 32-row tiles), 12 of column; qtr_create refuses limits above it
 #define QTR_NN_MAX_ROWS ((1 << 20) - 32)
-enum { CNT_NVOX = 0, CNT_VOX_OVERFLOW = 1, CNT_NBR_TOTAL = 2, CNT_NBR_OVERFLOW = 3, CNT_GRID_OVERFLOW = 4, CNT_KMAX = 5,
-       CNT_SORT_BITS = 6 /* significant bits of the voxel sort's keys */,
-       CNT_NBR_ARENA = 7 /* entries of the long-list arena handed out */, CNT_NBR_CAPACITY = 8 /* ... it was too small */,
-       CNT_VOX_TAILERR = 9 /* sticky: SOME tile of k2_vox_centroids (or of k2_cell_scan) gave up its look-back */,
-       CNT_NCELL = 10 /* cells of the neighbour-search grid over this cloud's bounding box (voxel stage, for the cell side
-                         the caller named): up to QTR_CELL_CAP the FPFH chain places the points by a dense cell table */ };
 // the largest neighbour-search grid served by the dense cell table (k2_cell_count / _scan / _place); above it — 160 x 160 x 30 m
 // at 0.75 m cells is 1.8 M — the chain sorts packed cell keys as it did until round 6
 #define QTR_CELL_CAP (1 << 21)
-// CNT_NBR_OVERFLOW: some point of the cloud has more than QTR_KMAX neighbours (k2_neighbors_big has work to do);
-// CNT_KMAX: the longest such list
 // matcher device counters (FrontBufs::mcounts, 16 ints)
 // MC_RECHECKx: rows sent to the exact re-check; MC_RECHECKx + 2: rows settled by the two-candidate exact compare
 // MC_NQ0 / MC_NHIT: query counts of the two nearest-neighbour directions (device-side: the second direction only asks
