@@ -33,8 +33,14 @@
 // their inf/NaN in the reference expression), s + t > 65536, non-finite input — is decided by pair_consistent(), the
 // reference expression in binary64 evaluated verbatim.  The result is bit-identical to evaluating the reference
 // expression everywhere (the margin is orders of magnitude wider than its own rounding).
+// The squared form decides only outside a relative band of 1e-9 around (s + t - beta^2)^2 = 4 s t, and only for lengths
+// within a factor 16 of each other (s, t within 256): the reference's a/b - 1 is rounded at ~2^-52 a/b and beta/b
+// likewise, so its decision is its roundings' wherever ||a - b| - beta| / min(a, b) is below ~2^-50 * 2.5 max / min, while
+// the band leaves the squared form every pair with ||a - b| - beta| / min(a, b) above ~4e-10 min / max — the two overlap
+// from a ratio of ~1e3 on (tests/graph_cases.py: extreme_ratio_tims; a near-duplicate in one cloud against a TIM of
+// beta + its length in the other).  At ratios <= 16 they are a factor ~700 apart.
 __device__ __forceinline__ bool pair_consistent(double s, double t, double beta, double beta2) {
-  if (s > 0.0 && t > 0.0) {
+  if (s > 0.0 && t > 0.0 && s < 256.0 * t && t < 256.0 * s) {
     const double u = s + t - beta2;
     if (u > 0.0) {
       const double lhs = u * u, rhs = 4.0 * s * t;
@@ -331,7 +337,9 @@ __global__ __launch_bounds__(GB2_THREADS, EXT ? 7 : 8) void k_graph_build(ViewEx
 // only when |z| > 2.4 |D| delta + 1.3 (beta^2 delta + delta^2) + u beta^4 + 1e-7 and P > 0.505 beta^2 + delta (s + t > 1.01 beta^2: the
 // squared form is valid, as in the other two kernels); the rest — a band ~1e-4 of the pairs wide at +-50 m, TIMs shorter
 // than beta — and every pair of a tile whose norms leave binary16's range (or are not finite) gets pair_consistent(), the
-// reference expression in binary64: the bit matrix is identical to the other two kernels' (tests/gpu_graph_bench.py).
+// reference expression in binary64: the bit matrix is identical to the other two kernels' and to the reference's
+// (tests/test_gpu_graph_edges.py on the adversarial inputs of tests/graph_cases.py; tests/test_graph_cases_cpu.py holds a
+// numpy model of gbm_records against the software part of the bound above, 27.1 - 16.1 = 11 u M + 2e-6).
 // Per entry the vector unit still does: P, D, -beta^2 P + beta^4 / 4, z (four packed instructions per two entries), the
 // margin (one fma), |z| - margin (one), two sign-bit shifts, half a min3 for the short-TIM test: 6.5 — against 12 + 5.
 #define GBM_KDELTA 1.8e-6f

@@ -33,8 +33,11 @@ if mode in ("check", "both"):
         bad += 0 if ok else 1
         print(f"L={L}: bitmap {'==' if np.array_equal(bm, ref) else '!='} oracle, edges {int(r['n_edges'])}, "
               f"clique {r['clique'].size} {'ok' if ok else 'MISMATCH'}", flush=True)
-    # noise bounds small enough that the binary32 screen must not decide anything (margin = inf), and a mid one
-    for nb_, L in ((0.002, 700), (0.004, 300), (0.02, 1500), (3.0, 900)):
+    # noise bounds small enough that the screens must not decide anything (margin = inf; the MFMA kernel's `safe` is
+    # false at beta <= 0.01), and a mid one — below GBM_MIN_L = 2048 (the tile kernel) and above it (k_graph_build_mfma);
+    # the pytest form of this on adversarial inputs is tests/test_gpu_graph_edges.py
+    for nb_, L in ((0.002, 700), (0.004, 300), (0.02, 1500), (3.0, 900), (0.002, 2500), (0.004, 2049), (0.02, 3000),
+                   (3.0, 2100)):
         s, t, _, _ = synth.correspondences(L, 0.2, seed=L, noise=nb_ / 3)
         p2 = ql.demo_params(noise_bound=nb_)
         h.solve(s, t, p2)
