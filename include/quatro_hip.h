@@ -690,6 +690,58 @@ QTR_API int qtr_evaluate_keyframes(qtr_handle* h, int slot, const qtr_keyframe* 
 QTR_API int qtr_evaluate_keyframes_batch(qtr_handle* h, int slot, const qtr_eval_kf_pair* pairs, int B,
                                          const qtr_eval_params* prm, qtr_eval_result* results);
 
+/* Robust pose-graph optimisation: from the edges (T, Omega) that qtr_evaluate* emits to corrected keyframe poses — Open3D's
+ * GlobalOptimizationLevenbergMarquardt with the line process of Choi et al. 2015 over the uncertain edges, on the device,
+ * bit-reproducible.  The arithmetic and every order of summation are include/qtr_pgo_math.h.
+ *   poses      n_nodes row-major 4x4, keyframe i's frame -> map frame (what qtr_keyframe_merge takes as poses[i])
+ *   fixed      one byte per node, non-zero = held; NULL = node 0 alone is held
+ *   edge e     Z[e] maps keyframe src[e]'s frame into keyframe dst[e]'s frame (a registration's T with src = the source /
+ *              query, dst = the target / candidate); info[e] is the evaluation's `information` (row-major 6x6, [omega | v],
+ *              upper triangle read); uncertain[e] non-zero = under the line process (NULL: none)
+ *   residual   vee(X_dst^-1 X_src Z^-1): Z^-1 on the RIGHT, the perturbation the information matrix was formed under
+ *              (Open3D puts it on the left)
+ *   weights    w = 1 for a certain edge, (mu / (mu + chi2))^2 for an uncertain one, mu = line_process_weight (<= 0: off);
+ *              weight_out[e] is the final one, n_pruned counts the uncertain edges below edge_prune_threshold
+ * The linear system of every step is solved by block-Jacobi preconditioned conjugate gradients inside ONE workgroup.
+ * Synchronous and stateless; an arena of its own per slot (allocated on first use, grown on demand); one host wait per LM
+ * iteration.  Registration, ICP and evaluation state of the slot are left alone.  A connected component without a fixed node
+ * is not an error (the damping keeps the system definite; the component keeps its gauge).  No edge, or no free node: QTR_OK,
+ * stop_reason QTR_PGO_STOP_NOTHING, poses_out = poses, weights 1, objectives 0.
+ * QTR_ERR_BAD_ARG, before anything is enqueued: a NULL array, n_nodes < 1, n_edges < 0, an edge index out of range or
+ * src = dst, a non-finite entry in rows 0 - 2 of a pose or a Z or in the upper triangle of an info, no fixed node, a
+ * tolerance (rel_tol, step_tol, tau, pcg_tol) that is not finite and positive, an iteration count out of range, a weight or
+ * threshold that is not finite.  n_nodes > QTR_PGO_MAX_NODES or n_edges > QTR_PGO_MAX_EDGES: QTR_ERR_CAPACITY. */
+#define QTR_PGO_MAX_NODES 65536
+#define QTR_PGO_MAX_EDGES (1 << 20)
+#define QTR_PGO_MAX_ITERATIONS 65536
+#define QTR_PGO_STOP_MAX_ITERATIONS 1 /* trial steps evaluated */
+#define QTR_PGO_STOP_RELATIVE 2       /* an accepted step lowered the objective by no more than rel_tol of it */
+#define QTR_PGO_STOP_STEP 3           /* max |delta| < step_tol */
+#define QTR_PGO_STOP_LAMBDA 4         /* the damping passed its ceiling (1e32) */
+#define QTR_PGO_STOP_NOTHING 5        /* no edge or no free node */
+typedef struct qtr_pgo_params {
+  int max_iterations;          /* 100 LM trial steps */
+  int pcg_max_iterations;      /* 500 per step */
+  double rel_tol;              /* 1e-6 */
+  double step_tol;             /* 1e-9 */
+  double tau;                  /* 1e-5: lambda_0 = tau max diag(H) */
+  double pcg_tol;              /* 1e-8: |res|^2 <= pcg_tol^2 |g|^2 */
+  double line_process_weight;  /* 0: off */
+  double edge_prune_threshold; /* 0.25 */
+  int reserved[8];
+} qtr_pgo_params;
+typedef struct qtr_pgo_result {
+  int status, valid, iterations, accepted, pcg_iterations_total, stop_reason, n_pruned, reserved;
+  double objective_initial, objective_final, lambda_final;
+} qtr_pgo_result;
+QTR_API void qtr_default_pgo_params(qtr_pgo_params* p);
+/* poses / poses_out: 16 n_nodes doubles; Z: 16 n_edges; info: 36 n_edges; weight_out: n_edges doubles or NULL.  All in host
+ * memory.  poses_out may be poses. */
+QTR_API int qtr_pgo_optimize(qtr_handle* h, int slot, int n_nodes, const double* poses, const unsigned char* fixed, int n_edges,
+                             const int* src, const int* dst, const double* Z, const double* info,
+                             const unsigned char* uncertain, const qtr_pgo_params* prm, double* poses_out, double* weight_out,
+                             qtr_pgo_result* res);
+
 /* Inspection of intermediates of the LAST call on a slot (tests / parity debugging).  Copies up to
  * `bytes` bytes to host memory `dst`; returns the number of bytes the item holds, or <0 on error. */
 #define QTR_DBG_GRAPH_BITMAP 1   /* uint64[L][ceil(L/64)] adjacency, original labels */
@@ -717,6 +769,9 @@ QTR_API int qtr_evaluate_keyframes_batch(qtr_handle* h, int slot, const qtr_eval
 #define QTR_DBG_ICP_TIMES 17     /* float[2] last ICP call: grid build, iterations (device milliseconds) */
 #define QTR_DBG_EVAL_CORR 18     /* int32[n_s] target index of every source point of the last evaluation (a batch: its
                                     first pair); -1: none */
+#define QTR_DBG_PGO_TRACE 19     /* double[1 + iterations][8] of the last optimisation; row 0 the start, row k trial step k:
+                                    F at the trial poses, lambda after the decision, rho, accepted, PCG iterations of the
+                                    step, F kept, the gain's denominator, max |delta| */
 QTR_API long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t bytes);
 
 /* Evaluates the shared deterministic math (include/qtr_math.h) ON THE DEVICE, for the test that pins

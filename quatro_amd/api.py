@@ -631,3 +631,71 @@ def close_loop(handle, index, keyframes, query_kf, k, id_lo=0, id_hi=None, fp=No
     if out["best"] >= 0:
         out["best_id"] = matches[out["best"]]["id"]
     return out
+
+
+def default_line_process_weight(edges, max_correspondence_distance, preference_loop_closure=1.0):
+    """Open3D's rule for the line process weight mu: preference_loop_closure x max_correspondence_distance^2 x the mean of
+    information[5][5] over the UNCERTAIN edges (information[5][5] is n_corr in the evaluation's matrix).  edges: (s, t, T,
+    information, uncertain) tuples.  0.0 without an uncertain edge (the line process is then off)."""
+    n = [float(np.asarray(e[3], dtype=np.float64).reshape(6, 6)[5, 5]) for e in edges if e[4]]
+    if not n:
+        return 0.0
+    return float(preference_loop_closure) * float(max_correspondence_distance) ** 2 * (sum(n) / len(n))
+
+
+class PoseGraph:
+    """A pose graph on the host: nodes (4 x 4 poses, keyframe frame -> map frame, what make_submap and close_loop(poses=)
+    take) and edges (s, t, T, information, uncertain) with T mapping keyframe s's frame into keyframe t's — a registration's
+    T with s the source / query and t the target / candidate — and information the 6 x 6 of the evaluation.  optimize()
+    runs Handle.optimize_pose_graph (qtr_pgo_optimize) and writes the poses back."""
+
+    def __init__(self):
+        self.poses, self.fixed, self.edges = [], [], []
+
+    def add_node(self, pose, fixed=False) -> int:
+        self.poses.append(np.array(pose, dtype=np.float64).reshape(4, 4))
+        self.fixed.append(bool(fixed))
+        return len(self.poses) - 1
+
+    def add_edge(self, s, t, T, information, uncertain=False) -> int:
+        s, t = int(s), int(t)
+        if not (0 <= s < len(self.poses) and 0 <= t < len(self.poses)) or s == t:
+            raise ValueError(f"PoseGraph.add_edge: ({s}, {t}) does not join two different nodes of {len(self.poses)}")
+        self.edges.append((s, t, np.array(T, dtype=np.float64).reshape(4, 4),
+                           np.array(information, dtype=np.float64).reshape(6, 6), bool(uncertain)))
+        return len(self.edges) - 1
+
+    def add_odometry(self, s, t, record, evaluation) -> int:
+        """A certain edge from a registration of keyframe s (source) against keyframe t (target): T from `record` (a
+        registration or refinement record), information from `evaluation` (an evaluation record at that T)."""
+        if not record.get("valid", True) or evaluation is None:
+            raise ValueError("PoseGraph.add_odometry: the registration is not valid or was not evaluated")
+        return self.add_edge(s, t, record["T"], evaluation["information"], False)
+
+    def add_loop(self, query_id, loop, use="best", uncertain=True) -> int:
+        """The loop edge of a close_loop(..., evaluate=...) output: query_id -> the chosen candidate's index entry.  use:
+        "best" or a candidate's position.  T is the refined one where the refinement ran (its status is QTR_OK), else the
+        registration's; information comes from "evaluations".  Raises when close_loop ran without evaluate, or when the
+        chosen candidate was not valid."""
+        if "evaluations" not in loop:
+            raise ValueError("PoseGraph.add_loop: close_loop was called without evaluate: there is no information matrix")
+        i = int(loop["best"]) if use == "best" else int(use)
+        if not 0 <= i < len(loop["records"]) or loop["evaluations"][i] is None:
+            raise ValueError("PoseGraph.add_loop: no valid, evaluated candidate to take the edge from")
+        ref = loop.get("refined")
+        T = ref[i]["T"] if ref and ref[i].get("status") == 0 else loop["records"][i]["T"]
+        return self.add_edge(query_id, loop["matches"][i]["id"], T, loop["evaluations"][i]["information"], uncertain)
+
+    def optimize(self, handle, params=None, slot=0) -> dict:
+        """Optimises, writes the poses back and returns the result dict with "weights" and "pruned" (the indices of the
+        uncertain edges whose final weight is below params.edge_prune_threshold)."""
+        prm = params or _ql.default_pgo_params()
+        if not any(self.fixed) and self.fixed:
+            fixed = None  # (node 0 is held)
+        else:
+            fixed = self.fixed
+        X, w, res = handle.optimize_pose_graph(np.stack(self.poses), self.edges, fixed, prm, slot)
+        self.poses = [X[i].copy() for i in range(X.shape[0])]
+        res["weights"] = w
+        res["pruned"] = [k for k, e in enumerate(self.edges) if e[4] and w[k] < prm.edge_prune_threshold]
+        return res

@@ -22,6 +22,7 @@ SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc"
     os.path.join("..", "..", "include", "qtr_math.h"), os.path.join("..", "..", "include", "qtr_icp_math.h"),
     os.path.join("..", "..", "include", "qtr_place_math.h"),
     os.path.join("..", "..", "include", "qtr_submap_math.h"), os.path.join("..", "..", "include", "qtr_eval_math.h"),
+    os.path.join("..", "..", "include", "qtr_pgo_math.h"),
     os.path.join("..", "..", "include", "quatro_hip.h")]
 
 

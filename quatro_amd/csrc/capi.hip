@@ -58,6 +58,7 @@ struct Slot {
   int last_ns = 0, last_nt = 0;
   IcpBufs icp;                   // ICP arena (allocated on first use: icp.hip)
   EvalBufs eval;                 // evaluation arena (allocated on first use, grown on demand: eval.hip)
+  PgoBufs pgo;                   // pose-graph optimisation arena (allocated on first use, grown on demand: pgo.hip)
   int reg_ready = 0;             // 1: the last call on this slot was a registration (qtr_refine_pair may use its clouds)
   double reg_T[16] = {};         // ... and its transform
   int icp_ns = 0, icp_iters = 0; // source points and updates of the last ICP call (debug ids)
@@ -452,6 +453,7 @@ void qtr_destroy(qtr_handle* h) {
     if (s.ex_arena) (void)hipFree(s.ex_arena);
     icp_free(s.icp);
     eval_free(s.eval);
+    pgo_free(s.pgo);
     if (s.place.arena) (void)hipFree(s.place.arena);
     if (s.place.pin) (void)hipHostFree(s.place.pin);
     if (s.merge_pin) (void)hipHostFree(s.merge_pin);
@@ -3848,6 +3850,168 @@ int qtr_evaluate_keyframes_batch(qtr_handle* h, int slot, const qtr_eval_kf_pair
   return rc;
 }
 
+// ---- pose-graph optimisation (pgo.hip) ---------------------------------------------------------------------------------
+void qtr_default_pgo_params(qtr_pgo_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->max_iterations = 100;
+  p->pcg_max_iterations = 500;
+  p->rel_tol = 1e-6;
+  p->step_tol = 1e-9;
+  p->tau = 1e-5;
+  p->pcg_tol = 1e-8;
+  p->line_process_weight = 0.0;
+  p->edge_prune_threshold = 0.25;
+}
+
+static bool pgo_finite(double x) { return (x - x) == 0.0; }
+
+// everything qtr_pgo_optimize refuses, before a device is touched
+static int check_pgo_args(qtr_handle* h, int N, const double* poses, const unsigned char* fixed, int E, const int* src,
+                          const int* dst, const double* Z, const double* info, const qtr_pgo_params* prm,
+                          const double* poses_out, const qtr_pgo_result* res) {
+  auto bad = [&](const char* fmt, int a, int b) {
+    snprintf(h->err, sizeof(h->err), fmt, a, b);
+    return QTR_ERR_BAD_ARG;
+  };
+  if (!res || !prm || !poses || !poses_out) return bad("qtr_pgo_optimize: poses, poses_out, params and result must not be NULL", 0, 0);
+  if (N < 1 || E < 0) return bad("qtr_pgo_optimize: %d nodes (>= 1), %d edges (>= 0)", N, E);
+  if (E > 0 && (!src || !dst || !Z || !info)) return bad("qtr_pgo_optimize: src, dst, Z and info must not be NULL with %d edges", E, 0);
+  const double tol[4] = {prm->rel_tol, prm->step_tol, prm->tau, prm->pcg_tol};
+  for (int k = 0; k < 4; ++k)
+    if (!pgo_finite(tol[k]) || !(tol[k] > 0.0))
+      return bad("qtr_pgo_optimize: tolerance %d (rel_tol, step_tol, tau, pcg_tol) is not finite and positive", k, 0);
+  if (prm->max_iterations < 0 || prm->max_iterations > QTR_PGO_MAX_ITERATIONS || prm->pcg_max_iterations < 1)
+    return bad("qtr_pgo_optimize: max_iterations %d (0 .. 65536), pcg_max_iterations %d (>= 1)", prm->max_iterations,
+               prm->pcg_max_iterations);
+  if (!pgo_finite(prm->line_process_weight) || !pgo_finite(prm->edge_prune_threshold))
+    return bad("qtr_pgo_optimize: line_process_weight and edge_prune_threshold must be finite", 0, 0);
+  if (N > QTR_PGO_MAX_NODES || E > QTR_PGO_MAX_EDGES) {
+    snprintf(h->err, sizeof(h->err), "qtr_pgo_optimize: %d nodes / %d edges exceed QTR_PGO_MAX_NODES / QTR_PGO_MAX_EDGES", N, E);
+    return QTR_ERR_CAPACITY;
+  }
+  if (fixed) {
+    bool any = false;
+    for (int i = 0; i < N; ++i) any = any || fixed[i] != 0;
+    if (!any) return bad("qtr_pgo_optimize: no fixed node among %d", N, 0);
+  }
+  for (int i = 0; i < N; ++i)
+    for (int k = 0; k < 12; ++k)
+      if (!pgo_finite(poses[(size_t)16 * i + k])) return bad("qtr_pgo_optimize: pose %d has a non-finite entry in rows 0 - 2", i, 0);
+  for (int e = 0; e < E; ++e) {
+    if (src[e] < 0 || src[e] >= N || dst[e] < 0 || dst[e] >= N) return bad("qtr_pgo_optimize: edge %d names a node outside 0 .. %d", e, N - 1);
+    if (src[e] == dst[e]) return bad("qtr_pgo_optimize: edge %d joins node %d to itself", e, src[e]);
+    for (int k = 0; k < 12; ++k)
+      if (!pgo_finite(Z[(size_t)16 * e + k])) return bad("qtr_pgo_optimize: Z of edge %d has a non-finite entry in rows 0 - 2", e, 0);
+    for (int a = 0; a < 6; ++a)
+      for (int b = a; b < 6; ++b)
+        if (!pgo_finite(info[(size_t)36 * e + 6 * a + b]))
+          return bad("qtr_pgo_optimize: info of edge %d has a non-finite entry in its upper triangle", e, 0);
+  }
+  return QTR_OK;
+}
+
+int qtr_pgo_optimize(qtr_handle* h, int slot, int N, const double* poses, const unsigned char* fixed, int E, const int* src,
+                     const int* dst, const double* Z, const double* info, const unsigned char* uncertain,
+                     const qtr_pgo_params* prm, double* poses_out, double* weight_out, qtr_pgo_result* res) {
+  Slot* sp = peek_slot(h, slot);  // (registration, ICP and evaluation state of the slot stay what they were)
+  if (!sp) return QTR_ERR_BAD_ARG;
+  int rc = check_pgo_args(h, N, poses, fixed, E, src, dst, Z, info, prm, poses_out, res);
+  if (rc != QTR_OK) {
+    if (res) {
+      memset(res, 0, sizeof(*res));
+      res->status = rc;
+    }
+    return rc;
+  }
+  memset(res, 0, sizeof(*res));
+  Slot& s = *sp;
+  std::vector<unsigned char> fx((size_t)N, 0), un((size_t)std::max(E, 1), 0);
+  int n_free = 0;
+  for (int i = 0; i < N; ++i) {
+    fx[i] = fixed ? (fixed[i] ? 1 : 0) : (i == 0 ? 1 : 0);
+    n_free += fx[i] ? 0 : 1;
+  }
+  for (int e = 0; e < E; ++e) un[e] = (uncertain && uncertain[e]) ? 1 : 0;
+  PgoBufs& P = s.pgo;
+  if (E == 0 || n_free == 0) {  // nothing to optimise
+    if (poses_out != poses) memmove(poses_out, poses, sizeof(double) * 16 * (size_t)N);
+    if (weight_out)
+      for (int e = 0; e < E; ++e) weight_out[e] = 1.0;
+    res->valid = 1;
+    res->stop_reason = QTR_PGO_STOP_NOTHING;
+    P.last_rows = 0;
+    return res->status = QTR_OK;
+  }
+  QtrPgoCfg cfg;
+  cfg.rel_tol = prm->rel_tol;
+  cfg.step_tol = prm->step_tol;
+  cfg.tau = prm->tau;
+  cfg.pcg_tol = prm->pcg_tol;
+  cfg.mu = prm->line_process_weight;
+  cfg.max_iterations = prm->max_iterations;
+  cfg.pcg_max_iterations = prm->pcg_max_iterations;
+  std::vector<int> off((size_t)N + 1), inc((size_t)2 * E);
+  qtr_pgo_incidence(N, E, src, dst, off.data(), inc.data());
+  rc = [&]() -> int {
+    QTR_HIP_TRY(h, hipSetDevice(h->device));
+    QTR_HIP_TRY(h, pgo_reserve(P, pgo_arena_bytes(N, E, cfg.max_iterations)));
+    PgoView v;
+    memset((void*)&v, 0, sizeof(v));
+    pgo_carve(P, N, E, cfg.max_iterations, v);
+    v.cfg = cfg;
+    P.last_trace = v.trace;
+    P.last_rows = 0;
+    const hipStream_t st = s.stream;
+    qtr_pgo_init(&P.pin[0]);
+    const size_t n = (size_t)N, e = (size_t)E;
+    QTR_HIP_TRY(h, hipMemcpyAsync((void*)v.fixed, fx.data(), n, hipMemcpyHostToDevice, st));
+    QTR_HIP_TRY(h, hipMemcpyAsync((void*)v.unc, un.data(), e, hipMemcpyHostToDevice, st));
+    QTR_HIP_TRY(h, hipMemcpyAsync((void*)v.src, src, e * 4, hipMemcpyHostToDevice, st));
+    QTR_HIP_TRY(h, hipMemcpyAsync((void*)v.dst, dst, e * 4, hipMemcpyHostToDevice, st));
+    QTR_HIP_TRY(h, hipMemcpyAsync((void*)v.off, off.data(), (n + 1) * 4, hipMemcpyHostToDevice, st));
+    QTR_HIP_TRY(h, hipMemcpyAsync((void*)v.inc, inc.data(), 2 * e * 4, hipMemcpyHostToDevice, st));
+    QTR_HIP_TRY(h, hipMemcpyAsync((void*)v.Z, Z, e * 128, hipMemcpyHostToDevice, st));
+    QTR_HIP_TRY(h, hipMemcpyAsync((void*)v.info, info, e * 288, hipMemcpyHostToDevice, st));
+    for (int k = 0; k < 2; ++k) QTR_HIP_TRY(h, hipMemcpyAsync(v.X[k], poses, n * 128, hipMemcpyHostToDevice, st));
+    QTR_HIP_TRY(h, hipMemcpyAsync(v.st, &P.pin[0], sizeof(QtrPgoState), hipMemcpyHostToDevice, st));
+    QTR_HIP_TRY(h, hipMemsetAsync(v.ticket, 0, 64, st));
+    const QtrPgoState& now = P.pin[1];
+    // one (linearize, step) pair and one host wait per LM iteration; the last pair's step returns at once
+    for (int it = 0; it <= cfg.max_iterations; ++it) {
+      hipLaunchKernelGGL(k_pgo_linearize, dim3(qtr_div_up(E, 256)), dim3(256), 0, st, v);
+      hipLaunchKernelGGL(k_pgo_step, dim3(1), dim3(QTR_PGO_THREADS), 0, st, v);
+      QTR_HIP_TRY(h, hipGetLastError());
+      QTR_HIP_TRY(h, hipMemcpyAsync(&P.pin[1], v.st, sizeof(QtrPgoState), hipMemcpyDeviceToHost, st));
+      QTR_HIP_TRY(h, hipStreamSynchronize(st));
+      if (now.stop) break;
+    }
+    if (!now.stop) {
+      snprintf(h->err, sizeof(h->err), "qtr_pgo_optimize: the device did not stop after %d iterations", cfg.max_iterations);
+      return QTR_ERR_HIP;
+    }
+    QTR_HIP_TRY(h, hipMemcpyAsync(poses_out, v.X[now.cur], n * 128, hipMemcpyDeviceToHost, st));
+    std::vector<double> w(e);
+    QTR_HIP_TRY(h, hipMemcpyAsync(w.data(), v.Ew[now.cur], e * 8, hipMemcpyDeviceToHost, st));
+    QTR_HIP_TRY(h, hipStreamSynchronize(st));
+    P.last_rows = 1 + now.trials;
+    res->iterations = now.trials;
+    res->accepted = now.accepted;
+    res->pcg_iterations_total = now.pcg_total;
+    res->stop_reason = now.reason;
+    res->objective_initial = now.F0;
+    res->objective_final = now.F;
+    res->lambda_final = now.lambda;
+    res->valid = pgo_finite(now.F) ? 1 : 0;
+    for (int k = 0; k < E; ++k) {
+      if (un[k] && w[k] < prm->edge_prune_threshold) res->n_pruned += 1;
+      if (weight_out) weight_out[k] = w[k];
+    }
+    return QTR_OK;
+  }();
+  return res->status = rc;
+}
+
 long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t bytes) {
   Slot* sp = peek_slot(h, slot);
   if (!sp) return -1;
@@ -3889,6 +4053,7 @@ long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t b
     case QTR_DBG_ICP_TRACE: src = s.icp.v.trace; have = s.icp.v.trace ? (size_t)s.icp_iters * 18 * 8 : 0; break;
     case QTR_DBG_ICP_TIMES: src = s.icp_ms; have = sizeof(s.icp_ms); break;
     case QTR_DBG_EVAL_CORR: src = s.eval.last_corr; have = s.eval.last_corr ? (size_t)s.eval.last_ns * 4 : 0; break;
+    case QTR_DBG_PGO_TRACE: src = s.pgo.last_trace; have = s.pgo.last_trace ? (size_t)s.pgo.last_rows * QTR_PGO_TRACE * 8 : 0; break;
     default: return -1;
   }
   const size_t n = have < bytes ? have : bytes;

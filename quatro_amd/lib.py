@@ -112,6 +112,18 @@ class EvalKfPair(C.Structure):
     _fields_ = [("source", C.c_void_p), ("target", C.c_void_p), ("T", C.c_double * 16)]
 
 
+class PgoParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int), ("pcg_max_iterations", C.c_int), ("rel_tol", C.c_double),
+                ("step_tol", C.c_double), ("tau", C.c_double), ("pcg_tol", C.c_double),
+                ("line_process_weight", C.c_double), ("edge_prune_threshold", C.c_double), ("reserved", C.c_int * 8)]
+
+
+class PgoResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("valid", C.c_int), ("iterations", C.c_int), ("accepted", C.c_int),
+                ("pcg_iterations_total", C.c_int), ("stop_reason", C.c_int), ("n_pruned", C.c_int), ("reserved", C.c_int),
+                ("objective_initial", C.c_double), ("objective_final", C.c_double), ("lambda_final", C.c_double)]
+
+
 class KeyframeInfo(C.Structure):
     _fields_ = [("n_points", C.c_int), ("n_voxels", C.c_int), ("voxel_size", C.c_float), ("normal_radius", C.c_float),
                 ("fpfh_radius", C.c_float), ("passed_through", C.c_int), ("device_bytes", C.c_ulonglong)]
@@ -140,6 +152,9 @@ PLACE_MAX_K = 64
 SUBMAP_MAX_KEYFRAMES = 64
 EVAL_MAX_PAIRS = 64
 DBG_EVAL_CORR = 18
+DBG_PGO_TRACE = 19
+PGO_MAX_NODES, PGO_MAX_EDGES, PGO_MAX_ITERATIONS, PGO_TRACE = 65536, 1 << 20, 65536, 8
+PGO_STOP_MAX_ITERATIONS, PGO_STOP_RELATIVE, PGO_STOP_STEP, PGO_STOP_LAMBDA, PGO_STOP_NOTHING = 1, 2, 3, 4, 5
 
 EXPORTS = [
     "qtr_create", "qtr_destroy", "qtr_last_error", "qtr_default_limits", "qtr_default_params", "qtr_demo_params",
@@ -154,6 +169,7 @@ EXPORTS = [
     "qtr_place_query_desc",
     "qtr_default_eval_params", "qtr_evaluate", "qtr_evaluate_pair", "qtr_evaluate_keyframes",
     "qtr_evaluate_keyframes_batch",
+    "qtr_default_pgo_params", "qtr_pgo_optimize",
 ]
 
 _lib = None
@@ -337,6 +353,11 @@ def load(path: str | None = None):
                                            C.POINTER(EvalResult)]
     lib.qtr_evaluate_keyframes_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(EvalKfPair), C.c_int, C.POINTER(EvalParams),
                                                  C.POINTER(EvalResult)]
+    lib.qtr_default_pgo_params.argtypes = [C.POINTER(PgoParams)]
+    lib.qtr_default_pgo_params.restype = None
+    lib.qtr_pgo_optimize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(PgoParams), C.c_void_p, C.c_void_p,
+                                     C.POINTER(PgoResult)]
     lib.qtr_default_place_params.argtypes = [C.POINTER(PlaceParams)]
     lib.qtr_place_index_create.argtypes = [C.c_void_p, C.POINTER(PlaceParams), C.c_int, C.POINTER(C.c_void_p)]
     lib.qtr_place_index_destroy.restype = None
@@ -408,6 +429,38 @@ def default_eval_params(**kw) -> EvalParams:
     for k, v in kw.items():
         setattr(p, k, v)
     return p
+
+
+def default_pgo_params(**kw) -> PgoParams:
+    """The pose-graph optimisation's knobs (qtr_default_pgo_params), overridden by keyword."""
+    p = PgoParams()
+    load().qtr_default_pgo_params(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def pgo_arrays(poses, edges, fixed=None):
+    """The arrays qtr_pgo_optimize takes, from poses (N x 4 x 4) and edges: (s, t, Z 4x4, information 6x6, uncertain)
+    tuples.  Returns (poses [N, 16], fixed uint8 [N] or None, src, dst int32 [E], Z [E, 16], info [E, 36], uncertain uint8)."""
+    X = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 16))
+    E = len(edges)
+    src = np.ascontiguousarray([e[0] for e in edges], dtype=np.int32).reshape(E)
+    dst = np.ascontiguousarray([e[1] for e in edges], dtype=np.int32).reshape(E)
+    Z = np.ascontiguousarray(np.asarray([np.asarray(e[2], dtype=np.float64).reshape(16) for e in edges],
+                                        dtype=np.float64).reshape(E, 16))
+    info = np.ascontiguousarray(np.asarray([np.asarray(e[3], dtype=np.float64).reshape(36) for e in edges],
+                                           dtype=np.float64).reshape(E, 36))
+    unc = np.ascontiguousarray([1 if e[4] else 0 for e in edges], dtype=np.uint8).reshape(E)
+    fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed).astype(bool).astype(np.uint8).reshape(-1))
+    return X, fx, src, dst, Z, info, unc
+
+
+def _pgo_dict(res: PgoResult) -> dict:
+    return {"status": res.status, "valid": bool(res.valid), "iterations": res.iterations, "accepted": res.accepted,
+            "pcg_iterations_total": res.pcg_iterations_total, "stop_reason": res.stop_reason, "n_pruned": res.n_pruned,
+            "objective_initial": res.objective_initial, "objective_final": res.objective_final,
+            "lambda_final": res.lambda_final}
 
 
 def _eval_dict(res: EvalResult) -> dict:
@@ -1222,6 +1275,21 @@ class Handle:
         res = (EvalResult * max(B, 1))()
         self._check(self._lib.qtr_evaluate_keyframes_batch(self._h, slot, arr, B, C.byref(prm), res))
         return [_eval_dict(res[i]) for i in range(B)]
+
+    def optimize_pose_graph(self, poses, edges, fixed=None, params: PgoParams | None = None, slot: int = 0):
+        """Robust pose-graph optimisation on the device (qtr_pgo_optimize).  poses: N x 4 x 4 (keyframe frame -> map frame);
+        edges: (s, t, Z, information, uncertain) tuples, Z mapping keyframe s's frame into keyframe t's; fixed: N flags
+        (None: node 0).  Returns (poses_out [N, 4, 4], weights [E], result dict)."""
+        prm = params or default_pgo_params()
+        X, fx, src, dst, Z, info, unc = pgo_arrays(poses, edges, fixed)
+        if fx is not None and fx.shape[0] != X.shape[0]:
+            raise ValueError("fixed must have one flag per node")
+        out, w, res = np.zeros_like(X), np.zeros(len(edges)), PgoResult()
+        rc = self._lib.qtr_pgo_optimize(self._h, slot, int(X.shape[0]), X.ctypes.data, None if fx is None else fx.ctypes.data,
+                                        len(edges), src.ctypes.data, dst.ctypes.data, Z.ctypes.data, info.ctypes.data,
+                                        unc.ctypes.data, C.byref(prm), out.ctypes.data, w.ctypes.data, C.byref(res))
+        self._check(rc)
+        return out.reshape(-1, 4, 4), w, _pgo_dict(res)
 
     def debug_fetch(self, what: int, dtype, slot: int = 0) -> np.ndarray:
         nbytes = self._lib.qtr_debug_fetch(self._h, slot, what, None, 0)
