@@ -25,7 +25,7 @@
 #include "qtr_math.h"
 
 #define QTR_ICP_CHUNK 256  // source points per workgroup / partial sum
-#define QTR_ICP_NT 32      // terms per point (30 used, padded)
+#define QTR_ICP_NT 32      // terms per point (30 used, 31 by method 3; padded)
 
 #define QTR_ICP_GICP_EPSILON 1e-3  // plane regularisation of method 2 (pcl's gicp_epsilon); fixed, see above
 
@@ -57,7 +57,7 @@ typedef struct QtrIcpCfg {
   double trans_eps;     // transformation_epsilon
   double fit_eps;       // euclidean_fitness_epsilon
   int max_iterations;
-  int method;           // 0 point-to-plane, 1 point-to-point, 2 plane-to-plane
+  int method;           // 0 point-to-plane, 1 point-to-point, 2 plane-to-plane, 3 voxelised plane-to-plane
   int min_corr;
   int pad;
 } QtrIcpCfg;
@@ -132,34 +132,10 @@ QM_HD bool qtr_icp_normal_ok(float x, float y, float z) {
   return ((a * a + b * b) + c * c) > 0.0;
 }
 
-// the plane-to-plane terms of one correspondence: q = T p, source normal a (source frame), target point t with normal
-// nb; d2 = qtr_icp_d2(q, t).  Both normals pass qtr_icp_normal_ok.  With K = [q]x and J = [-K | I]:
-//   J^T M J = [[-K M K, K M], [(K M)^T, M]],  J^T M d = (q x (M d), M d)
-// B = K M is formed column by column (B[:, j] = q x M[:, j]), then -K M K = B K^T row by row (row i = q x B[i, :]).
-QM_HD void qtr_icp_gicp_terms(const double* T, const double* q, float ax, float ay, float az, float tx, float ty, float tz,
-                              float bx, float by, float bz, double d2, double* o /* [QTR_ICP_NT] */) {
-  const double k = 1.0 - QTR_ICP_GICP_EPSILON;
-  double a0 = (double)ax, a1 = (double)ay, a2 = (double)az;
-  const double la = sqrt((a0 * a0 + a1 * a1) + a2 * a2);
-  a0 = a0 / la;
-  a1 = a1 / la;
-  a2 = a2 / la;
-  double n0 = (double)bx, n1 = (double)by, n2 = (double)bz;
-  const double ln = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
-  n0 = n0 / ln;
-  n1 = n1 / ln;
-  n2 = n2 / ln;
-  const double m0 = (T[0] * a0 + T[1] * a1) + T[2] * a2;
-  const double m1 = (T[4] * a0 + T[5] * a1) + T[6] * a2;
-  const double m2 = (T[8] * a0 + T[9] * a1) + T[10] * a2;
-  // Sigma (symmetric): s00 s01 s02 s11 s12 s22
-  const double s00 = 2.0 - k * (n0 * n0 + m0 * m0);
-  const double s01 = -(k * (n0 * n1 + m0 * m1));
-  const double s02 = -(k * (n0 * n2 + m0 * m2));
-  const double s11 = 2.0 - k * (n1 * n1 + m1 * m1);
-  const double s12 = -(k * (n1 * n2 + m1 * m2));
-  const double s22 = 2.0 - k * (n2 * n2 + m2 * m2);
-  // M = adj(Sigma) / det(Sigma)
+// What plane-to-plane and its voxelised form share, from Sigma = C_b + R C_a R^T (symmetric: s00 s01 s02 s11 s12 s22), q and
+// d: M = adj(Sigma) / det(Sigma), then J^T M J (21), J^T M d (6) and d^T M d into their places of o.  o[28 ..] is the caller's.
+QM_HD void qtr_icp_mahal_terms(double s00, double s01, double s02, double s11, double s12, double s22, const double* q,
+                               double d0, double d1, double dz, double* o /* [QTR_ICP_NT] */) {
   const double c00 = s11 * s22 - s12 * s12;
   const double c01 = s02 * s12 - s01 * s22;
   const double c02 = s01 * s12 - s02 * s11;
@@ -169,7 +145,6 @@ QM_HD void qtr_icp_gicp_terms(const double* T, const double* q, float ax, float 
   const double det = (s00 * c00 + s01 * c01) + s02 * c02;
   const double M00 = c00 / det, M01 = c01 / det, M02 = c02 / det, M11 = c11 / det, M12 = c12 / det, M22 = c22 / det;
   const double q0 = q[0], q1 = q[1], q2 = q[2];
-  const double d0 = q0 - (double)tx, d1 = q1 - (double)ty, dz = q2 - (double)tz;
   const double e0 = (M00 * d0 + M01 * d1) + M02 * dz;  // M d
   const double e1 = (M01 * d0 + M11 * d1) + M12 * dz;
   const double e2 = (M02 * d0 + M12 * d1) + M22 * dz;
@@ -206,9 +181,157 @@ QM_HD void qtr_icp_gicp_terms(const double* T, const double* q, float ax, float 
   o[QTR_ICP_T_JTR + 4] = e1;
   o[QTR_ICP_T_JTR + 5] = e2;
   o[QTR_ICP_T_R2] = (d0 * e0 + d1 * e1) + dz * e2;
+}
+
+// the plane-to-plane terms of one correspondence: q = T p, source normal a (source frame), target point t with normal
+// nb; d2 = qtr_icp_d2(q, t).  Both normals pass qtr_icp_normal_ok.  With K = [q]x and J = [-K | I]:
+//   J^T M J = [[-K M K, K M], [(K M)^T, M]],  J^T M d = (q x (M d), M d)
+// B = K M is formed column by column (B[:, j] = q x M[:, j]), then -K M K = B K^T row by row (row i = q x B[i, :]).
+QM_HD void qtr_icp_gicp_terms(const double* T, const double* q, float ax, float ay, float az, float tx, float ty, float tz,
+                              float bx, float by, float bz, double d2, double* o /* [QTR_ICP_NT] */) {
+  const double k = 1.0 - QTR_ICP_GICP_EPSILON;
+  double a0 = (double)ax, a1 = (double)ay, a2 = (double)az;
+  const double la = sqrt((a0 * a0 + a1 * a1) + a2 * a2);
+  a0 = a0 / la;
+  a1 = a1 / la;
+  a2 = a2 / la;
+  double n0 = (double)bx, n1 = (double)by, n2 = (double)bz;
+  const double ln = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+  n0 = n0 / ln;
+  n1 = n1 / ln;
+  n2 = n2 / ln;
+  const double m0 = (T[0] * a0 + T[1] * a1) + T[2] * a2;
+  const double m1 = (T[4] * a0 + T[5] * a1) + T[6] * a2;
+  const double m2 = (T[8] * a0 + T[9] * a1) + T[10] * a2;
+  // Sigma (symmetric): s00 s01 s02 s11 s12 s22
+  const double s00 = 2.0 - k * (n0 * n0 + m0 * m0);
+  const double s01 = -(k * (n0 * n1 + m0 * m1));
+  const double s02 = -(k * (n0 * n2 + m0 * m2));
+  const double s11 = 2.0 - k * (n1 * n1 + m1 * m1);
+  const double s12 = -(k * (n1 * n2 + m1 * m2));
+  const double s22 = 2.0 - k * (n2 * n2 + m2 * m2);
+  const double d0 = q[0] - (double)tx, d1 = q[1] - (double)ty, dz = q[2] - (double)tz;
+  qtr_icp_mahal_terms(s00, s01, s02, s11, s12, s22, q, d0, d1, dz, o);
   o[QTR_ICP_T_D2] = d2;
   o[QTR_ICP_T_CNT] = 1.0;
   o[30] = 0.0;
+  o[31] = 0.0;
+}
+
+// ---- voxelised plane-to-plane (method 3, VGICP: Koide et al., ICRA 2021) -------------------------------------------------
+// The target is summarised once per call as one Gaussian per voxel and a transformed source point is matched to the voxel
+// it falls into: a lookup in place of the search.
+//   grid     origin o = component-wise minimum of the finite target points, side c = max_correspondence_distance exactly,
+//            dims[a] = floor((max[a] - o[a]) / c) + 1, cell index floor((x - o[a]) / c) in binary64 (qtr_icp_cellf) for
+//            target points and transformed source points alike.  Unlike the search's, this grid is part of the result.
+//   members  of a voxel: the finite target points whose normal passes qtr_icp_normal_ok; a voxel without members does
+//            not exist.
+//   record   N, mu = (sum of the members' coordinates) / N, C_b = I - (1 - eps) S / N with S = sum n n^T over the members'
+//            unit normals, rep = the lowest original target index among the members.  EVERY sum runs over the members in
+//            ascending original target index, from 0.0 (qtr_icp_voxel_add, then qtr_icp_voxel_finish).
+//   match    q = T p; no correspondence if a cell index lies outside [0, dims) (compared as double: NaN and huge values fail)
+//            or the voxel does not exist; sources are not clamped and there is no distance test.
+//   terms    d = q - mu, Sigma = C_b + R C_a R^T, M = Sigma^-1 (both summands have eigenvalues in [eps, 1]), weight w = N:
+//            w J^T M J, w J^T M d, w d^T M d in the point-to-plane places, d^2, 1, and w in place QTR_ICP_T_W.
+//   result   fitness = mean d^2, rmse = sqrt(sum w d^T M d / sum w); solve, increment and stopping rules are point-to-plane's.
+#define QTR_ICP_T_W 30  // sum of the weights (method 3; one of the two padding places)
+
+typedef struct QtrIcpVoxel {
+  double mu[3];
+  double C[6];  // C_b: c00 c01 c02 c11 c12 c22
+  int n;        // members (0: the voxel does not exist)
+  int rep;      // lowest original target index among them
+} QtrIcpVoxel;
+
+// the largest cell table of a call.  A voxel grid of more cells is refused (QTR_ERR_CAPACITY), never coarsened.
+#define QTR_ICP_CELL_CAP (1 << 22)
+
+QM_HD double qtr_icp_cellf(double x, double o, double c) { return floor((x - o) / c); }
+
+// dims of the voxel grid over the box [o, mx] of the finite target points; returns the number of cells as a double
+// (dims is meaningful only when that is <= QTR_ICP_CELL_CAP)
+QM_HD double qtr_icp_voxel_dims(const double* o, const double* mx, double c, int* dims) {
+  double nc = 1.0;
+  for (int a = 0; a < 3; ++a) {
+    const double d = qtr_icp_cellf(mx[a], o[a], c) + 1.0;
+    nc = nc * d;
+    dims[a] = (d >= 1.0 && d <= (double)QTR_ICP_CELL_CAP) ? (int)d : 0;
+  }
+  return nc;
+}
+
+// the cell of q on the voxel grid (o, c, dims): false if it lies outside
+QM_HD bool qtr_icp_voxel_cell(const double* q, const double* o, double c, const int* dims, int* lin) {
+  int i[3];
+  for (int a = 0; a < 3; ++a) {
+    const double f = qtr_icp_cellf(q[a], o[a], c);
+    if (!(f >= 0.0 && f <= (double)(dims[a] - 1))) return false;  // (NaN / huge: compared as double before the cast)
+    i[a] = (int)f;
+  }
+  *lin = i[0] + dims[0] * (i[1] + dims[1] * i[2]);
+  return true;
+}
+
+// one member into the running sums acc[9] (coordinates 3, n n^T 6; zero before the first member)
+QM_HD void qtr_icp_voxel_add(double* acc, float tx, float ty, float tz, float bx, float by, float bz) {
+  double n0 = (double)bx, n1 = (double)by, n2 = (double)bz;
+  const double ln = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+  n0 = n0 / ln;
+  n1 = n1 / ln;
+  n2 = n2 / ln;
+  acc[0] = acc[0] + (double)tx;
+  acc[1] = acc[1] + (double)ty;
+  acc[2] = acc[2] + (double)tz;
+  acc[3] = acc[3] + n0 * n0;
+  acc[4] = acc[4] + n0 * n1;
+  acc[5] = acc[5] + n0 * n2;
+  acc[6] = acc[6] + n1 * n1;
+  acc[7] = acc[7] + n1 * n2;
+  acc[8] = acc[8] + n2 * n2;
+}
+
+QM_HD void qtr_icp_voxel_finish(const double* acc, int n, int rep, QtrIcpVoxel* vx) {
+  const double k = 1.0 - QTR_ICP_GICP_EPSILON, N = (double)n;
+  for (int a = 0; a < 3; ++a) vx->mu[a] = n > 0 ? acc[a] / N : 0.0;
+  for (int a = 0; a < 6; ++a) vx->C[a] = 0.0;
+  if (n > 0) {
+    vx->C[0] = 1.0 - k * (acc[3] / N);
+    vx->C[1] = -(k * (acc[4] / N));
+    vx->C[2] = -(k * (acc[5] / N));
+    vx->C[3] = 1.0 - k * (acc[6] / N);
+    vx->C[4] = -(k * (acc[7] / N));
+    vx->C[5] = 1.0 - k * (acc[8] / N);
+  }
+  vx->n = n;
+  vx->rep = rep;
+}
+
+// the terms of one source point q = T p (normal a, source frame, qtr_icp_normal_ok) against the voxel it fell into
+QM_HD void qtr_icp_vgicp_terms(const double* T, const double* q, float ax, float ay, float az, const QtrIcpVoxel* vx,
+                               double* o /* [QTR_ICP_NT] */) {
+  const double k = 1.0 - QTR_ICP_GICP_EPSILON;
+  double a0 = (double)ax, a1 = (double)ay, a2 = (double)az;
+  const double la = sqrt((a0 * a0 + a1 * a1) + a2 * a2);
+  a0 = a0 / la;
+  a1 = a1 / la;
+  a2 = a2 / la;
+  const double m0 = (T[0] * a0 + T[1] * a1) + T[2] * a2;
+  const double m1 = (T[4] * a0 + T[5] * a1) + T[6] * a2;
+  const double m2 = (T[8] * a0 + T[9] * a1) + T[10] * a2;
+  // Sigma = C_b + (I - (1 - eps) m m^T)
+  const double s00 = vx->C[0] + (1.0 - k * (m0 * m0));
+  const double s01 = vx->C[1] + -(k * (m0 * m1));
+  const double s02 = vx->C[2] + -(k * (m0 * m2));
+  const double s11 = vx->C[3] + (1.0 - k * (m1 * m1));
+  const double s12 = vx->C[4] + -(k * (m1 * m2));
+  const double s22 = vx->C[5] + (1.0 - k * (m2 * m2));
+  const double d0 = q[0] - vx->mu[0], d1 = q[1] - vx->mu[1], dz = q[2] - vx->mu[2];
+  qtr_icp_mahal_terms(s00, s01, s02, s11, s12, s22, q, d0, d1, dz, o);
+  const double w = (double)vx->n;
+  for (int j = 0; j <= QTR_ICP_T_R2; ++j) o[j] = w * o[j];
+  o[QTR_ICP_T_D2] = (d0 * d0 + d1 * d1) + dz * dz;
+  o[QTR_ICP_T_CNT] = 1.0;
+  o[QTR_ICP_T_W] = w;
   o[31] = 0.0;
 }
 
@@ -322,8 +445,8 @@ QM_HD void qtr_icp_step(const QtrIcpCfg* cfg, const double* S, QtrIcpState* st, 
   const double mse = S[QTR_ICP_T_D2] / n;
   st->fitness = mse;
   double dR[9], dt[3];
-  if (cfg->method != 1) {  // (plane-to-plane: the same solve over J^T M J, J^T M d, d^T M d)
-    st->rmse = sqrt(S[QTR_ICP_T_R2] / n);
+  if (cfg->method != 1) {  // (plane-to-plane: the same solve over J^T M J, J^T M d, d^T M d; voxelised: weighted)
+    st->rmse = sqrt(S[QTR_ICP_T_R2] / (cfg->method == 3 ? S[QTR_ICP_T_W] : n));
     double b[6], x[6];
     for (int a = 0; a < 6; ++a) b[a] = -S[QTR_ICP_T_JTR + a];
     if (!qtr_icp_solve6(S, b, x)) {

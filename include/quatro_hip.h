@@ -418,6 +418,16 @@ QTR_API int qtr_get_nn_dir_times(qtr_handle* h, int slot, float* dir1_ms, float*
  *                   sum d^T (C_b + R C_a R^T)^-1 d per iteration, d = q - t, the same 6x6 solve and increment.  A source
  *                   point whose normal is not finite or has zero length is skipped; a correspondence whose target normal
  *                   is not finite or has zero length is dropped.  rmse = sqrt(mean d^T M d), fitness = mean d^2
+ *   voxelised plane-to-plane: VGICP (Koide et al., ICRA 2021; fast_gicp's FastVGICP) — the search is replaced by a lookup.
+ *                   The target is summarised once per call as one Gaussian per voxel of side max_correspondence_distance
+ *                   (grid origin: the minimum of the finite target points; never coarsened: a grid of more than 2^22 cells
+ *                   is QTR_ERR_CAPACITY): member count N, mean mu of the members, C_b = I - (1 - eps) mean(n n^T); members
+ *                   are the finite target points with a usable normal, summed in ascending index.  A transformed source
+ *                   point is matched to the voxel it falls into (none outside the grid or in a voxel without members; no
+ *                   distance test): d = q - mu, weight N, one Gauss-Newton step of sum N d^T (C_b + R C_a R^T)^-1 d.
+ *                   Unlike the three search methods the result depends on the grid, hence on the distance as voxel side.
+ *                   fitness = mean d^2, rmse = sqrt(sum N d^T M d / sum N); QTR_DBG_ICP_CORR reports a voxel as the
+ *                   lowest target index among its members.  The contract is include/qtr_icp_math.h's
  *   stopping:       max_iterations updates; max |dT - I| <= transformation_epsilon; |mse - mse_prev| <=
  *                   euclidean_fitness_epsilon * mse_prev; fewer than min_correspondences correspondences (valid = 0, T the
  *                   last good transform); a rank-deficient system, e.g. a single plane (valid = 0, T the last good one)
@@ -426,6 +436,7 @@ QTR_API int qtr_get_nn_dir_times(qtr_handle* h, int slot, float* dir1_ms, float*
 #define QTR_ICP_POINT_TO_PLANE 0
 #define QTR_ICP_POINT_TO_POINT 1
 #define QTR_ICP_PLANE_TO_PLANE 2
+#define QTR_ICP_VOXEL_PLANE_TO_PLANE 3
 #define QTR_ICP_MAX_ITERATIONS 1000 /* largest max_iterations accepted */
 /* qtr_icp_result.stop_reason */
 #define QTR_ICP_STOP_NONE 0
@@ -439,9 +450,10 @@ typedef struct qtr_icp_params {
   double transformation_epsilon;      /* 1e-7: max |dT - I| of an update (setTransformationEpsilon) */
   double euclidean_fitness_epsilon;   /* 1e-6: relative change of the correspondences' MSE (setEuclideanFitnessEpsilon) */
   int max_iterations;                 /* 30 (setMaximumIterations), 1 .. QTR_ICP_MAX_ITERATIONS */
-  int method;                         /* QTR_ICP_POINT_TO_PLANE (default), _POINT_TO_POINT, _PLANE_TO_PLANE */
+  int method;                         /* QTR_ICP_POINT_TO_PLANE (default), _POINT_TO_POINT, _PLANE_TO_PLANE,
+                                         _VOXEL_PLANE_TO_PLANE */
   int min_correspondences;            /* 0 = the method's minimum: 6 point-to-plane, 3 point-to-point,
-                                         4 plane-to-plane */
+                                         4 plane-to-plane (voxelised or not) */
   float normal_radius;                /* 0.5 m: normals of qtr_icp / qtr_gicp that the caller does not pass (the FPFH
                                          stage's normal estimation); qtr_refine_pair uses the registration's normals */
 } qtr_icp_params;
@@ -454,12 +466,12 @@ typedef struct qtr_icp_result {
 QTR_API void qtr_default_icp_params(qtr_icp_params* p);
 /* src4 (n_s) / tgt4 (n_t): 16-byte records; tgt_normals4: n_t records nx,ny,nz,* (point-to-plane and plane-to-plane; NULL:
  * computed at normal_radius).  guess: row-major 4x4 (NULL = identity).  mem: where the clouds live.  Plane-to-plane
- * computes the source normals at normal_radius: qtr_icp(method 2) is qtr_gicp with src_normals4 = NULL. */
+ * computes the source normals at normal_radius: qtr_icp(method 2 or 3) is qtr_gicp with src_normals4 = NULL. */
 QTR_API int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const float* tgt4, int n_t, const float* tgt_normals4,
                     const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res, int mem);
 /* Plane-to-plane for callers who bring both normal sets: src_normals4 (n_s records, source frame) / tgt_normals4 (n_t
- * records); either may be NULL (computed at normal_radius).  prm->method must be QTR_ICP_PLANE_TO_PLANE (QTR_ERR_BAD_ARG
- * otherwise).  Validation, capacity, empty clouds, mem and the QTR_DBG_ICP_* items as qtr_icp. */
+ * records); either may be NULL (computed at normal_radius).  prm->method must be QTR_ICP_PLANE_TO_PLANE or
+ * QTR_ICP_VOXEL_PLANE_TO_PLANE (QTR_ERR_BAD_ARG otherwise).  Validation, capacity, empty clouds, mem and the QTR_DBG_ICP_* items as qtr_icp. */
 QTR_API int qtr_gicp(qtr_handle* h, int slot, const float* src4, int n_s, const float* src_normals4, const float* tgt4, int n_t,
                      const float* tgt_normals4, const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res, int mem);
 /* Refines the slot's last qtr_register_pair / qtr_register_pair_corr on its voxelised clouds (the CALLER's source and

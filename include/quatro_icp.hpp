@@ -3,7 +3,8 @@
 // follows a Quatro registration (Quatro recovers yaw and translation; roll and pitch come only from estimated_RyRx_).
 // Point-to-plane by default (pcl::IterativeClosestPointWithNormals; target normals at normal_radius unless
 // setTargetNormals gives them), point-to-point or plane-to-plane (Generalized ICP: qtr_gicp with the normals of both
-// clouds, given by setSourceNormals / setTargetNormals or computed at normal_radius) on request.  Host code only; link
+// clouds, given by setSourceNormals / setTargetNormals or computed at normal_radius) or its voxelised form (VGICP: the voxel
+// side is setMaxCorrespondenceDistance, normals as for plane-to-plane) on request.  Host code only; link
 // with -lquatro_hip.  Compiles with the
 // built-in stand-ins of quatro.hpp and against PCL / Eigen (QUATRO_HAVE_PCL).
 #ifndef QUATRO_ICP_H
@@ -25,7 +26,8 @@ class IterativeClosestPoint {
   enum class Method {
     POINT_TO_PLANE = QTR_ICP_POINT_TO_PLANE,
     POINT_TO_POINT = QTR_ICP_POINT_TO_POINT,
-    PLANE_TO_PLANE = QTR_ICP_PLANE_TO_PLANE
+    PLANE_TO_PLANE = QTR_ICP_PLANE_TO_PLANE,
+    VOXEL_PLANE_TO_PLANE = QTR_ICP_VOXEL_PLANE_TO_PLANE  // (VGICP: routed like PLANE_TO_PLANE)
   };
 
   explicit IterativeClosestPoint(Method method = Method::POINT_TO_PLANE) {
@@ -73,7 +75,7 @@ class IterativeClosestPoint {
     const int ns = static_cast<int>(input_->points.size()), nt = static_cast<int>(target_->points.size());
     const bool given = !normals_.empty() && normals_.size() == 4 * target_->points.size();
     int rc;
-    if (prm_.method == QTR_ICP_PLANE_TO_PLANE) {
+    if (prm_.method == QTR_ICP_PLANE_TO_PLANE || prm_.method == QTR_ICP_VOXEL_PLANE_TO_PLANE) {
       const bool src_given = !src_normals_.empty() && src_normals_.size() == 4 * input_->points.size();
       rc = qtr_gicp(h, slot_lease.slot, xyz4(input_->points), ns, src_given ? src_normals_.data() : nullptr,
                     xyz4(target_->points), nt, given ? normals_.data() : nullptr, g, &prm_, &res_, QTR_MEM_HOST);

@@ -419,13 +419,15 @@ class IterativeClosestPoint:
     qtr_icp: the 6-DoF refinement that normally follows a global registration.  Point-to-plane by default
     (pcl::IterativeClosestPointWithNormals; target normals at normal_radius unless setTargetNormals gives them),
     point-to-point with method="point_to_point", plane-to-plane (Generalized ICP; setSourceNormals / setTargetNormals, or
-    both normal sets at normal_radius) with method="plane_to_plane".  Everything numerical runs on the device."""
+    both normal sets at normal_radius) with method="plane_to_plane", its voxelised form (VGICP: the target as one Gaussian
+    per voxel of side max_correspondence_distance, a lookup in place of the search; normals as for plane-to-plane) with
+    method="voxel_plane_to_plane".  Everything numerical runs on the device."""
 
     def __init__(self, handle=None, method: str = "point_to_plane", normal_radius: float = 0.5):
         methods = {"point_to_plane": _ql.ICP_POINT_TO_PLANE, "point_to_point": _ql.ICP_POINT_TO_POINT,
-                   "plane_to_plane": _ql.ICP_PLANE_TO_PLANE}
+                   "plane_to_plane": _ql.ICP_PLANE_TO_PLANE, "voxel_plane_to_plane": _ql.ICP_VOXEL_PLANE_TO_PLANE}
         if method not in methods:
-            raise ValueError("method must be 'point_to_plane', 'point_to_point' or 'plane_to_plane'")
+            raise ValueError("method must be 'point_to_plane', 'point_to_point', 'plane_to_plane' or 'voxel_plane_to_plane'")
         self._h = handle
         self.params_ = _ql.default_icp_params(method=methods[method], normal_radius=float(normal_radius))
         self.input_ = None
@@ -476,7 +478,7 @@ class IterativeClosestPoint:
             raise ValueError("input clouds not set")
         h = self._h or _handle()
         g = np.eye(4) if guess is None else guess
-        if self.params_.method == _ql.ICP_PLANE_TO_PLANE:
+        if self.params_.method in (_ql.ICP_PLANE_TO_PLANE, _ql.ICP_VOXEL_PLANE_TO_PLANE):
             r = h.gicp(self.input_, self.target_, self.source_normals_, self.target_normals_, g, self.params_)
         else:
             r = h.icp(self.input_, self.target_, self.target_normals_, g, self.params_)

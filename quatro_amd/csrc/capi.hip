@@ -2855,7 +2855,7 @@ static int lane_enqueue_refine(qtr_handle* h, Lane& ln) {
   ln.active.swap(ref);
   if (ln.active.empty()) return lane_start_chunk(h, ln);
   const QtrIcpCfg cfg = icp_cfg_of(&J.icp);
-  const bool gicp = J.icp.method == QTR_ICP_PLANE_TO_PLANE;
+  const bool gicp = J.icp.method == QTR_ICP_PLANE_TO_PLANE || J.icp.method == QTR_ICP_VOXEL_PLANE_TO_PLANE;  // (needs source normals)
   const bool plane = J.icp.method == QTR_ICP_POINT_TO_PLANE || gicp;
   ln.iv.clear();
   std::vector<int> seqs;
@@ -2904,7 +2904,7 @@ static int lane_enqueue_icp_block(qtr_handle* h, Lane& ln) {
   const int block = h->icp_block > 0 ? h->icp_block : J.icp.max_iterations;
   const int m = std::min(block, J.icp.max_iterations - ln.ref_it);
   QTR_HIP_TRY(h, icp_iter_enqueue_group(ln.ref_views, (int)seqs.size(), ln.ref_nchunk, m, ds, lead.stream,
-                                        J.icp.method == QTR_ICP_PLANE_TO_PLANE));
+                                        J.icp.method));
   ln.ref_it += m;
   ln.phase = LANE_REFINE_ITER;
   return QTR_OK;
@@ -2918,18 +2918,29 @@ static int lane_refine_grids(qtr_handle* h, Lane& ln) {
   std::vector<IcpView> V;
   std::vector<QtrIcpState> init;
   int max_nt = 1, max_ncell = 1, max_nchunk = 1;
+  const bool voxels = J.icp.method == QTR_ICP_VOXEL_PLANE_TO_PLANE;
   for (size_t k = 0; k < ln.active.size(); ++k) {
     const int g = ln.active[k], pair = ln.first_pair + g;
     Slot& s = h->slots[ln.first_slot + g];
     IcpView v = ln.iv[k];
     QtrIcpState st0;
     qtr_icp_init(&st0, J.results[pair].T);
-    if (!icp_grid_of(v, s.mail + MAIL_ICP_BOX, J.icp.max_correspondence_distance, s.icp.cap_cells)) {
+    // (method 3: the grid is part of the result, so it follows the rule and QTR_ICP_CELL_CAP, not this arena's capacity; a
+    // grid past the slot's table grows it, as the single-pair call does.  Past the cap only this pair is refused.)
+    const int grid = voxels ? icp_voxel_grid_of(v, s.mail + MAIL_ICP_BOX, J.icp.max_correspondence_distance, h->err, sizeof(h->err))
+                            : (int)icp_grid_of(v, s.mail + MAIL_ICP_BOX, J.icp.max_correspondence_distance, s.icp.cap_cells);
+    if (grid <= 0) {
       st0.reason = QTR_ICP_STOP_TOO_FEW;
       icp_result_from(&J.refined[pair], st0);
-      J.refined[pair].status = QTR_OK;
+      J.refined[pair].status = grid < 0 ? QTR_ERR_CAPACITY : QTR_OK;
       J.ref_state[pair] = 2;
       continue;
+    }
+    if (voxels && v.ncell > s.icp.cap_cells) {
+      QTR_HIP_TRY(h, hipStreamSynchronize(lead.stream));  // (nothing of this lane may still read the table)
+      QTR_HIP_TRY(h, icp_reserve_cells(s.icp, v.ncell));
+      v.cell_cnt = s.icp.cells;
+      v.cell_start = s.icp.cells + s.icp.cap_cells + 1;
     }
     keep.push_back(g);
     V.push_back(v);
@@ -2948,7 +2959,7 @@ static int lane_refine_grids(qtr_handle* h, Lane& ln) {
     snprintf(h->err, sizeof(h->err), "batch refine: the lane's view stage is full");
     return QTR_ERR_HIP;
   }
-  QTR_HIP_TRY(h, icp_grid_enqueue_group(dv, di, G, max_nt, max_ncell, lead.stream));
+  QTR_HIP_TRY(h, icp_grid_enqueue_group(dv, di, G, max_nt, max_ncell, lead.stream, voxels));
   ln.ref_views = dv;
   ln.ref_nchunk = max_nchunk;
   ln.ref_it = 0;
@@ -3229,10 +3240,12 @@ static int submit_batch_impl(qtr_handle* h, const qtr_pair_desc* pairs, int B, c
     return QTR_ERR_BAD_ARG;
   }
   QTR_HIP_TRY(h, hipSetDevice(h->device));
-  if (icp)  // every slot's ICP arena, and a cell table no grid of the refine phase outgrows (no allocation in the lanes)
+  if (icp)  // every slot's ICP arena, and a cell table no grid of the search methods outgrows (no allocation in the lanes;
+            // method 3's grid is the rule's, so a lane grows the table of a pair that needs more: lane_refine_grids)
     for (auto& sl : h->slots) {
       QTR_HIP_TRY(h, icp_reserve(sl.icp, h->lim.max_voxels, QTR_ICP_MAX_ITERATIONS));
       QTR_HIP_TRY(h, icp_reserve_cells(sl.icp, QTR_ICP_BATCH_CELLS));
+      if (icp->method == QTR_ICP_VOXEL_PLANE_TO_PLANE) QTR_HIP_TRY(h, icp_reserve_vox(sl.icp, h->lim.max_voxels));
     }
   BatchJob& J = h->job;
   J.pairs = pairs;
@@ -3396,7 +3409,8 @@ static int check_icp_params(qtr_handle* h, const qtr_icp_params* p) {
   if (!p || !icp_finite(p->max_correspondence_distance) || !(p->max_correspondence_distance > 0) ||
       !icp_finite(p->transformation_epsilon) || p->transformation_epsilon < 0 || !icp_finite(p->euclidean_fitness_epsilon) ||
       p->euclidean_fitness_epsilon < 0 || p->max_iterations < 1 || p->max_iterations > QTR_ICP_MAX_ITERATIONS ||
-      (p->method != QTR_ICP_POINT_TO_PLANE && p->method != QTR_ICP_POINT_TO_POINT && p->method != QTR_ICP_PLANE_TO_PLANE) || p->min_correspondences < 0 ||
+      (p->method != QTR_ICP_POINT_TO_PLANE && p->method != QTR_ICP_POINT_TO_POINT && p->method != QTR_ICP_PLANE_TO_PLANE &&
+       p->method != QTR_ICP_VOXEL_PLANE_TO_PLANE) || p->min_correspondences < 0 ||
       !icp_finite((double)p->normal_radius) || !(p->normal_radius > 0)) {
     snprintf(h->err, sizeof(h->err), "invalid ICP parameter");
     return QTR_ERR_BAD_ARG;
@@ -3417,13 +3431,15 @@ static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const
   s.icp_iters = 0;
   s.icp_ms[0] = s.icp_ms[1] = 0.f;
   if (ns == 0 || nt == 0) return QTR_OK;
-  const bool gicp = prm->method == QTR_ICP_PLANE_TO_PLANE;
+  const bool voxels = prm->method == QTR_ICP_VOXEL_PLANE_TO_PLANE;
+  const bool gicp = prm->method == QTR_ICP_PLANE_TO_PLANE || voxels;  // (needs source normals)
   if (gicp && (!d_nrm || !d_src_nrm)) {
     snprintf(h->err, sizeof(h->err), "plane-to-plane needs the normals of both clouds");
     return QTR_ERR_BAD_ARG;
   }
   IcpBufs& B = s.icp;
   QTR_HIP_TRY(h, icp_reserve(B, h->lim.max_voxels, QTR_ICP_MAX_ITERATIONS));
+  if (voxels) QTR_HIP_TRY(h, icp_reserve_vox(B, h->lim.max_voxels));
   IcpView& v = B.v;
   v.src = d_src;
   v.tgt = d_tgt;
@@ -3438,20 +3454,27 @@ static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const
   QTR_HIP_TRY(h, icp_box_enqueue(v, B.h_bbox, st));
   QTR_HIP_TRY(h, hipMemcpyAsync(B.h_bbox, v.bbox, 24, hipMemcpyDeviceToHost, st));
   QTR_HIP_TRY(h, hipStreamSynchronize(st));
-  if (!icp_grid_of(v, B.h_bbox, prm->max_correspondence_distance, QTR_ICP_CELL_CAP)) return QTR_OK;  // no finite target point
+  if (voxels) {
+    const int grid = icp_voxel_grid_of(v, B.h_bbox, prm->max_correspondence_distance, h->err, sizeof(h->err));
+    if (grid < 0) return QTR_ERR_CAPACITY;
+    if (grid == 0) return QTR_OK;
+  } else if (!icp_grid_of(v, B.h_bbox, prm->max_correspondence_distance, QTR_ICP_CELL_CAP)) {
+    return QTR_OK;  // no finite target point
+  }
   QTR_HIP_TRY(h, icp_reserve_cells(B, v.ncell));
   v.cell_cnt = B.cells;
   v.cell_start = B.cells + B.cap_cells + 1;
   QtrIcpState st0;
   qtr_icp_init(&st0, guess);
-  QTR_HIP_TRY(h, icp_grid_enqueue(v, st0, st));
+  QTR_HIP_TRY(h, icp_grid_enqueue(v, st0, st, voxels));
   QTR_HIP_TRY(h, hipEventRecord(s.ev[1], st));
   const int nchunk = qtr_div_up(ns, QTR_ICP_CHUNK);
   const int block = h->icp_block > 0 ? h->icp_block : prm->max_iterations;
   for (int it = 0; it < prm->max_iterations;) {
     const int m = std::min(block, prm->max_iterations - it);
     for (int k = 0; k < m; ++k) {
-      if (gicp) hipLaunchKernelGGL(k_icp_iter_gicp, dim3(nchunk), dim3(256), 0, st, v);
+      if (voxels) hipLaunchKernelGGL(k_icp_iter_vgicp, dim3(nchunk), dim3(256), 0, st, v);
+      else if (gicp) hipLaunchKernelGGL(k_icp_iter_gicp, dim3(nchunk), dim3(256), 0, st, v);
       else hipLaunchKernelGGL(k_icp_iter, dim3(nchunk), dim3(256), 0, st, v);
     }
     QTR_HIP_TRY(h, hipGetLastError());
@@ -3551,7 +3574,7 @@ int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const float* tg
   Slot& s = *sp;
   int rc = check_icp_params(h, prm);
   if (rc != QTR_OK) return res->status = rc;
-  if (prm->method == QTR_ICP_PLANE_TO_PLANE)  // (the source normals at normal_radius)
+  if (prm->method == QTR_ICP_PLANE_TO_PLANE || prm->method == QTR_ICP_VOXEL_PLANE_TO_PLANE)  // (the source normals at normal_radius)
     return qtr_gicp(h, slot, src4, n_s, nullptr, tgt4, n_t, tgt_normals4, guess, prm, res, mem);
   const bool plane = prm->method == QTR_ICP_POINT_TO_PLANE, run = n_s > 0 && n_t > 0;
   const int n[2] = {n_s, n_t};
@@ -3575,8 +3598,8 @@ int qtr_gicp(qtr_handle* h, int slot, const float* src4, int n_s, const float* s
   Slot& s = *sp;
   int rc = check_icp_params(h, prm);
   if (rc != QTR_OK) return res->status = rc;
-  if (prm->method != QTR_ICP_PLANE_TO_PLANE) {
-    snprintf(h->err, sizeof(h->err), "qtr_gicp: method must be QTR_ICP_PLANE_TO_PLANE");
+  if (prm->method != QTR_ICP_PLANE_TO_PLANE && prm->method != QTR_ICP_VOXEL_PLANE_TO_PLANE) {
+    snprintf(h->err, sizeof(h->err), "qtr_gicp: method must be QTR_ICP_PLANE_TO_PLANE or QTR_ICP_VOXEL_PLANE_TO_PLANE");
     return res->status = QTR_ERR_BAD_ARG;
   }
   const bool run = n_s > 0 && n_t > 0;

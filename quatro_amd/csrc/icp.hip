@@ -1,5 +1,7 @@
 // icp.hip — 6-DoF ICP refinement on the device (qtr_icp / qtr_gicp / qtr_refine_pair): point-to-plane (default),
-// point-to-point and plane-to-plane (Generalized ICP; its iteration is an instantiation of its own, d_icp_iter<true>).
+// point-to-point, plane-to-plane (Generalized ICP; its iteration is an instantiation of its own, d_icp_iter<2>) and
+// voxelised plane-to-plane (VGICP, d_icp_iter<3>: the target as one record per cell of side max_correspondence_distance,
+// k_icp_voxel_order / k_icp_voxel_stats after the counting sort, and a lookup in place of the search).
 //
 // Per call: a uniform cell grid over the finite target points (cell side >= max_correspondence_distance, so the
 // nearest target within reach of any query lies in its 27 neighbouring cells), built by a counting sort into the
@@ -46,7 +48,9 @@ struct IcpView {
   int* corr;              // [ns] target index of every source point in the last evaluated iteration (-1: none)
   double* trace;          // [max_iterations][18] (an evaluation, eval.hip: its QtrEvalRecord)
   int* mail;              // grouped launches: device view of the slot's host mailbox (frontend.h MAIL_ICP*), else null
-  const float4* src_nrm;  // [ns] source normals, source frame (plane-to-plane) or null
+  const float4* src_nrm;  // [ns] source normals, source frame (plane-to-plane, voxelised or not) or null
+  QtrIcpVoxel* vox;       // [nt] voxelised plane-to-plane: the record of cell c at cell_start[c] (IcpBufs: icp_reserve_vox)
+  int* vord;              // [nt] ... and its scratch: every cell's places in spts in ascending original index
 };
 
 __device__ __forceinline__ int icp_enc(float f) {  // order-preserving int of a finite float (for atomicMin / Max)
@@ -207,10 +211,54 @@ __device__ __forceinline__ bool icp_reduce_tail(const double* x, double* partial
   return true;
 }
 
-// One workgroup (chunk `blk` of `nblk`) of one iteration of one pair.  GICP: the plane-to-plane body (cfg.method == 2);
-// the other two methods share the instantiation they always had.
-template <bool GICP>
+// ---- voxelised plane-to-plane: one record per non-empty cell (include/qtr_icp_math.h), after k_icp_place ----------------
+// k_icp_place orders a cell by atomic rank, which differs from run to run, and the record's sums run in ascending original
+// index: d_icp_voxel_order gives every finite target point its rank by index among its cell's points (a count over the
+// cell: the cells of a voxelised cloud are small) and writes its place in spts there.
+__device__ __forceinline__ void d_icp_voxel_order(const IcpView& v, int i) {
+  if (i >= v.nt) return;
+  const int lin = v.place[2 * i];
+  if (lin < 0) return;
+  const int s = v.cell_start[lin], e = v.cell_start[lin + 1];
+  int rank = 0;
+  for (int j = s; j < e; ++j) rank += __float_as_int(v.spts[j].w) < i ? 1 : 0;
+  v.vord[s + rank] = s + v.place[2 * i + 1];
+}
+
+// The thread of the point that k_icp_place put first in its cell folds the cell: its members in ascending original index
+// into the record at cell_start[cell] (n = 0: no member, the voxel does not exist).
+__device__ __forceinline__ void d_icp_voxel_stats(const IcpView& v, int i) {
+  if (i >= v.nt) return;
+  const int lin = v.place[2 * i];
+  if (lin < 0 || v.place[2 * i + 1] != 0) return;
+  const int s = v.cell_start[lin], e = v.cell_start[lin + 1];
+  double acc[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+  int n = 0, rep = -1;
+  for (int r = s; r < e; ++r) {
+    const int j = v.vord[r];
+    const float4 t = v.spts[j];
+    const float4 b = v.snrm[j];
+    if (!qtr_icp_normal_ok(b.x, b.y, b.z)) continue;
+    if (n == 0) rep = __float_as_int(t.w);
+    qtr_icp_voxel_add(acc, t.x, t.y, t.z, b.x, b.y, b.z);
+    ++n;
+  }
+  QtrIcpVoxel vx;
+  qtr_icp_voxel_finish(acc, n, rep, &vx);
+  v.vox[s] = vx;
+}
+
+__global__ __launch_bounds__(256) void k_icp_voxel_order(IcpView v) { d_icp_voxel_order(v, blockIdx.x * blockDim.x + threadIdx.x); }
+__global__ __launch_bounds__(256) void k_icp_voxel_stats(IcpView v) { d_icp_voxel_stats(v, blockIdx.x * blockDim.x + threadIdx.x); }
+
+// One workgroup (chunk `blk` of `nblk`) of one iteration of one pair.  METHOD 2: the plane-to-plane body (cfg.method == 2);
+// 3: its voxelised form, a lookup in place of the search (cfg.method == 3); 0: the instantiation the other two methods
+// always shared.
+template <int METHOD>
 __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) {
+  constexpr bool GICP = METHOD == 2, VGICP = METHOD == 3;
   __shared__ double s_S[QTR_ICP_NT];
   const QtrIcpState* st = v.st;
   if (st->stop) return;  // (uniform: written by an earlier launch)
@@ -226,15 +274,29 @@ __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) 
     int best = -1, bat = -1;
     double bd = 0.0, q[3];
     bool use = qtr_icp_finite3(p.x, p.y, p.z) && v.ncell > 0;
-    if (GICP && use) {  // (a source point without a usable normal is skipped before the search)
+    if ((GICP || VGICP) && use) {  // (a source point without a usable normal is skipped before the search)
       const float4 a = v.src_nrm[i];
       use = qtr_icp_normal_ok(a.x, a.y, a.z);
     }
     if (use) {
       qtr_icp_transform(T, p.x, p.y, p.z, q);
-      icp_nearest(v, q, best, bat, bd);
+      if (!VGICP) icp_nearest(v, q, best, bat, bd);
     }
-    if (GICP) {
+    if (VGICP) {
+      int lin = 0;
+      if (use && qtr_icp_voxel_cell(q, v.mn, v.cell, v.dims, &lin)) {
+        const int s = v.cell_start[lin];
+        if (s < v.cell_start[lin + 1]) {
+          const QtrIcpVoxel vx = v.vox[s];
+          if (vx.n > 0) {
+            const float4 a = v.src_nrm[i];
+            best = vx.rep;
+            qtr_icp_vgicp_terms(T, q, a.x, a.y, a.z, &vx, o);
+          }
+        }
+      }
+      v.corr[i] = best;
+    } else if (GICP) {
       if (best >= 0) {
         const float4 n = v.snrm[bat];
         if (!qtr_icp_normal_ok(n.x, n.y, n.z)) best = -1;
@@ -259,9 +321,10 @@ __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) 
       }
     }
   }
-  if (!icp_reduce_tail<QTR_ICP_T_CNT + 1, QTR_ICP_NT>(o, v.partials, v.ticket, blk, nblk, s_S)) return;
+  constexpr int NT = VGICP ? QTR_ICP_T_W + 1 : QTR_ICP_T_CNT + 1;
+  if (!icp_reduce_tail<NT, QTR_ICP_NT>(o, v.partials, v.ticket, blk, nblk, s_S)) return;
   if (threadIdx.x == 0) {
-    for (int k = QTR_ICP_T_CNT + 1; k < QTR_ICP_NT; ++k) s_S[k] = 0.0;  // (the padding terms)
+    for (int k = NT; k < QTR_ICP_NT; ++k) s_S[k] = 0.0;  // (the padding terms)
     QtrIcpState s = *v.st;
     double* tr = (s.iterations < v.cfg.max_iterations) ? v.trace + (size_t)s.iterations * 18 : nullptr;
     qtr_icp_step(&v.cfg, s_S, &s, tr);
@@ -270,8 +333,9 @@ __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) 
   }
 }
 
-__global__ __launch_bounds__(256) void k_icp_iter(IcpView v) { d_icp_iter<false>(v, (int)blockIdx.x, (int)gridDim.x); }
-__global__ __launch_bounds__(256) void k_icp_iter_gicp(IcpView v) { d_icp_iter<true>(v, (int)blockIdx.x, (int)gridDim.x); }
+__global__ __launch_bounds__(256) void k_icp_iter(IcpView v) { d_icp_iter<0>(v, (int)blockIdx.x, (int)gridDim.x); }
+__global__ __launch_bounds__(256) void k_icp_iter_gicp(IcpView v) { d_icp_iter<2>(v, (int)blockIdx.x, (int)gridDim.x); }
+__global__ __launch_bounds__(256) void k_icp_iter_vgicp(IcpView v) { d_icp_iter<3>(v, (int)blockIdx.x, (int)gridDim.x); }
 
 // ---- grouped forms (the lane's refine phase of qtr_submit_batch_refine): blockIdx.y = pair of the group ----------------
 // A launch is as wide as the group's largest pair; workgroups past the pair's own end return first.
@@ -360,18 +424,33 @@ __global__ __launch_bounds__(256) void k_icp_place_group(ViewExt<IcpView> x) {
   d_icp_place(v, blockIdx.x * blockDim.x + threadIdx.x);
 }
 
+__global__ __launch_bounds__(256) void k_icp_voxel_order_group(ViewExt<IcpView> x) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  d_icp_voxel_order(v, blockIdx.x * blockDim.x + threadIdx.x);
+}
+__global__ __launch_bounds__(256) void k_icp_voxel_stats_group(ViewExt<IcpView> x) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  d_icp_voxel_stats(v, blockIdx.x * blockDim.x + threadIdx.x);
+}
+
 // one iteration of every pair of the group: the pair's chunk count stands where k_icp_iter has gridDim.x
 __global__ __launch_bounds__(256) void k_icp_iter_group(ViewExt<IcpView> x) {
   const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
   const int nblk = (v.ns + QTR_ICP_CHUNK - 1) / QTR_ICP_CHUNK;
   if ((int)blockIdx.x >= nblk) return;  // (before the stop flag and the ticket)
-  d_icp_iter<false>(v, (int)blockIdx.x, nblk);
+  d_icp_iter<0>(v, (int)blockIdx.x, nblk);
 }
 __global__ __launch_bounds__(256) void k_icp_iter_gicp_group(ViewExt<IcpView> x) {
   const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
   const int nblk = (v.ns + QTR_ICP_CHUNK - 1) / QTR_ICP_CHUNK;
   if ((int)blockIdx.x >= nblk) return;
-  d_icp_iter<true>(v, (int)blockIdx.x, nblk);
+  d_icp_iter<2>(v, (int)blockIdx.x, nblk);
+}
+__global__ __launch_bounds__(256) void k_icp_iter_vgicp_group(ViewExt<IcpView> x) {
+  const IcpView& v = x.ext[blockIdx.y];  // (inline on purpose: see ViewExt)
+  const int nblk = (v.ns + QTR_ICP_CHUNK - 1) / QTR_ICP_CHUNK;
+  if ((int)blockIdx.x >= nblk) return;
+  d_icp_iter<3>(v, (int)blockIdx.x, nblk);
 }
 
 // the first QTR_ICP_MAIL_WORDS words of every pair's state into its mailbox (three tagged lines from MAIL_ICP), then
@@ -400,11 +479,13 @@ struct IcpBufs {
   IcpView v{};
   QtrIcpState* h_state = nullptr;  // pinned read-back
   int* h_bbox = nullptr;
+  void* vox = nullptr;    // voxelised plane-to-plane: records and order scratch (icp_reserve_vox, on the slot's first such call)
+  int cap_vox = 0;        // points they hold
 };
 
-// the largest cell table of a call: a grid that would need more cells takes larger cells (still >= the correspondence
-// distance, so the result is the same; only the candidate lists get longer)
-#define QTR_ICP_CELL_CAP (1 << 22)
+// QTR_ICP_CELL_CAP (include/qtr_icp_math.h), the largest cell table of a call: a grid of the search methods that would need
+// more cells takes larger cells (still >= the correspondence distance, so the result is the same; only the candidate lists
+// get longer); the voxel grid of method 3 is refused instead.
 // the cell table every slot reserves for the batched refinement (qtr_submit_batch_refine), so that the lanes never allocate:
 // a larger grid takes larger cells (icp_grid_of).  2^20 cells of 1 m cover a 100 m x 100 m x 100 m box.
 #define QTR_ICP_BATCH_CELLS (1 << 20)
@@ -454,7 +535,23 @@ static hipError_t icp_reserve_cells(IcpBufs& B, int ncell) {
   return hipSuccess;
 }
 
+// the voxel records and their scratch, for clouds of cap_pts points
+static hipError_t icp_reserve_vox(IcpBufs& B, int cap_pts) {
+  if (B.vox && B.cap_vox >= cap_pts) return hipSuccess;
+  if (B.vox) (void)hipFree(B.vox);
+  B.vox = nullptr;
+  B.cap_vox = 0;
+  const size_t rec = ((size_t)cap_pts * sizeof(QtrIcpVoxel) + 255) & ~(size_t)255;
+  const hipError_t e = hipMalloc(&B.vox, rec + (size_t)cap_pts * 4 + 256);
+  if (e != hipSuccess) return e;
+  B.v.vox = (QtrIcpVoxel*)B.vox;
+  B.v.vord = (int*)((char*)B.vox + rec);
+  B.cap_vox = cap_pts;
+  return hipSuccess;
+}
+
 static void icp_free(IcpBufs& B) {
+  if (B.vox) (void)hipFree(B.vox);
   if (B.arena) (void)hipFree(B.arena);
   if (B.cells) (void)hipFree(B.cells);
   if (B.h_state) (void)hipHostFree(B.h_state);
@@ -470,7 +567,7 @@ static QtrIcpCfg icp_cfg_of(const qtr_icp_params* prm) {
   c.method = prm->method;
   c.min_corr = prm->min_correspondences > 0 ? prm->min_correspondences
                : prm->method == QTR_ICP_POINT_TO_PLANE ? 6
-               : prm->method == QTR_ICP_PLANE_TO_PLANE ? 4  // (pcl GICP's min_number_correspondences_)
+               : (prm->method == QTR_ICP_PLANE_TO_PLANE || prm->method == QTR_ICP_VOXEL_PLANE_TO_PLANE) ? 4  // (pcl GICP's min_number_correspondences_)
                                                        : 3;
   c.pad = 0;
   return c;
@@ -507,6 +604,25 @@ static bool icp_grid_of(IcpView& v, const int* bbox, double max_d, int cap_cells
   return true;
 }
 
+// The voxel grid of method 3 (include/qtr_icp_math.h): origin = the box's minimum, side = the correspondence distance
+// exactly.  The result depends on this grid, so it is never coarsened and every path derives it from this rule and
+// QTR_ICP_CELL_CAP, not from an arena's capacity.  0: no finite target point (the empty grid, as icp_grid_of leaves it),
+// 1: the view carries the grid, -1: more than QTR_ICP_CELL_CAP cells (msg names side and box).
+static int icp_voxel_grid_of(IcpView& v, const int* bbox, double side, char* msg, size_t msg_len) {
+  if (!icp_grid_of(v, bbox, side, QTR_ICP_CELL_CAP)) return 0;  // (its origin stays, its grid is overwritten below)
+  const double mx[3] = {(double)icp_dec(bbox[3]), (double)icp_dec(bbox[4]), (double)icp_dec(bbox[5])};
+  v.cell = side;
+  const double nc = qtr_icp_voxel_dims(v.mn, mx, side, v.dims);
+  if (!(nc <= (double)QTR_ICP_CELL_CAP)) {
+    snprintf(msg, msg_len, "voxelised plane-to-plane: voxels of side %g m over a box of %g x %g x %g m are %.0f cells, more than %d",
+             side, mx[0] - v.mn[0], mx[1] - v.mn[1], mx[2] - v.mn[2], nc, QTR_ICP_CELL_CAP);
+    v.ncell = v.dims[0] = v.dims[1] = v.dims[2] = 0;
+    return -1;
+  }
+  v.ncell = v.dims[0] * v.dims[1] * v.dims[2];
+  return 1;
+}
+
 static void icp_result_from(qtr_icp_result* res, const QtrIcpState& st) {
   res->valid = st.valid;
   res->converged = st.converged;
@@ -532,13 +648,17 @@ static hipError_t icp_box_enqueue(const IcpView& v, int* h_bbox, hipStream_t st)
 }
 
 // the cell grid of the view (it carries its grid now: icp_grid_of) and the initial state
-static hipError_t icp_grid_enqueue(const IcpView& v, const QtrIcpState& init, hipStream_t st) {
+static hipError_t icp_grid_enqueue(const IcpView& v, const QtrIcpState& init, hipStream_t st, bool voxels = false) {
   hipError_t e = hipMemsetAsync(v.cell_cnt, 0, (size_t)(v.ncell + 1) * 4, st);
   if (e != hipSuccess) return e;
   if (v.nt > 0) {
     hipLaunchKernelGGL(k_icp_count, dim3(qtr_div_up(v.nt, 256)), dim3(256), 0, st, v);
     if ((e = exclusive_scan_i32(v.cell_cnt, v.cell_start, v.ncell, st)) != hipSuccess) return e;
     hipLaunchKernelGGL(k_icp_place, dim3(qtr_div_up(v.nt, 256)), dim3(256), 0, st, v);
+    if (voxels) {  // (method 3: the cells' records)
+      hipLaunchKernelGGL(k_icp_voxel_order, dim3(qtr_div_up(v.nt, 256)), dim3(256), 0, st, v);
+      hipLaunchKernelGGL(k_icp_voxel_stats, dim3(qtr_div_up(v.nt, 256)), dim3(256), 0, st, v);
+    }
   }
   hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, v, init);
   return hipGetLastError();
@@ -555,22 +675,27 @@ static hipError_t icp_box_enqueue_group(const IcpView* dv, int G, int max_nt, co
 
 // the cell grids of the group (views carry their grids now) and the initial states
 static hipError_t icp_grid_enqueue_group(const IcpView* dv, const QtrIcpState* dinit, int G, int max_nt, int max_ncell,
-                                         hipStream_t st) {
+                                         hipStream_t st, bool voxels = false) {
   const ViewExt<IcpView> x{dv, {0, 0, 0}};
   hipLaunchKernelGGL(k_icp_prep_group, dim3(std::min(qtr_div_up((long long)max_ncell + 1, 256), 1024), G), dim3(256), 0, st,
                      x, dinit);
   hipLaunchKernelGGL(k_icp_count_group, dim3(qtr_div_up(max_nt, 256), G), dim3(256), 0, st, x);
   hipLaunchKernelGGL(k_icp_scan_group, dim3(1, G), dim3(1024), 0, st, x);
   hipLaunchKernelGGL(k_icp_place_group, dim3(qtr_div_up(max_nt, 256), G), dim3(256), 0, st, x);
+  if (voxels) {
+    hipLaunchKernelGGL(k_icp_voxel_order_group, dim3(qtr_div_up(max_nt, 256), G), dim3(256), 0, st, x);
+    hipLaunchKernelGGL(k_icp_voxel_stats_group, dim3(qtr_div_up(max_nt, 256), G), dim3(256), 0, st, x);
+  }
   return hipGetLastError();
 }
 
-// `launches` iterations of the group (gicp: the plane-to-plane instantiation), then every pair's state into its mailbox
+// `launches` iterations of the group (method: which instantiation), then every pair's state into its mailbox
 static hipError_t icp_iter_enqueue_group(const IcpView* dv, int G, int max_nchunk, int launches, const int* dseqs,
-                                         hipStream_t st, bool gicp) {
+                                         hipStream_t st, int method) {
   const ViewExt<IcpView> x{dv, {0, 0, 0}};
   for (int k = 0; k < launches; ++k) {
-    if (gicp) hipLaunchKernelGGL(k_icp_iter_gicp_group, dim3(max_nchunk, G), dim3(256), 0, st, x);
+    if (method == QTR_ICP_VOXEL_PLANE_TO_PLANE) hipLaunchKernelGGL(k_icp_iter_vgicp_group, dim3(max_nchunk, G), dim3(256), 0, st, x);
+    else if (method == QTR_ICP_PLANE_TO_PLANE) hipLaunchKernelGGL(k_icp_iter_gicp_group, dim3(max_nchunk, G), dim3(256), 0, st, x);
     else hipLaunchKernelGGL(k_icp_iter_group, dim3(max_nchunk, G), dim3(256), 0, st, x);
   }
   hipLaunchKernelGGL(k_icp_publish_group, dim3(G), dim3(64), 0, st, x, dseqs);

@@ -23,7 +23,7 @@ DBG_GRAPH_BITMAP, DBG_CORE, DBG_PERM, DBG_NBR_OFFSETS, DBG_NBR_INDEX, DBG_NBR_DI
 DBG_NN_LARGE_OF_SMALL, DBG_NN_SMALL_OF_LARGE, DBG_VOX_SRC, DBG_VOX_TGT, DBG_CORR, DBG_MATCH_STATS = 8, 9, 10, 11, 12, 13
 DBG_SOLVER_STATE = 14
 DBG_ICP_CORR, DBG_ICP_TRACE, DBG_ICP_TIMES = 15, 16, 17
-ICP_POINT_TO_PLANE, ICP_POINT_TO_POINT, ICP_PLANE_TO_PLANE = 0, 1, 2
+ICP_POINT_TO_PLANE, ICP_POINT_TO_POINT, ICP_PLANE_TO_PLANE, ICP_VOXEL_PLANE_TO_PLANE = 0, 1, 2, 3
 ICP_STOP_NONE, ICP_STOP_MAX_ITERATIONS, ICP_STOP_TRANSFORMATION, ICP_STOP_FITNESS, ICP_STOP_TOO_FEW, ICP_STOP_DEGENERATE = range(6)
 
 
@@ -1160,7 +1160,7 @@ class Handle:
     def icp(self, src4, tgt4, tgt_normals4=None, guess=None, params: IcpParams | None = None, slot: int = 0) -> dict:
         """6-DoF ICP of src4 onto tgt4 (qtr_icp).  numpy arrays (host) or contiguous [N,4] float32 torch device tensors
         (all on the device: mem = QTR_MEM_DEVICE).  tgt_normals4 None: the target normals are computed at
-        params.normal_radius (point-to-plane; plane-to-plane computes the source's as well: gicp with src_normals4 = None).
+        params.normal_radius (point-to-plane; plane-to-plane, voxelised or not, computes the source's as well: gicp with src_normals4 = None).
         Returns the result record as a dict (T row-major 4x4)."""
         prm = params or default_icp_params()
         if isinstance(src4, np.ndarray) or isinstance(tgt4, np.ndarray):
@@ -1185,7 +1185,8 @@ class Handle:
              slot: int = 0) -> dict:
         """Plane-to-plane (Generalized) ICP of src4 onto tgt4 with both normal sets (qtr_gicp); a normal set given as None
         is computed at params.normal_radius.  Arrays as for icp (numpy on the host, or torch tensors all on the device);
-        params None = the defaults with method = ICP_PLANE_TO_PLANE."""
+        params None = the defaults with method = ICP_PLANE_TO_PLANE; method = ICP_VOXEL_PLANE_TO_PLANE is its voxelised form
+        (VGICP: one Gaussian per target voxel of side max_correspondence_distance, a lookup in place of the search)."""
         prm = params or default_icp_params(method=ICP_PLANE_TO_PLANE)
         if isinstance(src4, np.ndarray) or isinstance(tgt4, np.ndarray):
             src4, tgt4 = _f4(src4), _f4(tgt4)
