@@ -29,6 +29,7 @@
 //      Within-core order is racy in the reference itself, so no order is "the" reference order.
 //   D3 ties: NN search -> lowest index; std::sort sites -> stable by (key, original position).
 //   D4 COTE median with n_card<=1 (UB in reference include/quatro.hpp:714-730) -> defined.
+//      A single measurement (assert(!only_one_element), :629-631) -> the measurement itself.
 //   D5 GNC rotation noise bound taken from the current params, not a function-local static
 //      (reference include/quatro.hpp:469-470); identical in the single-call demo flow.
 //   D6 2x2 weighted rotation in closed form instead of Eigen::JacobiSVD (utils.h:151-166); the

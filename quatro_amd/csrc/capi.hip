@@ -797,6 +797,16 @@ static int check_params(qtr_handle* h, const qtr_params* prm) {
     snprintf(h->err, sizeof(h->err), "invalid solver parameter");
     return QTR_ERR_BAD_ARG;
   }
+  // COTE's range is cote_noise_bound * sqrt(cbar2) (reference include/quatro.hpp:585-616): a negative or NaN range has
+  // no meaning there (intervals that close before they open, NaN sort keys); 0 is computed with under IEEE rules
+  if (!(prm->cote_noise_bound >= 0)) {
+    snprintf(h->err, sizeof(h->err), "invalid solver parameter: cote_noise_bound must be >= 0");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (!(prm->cbar2 >= 0)) {
+    snprintf(h->err, sizeof(h->err), "invalid solver parameter: cbar2 must be >= 0");
+    return QTR_ERR_BAD_ARG;
+  }
   return QTR_OK;
 }
 
