@@ -573,6 +573,79 @@ def make_submap(handle, keyframes, poses, center, half_width, fp=None, id_lo=0, 
     return handle.merge_keyframes([keyframes[i] for i in range(lo, hi)], rel, fp, slot)
 
 
+def build_map(handle, keyframes, poses, voxel_size=1.0, capacity=None):
+    """The global map: every keyframe inserted under its pose (4 x 4, keyframe frame -> map frame — what
+    Handle.optimize_pose_graph returns) into a new VoxelMap of side voxel_size, in list order.  capacity None: the sum of
+    the keyframes' voxel counts, which no map of them can exceed (at least 1).  The caller destroys the returned map; its
+    fetch() is the map cloud."""
+    assert len(keyframes) == len(poses)
+    if capacity is None:
+        capacity = max(1, sum(int(kf.info["n_voxels"]) for kf in keyframes))
+    vmap = handle.voxel_map(voxel_size, capacity)
+    try:
+        for kf, pose in zip(keyframes, poses):
+            vmap.insert_keyframe(kf, pose)
+    except Exception:
+        vmap.destroy()
+        raise
+    return vmap
+
+
+def localize(handle, vmap, keyframe, guess, icp=None):
+    """Localisation of a scan (a Keyframe) in a finished map: the voxelised plane-to-plane refinement of the keyframe
+    against vmap from `guess` (4 x 4, keyframe frame -> map frame).  The map is only read.  Returns the ICP result dict; its T
+    is the pose."""
+    return vmap.register_keyframe(keyframe, guess, icp)
+
+
+def constant_velocity_guess(T_prev2, T_prev1):
+    """T_{k-1} (T_{k-2}^-1 T_{k-1}) for rigid 4 x 4 poses, in plain float64 arithmetic of a fixed order (the inverse is
+    [R^T | -R^T t]), so every caller gets the same bits from the same poses."""
+    A = [[float(x) for x in row] for row in np.asarray(T_prev2, dtype=np.float64).reshape(4, 4)]
+    B = [[float(x) for x in row] for row in np.asarray(T_prev1, dtype=np.float64).reshape(4, 4)]
+    inv = [[A[c][r] for c in range(3)] + [-((A[0][r] * A[0][3] + A[1][r] * A[1][3]) + A[2][r] * A[2][3])] for r in range(3)]
+    inv.append([0.0, 0.0, 0.0, 1.0])
+
+    def mul(X, Y):
+        return [[((X[r][0] * Y[0][c] + X[r][1] * Y[1][c]) + X[r][2] * Y[2][c]) + X[r][3] * Y[3][c] for c in range(4)]
+                for r in range(4)]
+
+    G = mul(B, mul(inv, B))
+    G[3] = [0.0, 0.0, 0.0, 1.0]
+    return np.array(G, dtype=np.float64)
+
+
+def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capacity=None):
+    """Scan-to-map odometry: a keyframe of every scan (fp; a scan that already is a Keyframe is used as it is), the first
+    inserted at the identity, every later one registered against the map from the constant-velocity guess
+    T_{k-1} (T_{k-2}^-1 T_{k-1}) (the identity motion for the second scan) and inserted under the result.  A registration
+    that is not valid keeps its guess as the pose.  Returns (poses [K, 4, 4], vmap); the caller destroys the map.  The
+    keyframes made here are closed before the call returns.  capacity None: 1 << 20 voxels."""
+    fp = fp or _ql.default_frontend_params()
+    vmap = handle.voxel_map(voxel_size, (1 << 20) if capacity is None else capacity)
+    poses = []
+    try:
+        for k, scan in enumerate(scans):
+            own = not isinstance(scan, _ql.Keyframe)
+            kf = handle.keyframe(scan, fp) if own else scan
+            try:
+                if k == 0:
+                    T = np.eye(4)
+                else:
+                    guess = poses[-1] if k == 1 else constant_velocity_guess(poses[-2], poses[-1])
+                    r = localize(handle, vmap, kf, guess, icp)
+                    T = np.array(r["T"], dtype=np.float64) if r["valid"] else np.array(guess, dtype=np.float64)
+                vmap.insert_keyframe(kf, T)
+            finally:
+                if own:
+                    kf.close()
+            poses.append(T)
+    except Exception:
+        vmap.destroy()
+        raise
+    return (np.stack(poses) if poses else np.zeros((0, 4, 4))), vmap
+
+
 def close_loop(handle, index, keyframes, query_kf, k, id_lo=0, id_hi=None, fp=None, params=None, icp=None, poses=None,
                submap_half_width=0, evaluate=None, min_overlap=None):
     """Loop closing from the first link: index.query(query_kf) picks the k entries of [id_lo, id_hi) whose Scan Context

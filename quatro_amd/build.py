@@ -18,11 +18,14 @@ LIB = os.path.join(HERE, "libquatro_hip.so")
 # search, one-workgroup matcher tails, peeling / sweep core numbers, quadratic ranking) and the knobs that select them
 # live in a second build with -DQTR_TEST_ENGINES that only tests load (quatro_amd.lib.Handle(lib_path=...))
 TEST_LIB = os.path.join(HERE, "libquatro_hip_testengines.so")
+# the voxel map's entry points (include/quatro_voxelmap.h) are a library of their own over the same sources: libquatro_hip.so's
+# dynamic symbol table stays the C ABI of include/quatro_hip.h
+VOXELMAP_LIB = os.path.join(HERE, "libquatro_voxelmap.so")
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))) + [
     os.path.join("..", "..", "include", "qtr_math.h"), os.path.join("..", "..", "include", "qtr_icp_math.h"),
     os.path.join("..", "..", "include", "qtr_place_math.h"),
     os.path.join("..", "..", "include", "qtr_submap_math.h"), os.path.join("..", "..", "include", "qtr_eval_math.h"),
-    os.path.join("..", "..", "include", "qtr_pgo_math.h"),
+    os.path.join("..", "..", "include", "qtr_pgo_math.h"), os.path.join("..", "..", "include", "qtr_vmap_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap.h"),
     os.path.join("..", "..", "include", "quatro_hip.h")]
 
 
@@ -37,13 +40,18 @@ def build_test_engines(force: bool = False, verbose: bool = True) -> str:
     return build(force, verbose, lib=TEST_LIB, defines=("-DQTR_TEST_ENGINES",))
 
 
-def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=()) -> str:
+def build_voxelmap(force: bool = False, verbose: bool = True) -> str:
+    build(force, verbose)  # (the two libraries come from the same sources)
+    return build(force, verbose, lib=VOXELMAP_LIB, defines=("-DQTR_VOXELMAP_LIB",), exports="exports_voxelmap.map")
+
+
+def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=(), exports: str = "exports.map") -> str:
     if not force and not is_stale(lib):
         return lib
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cmd = [hipcc, *defines, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
            "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-Wno-unused-value", "-fvisibility=hidden",
-           "-Wl,--version-script=" + os.path.join(CSRC, "exports.map"),
+           "-Wl,--version-script=" + os.path.join(CSRC, exports),
            os.path.join(CSRC, "unity.hip"), "-ldl", "-o", lib]
     if verbose:
         print(" ".join(cmd), flush=True)
@@ -53,4 +61,5 @@ def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=())
 
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
+    build_voxelmap(force="--force" in sys.argv)
     build_test_engines(force="--force" in sys.argv)

@@ -105,6 +105,8 @@ struct qtr_place_index {
   qtr_place_index_info info = {};
 };
 
+struct qtr_voxel_map;  // (voxelmap.hip)
+
 struct BatchJob {
   const qtr_pair_desc* pairs = nullptr;
   int B = 0, next = 0, done = 0;
@@ -159,10 +161,12 @@ struct qtr_handle {
   std::mutex kf_mu;                    // guards `keyframes` (qtr_keyframe_create / _destroy from several threads)
   std::vector<qtr_keyframe*> keyframes;  // the live keyframes of this handle: qtr_destroy frees what the caller forgot
   std::vector<qtr_place_index*> place_indexes;  // the live place indexes, likewise (under kf_mu)
+  std::vector<qtr_voxel_map*> voxel_maps;       // the live voxel maps, likewise (voxelmap.hip)
   char err[512];
 };
 
 static std::atomic<unsigned long long> g_handle_uid{0};
+static void vmap_free_all(qtr_handle* h);  // (voxelmap.hip)
 
 #define QTR_TRY(expr)                  \
   do {                                 \
@@ -423,6 +427,7 @@ void qtr_destroy(qtr_handle* h) {
     delete ix;
   }
   h->place_indexes.clear();
+  vmap_free_all(h);
   for (auto& l : h->lanes) {
     if (l.stage.h) (void)hipHostFree(l.stage.h);
     if (l.stage.d) (void)hipFree(l.stage.d);

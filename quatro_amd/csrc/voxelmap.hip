@@ -1,0 +1,716 @@
+// voxelmap.hip — the persistent Gaussian voxel map (qtr_voxel_map_*, include/quatro_voxelmap.h): one record per voxel of a world-anchored grid, kept in
+// HBM between calls.  Clouds and keyframes are inserted under poses, scans are registered against it with the VGICP
+// iteration of icp.hip, and the voxel means come back as the map cloud.  The arithmetic is include/qtr_vmap_math.h.
+//
+// The entry points are the exports of a library of their own, libquatro_voxelmap.so: the same unity.hip built with
+// -DQTR_VOXELMAP_LIB and exports_voxelmap.map, so that it shares every structure of the handle with libquatro_hip.so, whose
+// own symbol table stays the C ABI of include/quatro_hip.h.  A handle made by one library is used by the other: both run the
+// same code on the same HIP runtime, and nothing here touches a file-scope variable of capi.hip.
+//
+// Table: open addressing with linear probing over S slots (a power of two >= 2 x capacity), 64-bit keys, QTR_VMAP_EMPTY for
+// a free slot.  Everything a voxel owns lives at its slot: member count, the raw sums acc[9] and the FINISHED record
+// (qtr_icp_voxel_finish, stored beside acc: a lookup is then one record load, as in method 3, instead of nine loads, six
+// divisions and the finish per source point and iteration; the bits are the same either way).  Which slot a key lands in
+// differs from run to run; nothing that leaves this file depends on it (fetches are in ascending key order).
+//
+// Insert of n points (the chain of method 3's build with a dense id per TOUCHED voxel in place of the cell number):
+//   k_vmap_claim   member test, key, find-or-claim the slot with the returning 64-bit atomicCAS (agent scope: a probe sees
+//                  other CUs' claims), rank among the call's members of that slot (atomic, order free)
+//   k_vmap_assign  the rank-0 member of every touched slot takes a dense id d, notes the slot and its member count, and
+//                  zeroes the slot's rank counter again
+//   (host)         reads four counters back; more voxels than capacity: k_vmap_rollback frees the slots this call claimed
+//                  (they still have n = 0, and with linear probing a key claimed by this call is never on the probe path of
+//                  an older key) and the call returns QTR_ERR_CAPACITY with the map as it was
+//   scan           exclusive_scan_i32 over the <= n dense ids
+//   k_vmap_place   member i -> list[start[d] + rank]
+//   k_vmap_order   its rank by ascending point index among the members of d (a count over the voxel's list)
+//   k_vmap_fold    one thread per touched voxel: continues the stored acc over its members in ascending index, stores acc,
+//                  the count and the finished record
+// No kernel waits for another workgroup, none is launched cooperatively, all stores are plain vector stores.
+//
+// Registration: k_vmap_iter is d_icp_iter<3> (icp.hip) with the hash lookup in place of the dense cell table: the slot's
+// IcpBufs state, partials, ticket, trace and corr, icp_reduce_tail<QTR_ICP_T_W + 1, QTR_ICP_NT>, qtr_icp_step, the stop
+// flag's early return.  Lookups are plain loads: the table was written by earlier launches.
+#ifndef QTR_VOXELMAP_LIB  // libquatro_hip.so carries this code (its handle frees the maps) but exports none of it
+#define QTR_VMAP_API __attribute__((visibility("hidden")))
+#endif
+#include "../../include/quatro_voxelmap.h"
+#include "../../include/qtr_vmap_math.h"
+
+struct VmapView {
+  u64* keys;          // [S]
+  int* cnt;           // [S] members (0 with a key: claimed by an insert that has not folded yet)
+  double* acc;        // [S][9]
+  QtrIcpVoxel* rec;   // [S]
+  u64 mask;           // S - 1
+  double side;
+};
+
+enum { VM_CTR_MEMBERS = 0, VM_CTR_NEW, VM_CTR_TOUCHED, VM_CTR_OVERFLOW, VM_CTR_INTS = 16 };
+
+struct VmapIns {
+  const float4* pts;
+  const float4* nrm;
+  int n;
+  double P[12];
+  int* slot_of;   // [n] slot of member i (-1: not a member)
+  int* rank;      // [n] atomic rank among the call's members of that slot
+  int* tcnt;      // [S] the rank counters (zero between calls)
+  int* did;       // [S] dense id of a touched slot (valid for the slots this call touched)
+  int* dcnt;      // [n + 1] members per dense id
+  int* dstart;    // [n + 1] its exclusive scan
+  int* dslot;     // [n] slot of a dense id
+  int* list;      // [n] members by dense id, atomic-rank order
+  int* ord;       // [n] ... in ascending point index
+  int* ctr;       // [VM_CTR_INTS]
+};
+
+__device__ __forceinline__ bool d_vmap_member(const VmapView& m, const VmapIns& a, int i, double* X, double* w, u64* key) {
+  const float4 p = a.pts[i];
+  const float4 b = a.nrm[i];
+  double P[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) P[k] = a.P[k];
+  return qtr_vmap_member(P, p.x, p.y, p.z, b.x, b.y, b.z, m.side, X, w, key);
+}
+
+__global__ __launch_bounds__(256) void k_vmap_claim(VmapView m, VmapIns a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  double X[3], w[3];
+  u64 key = 0;
+  if (!d_vmap_member(m, a, i, X, w, &key)) {
+    a.slot_of[i] = -1;
+    return;
+  }
+  u64 s = qtr_vmap_hash(key, m.mask);
+  bool found = false;
+  for (u64 probe = 0; probe <= m.mask; ++probe) {
+    const u64 old = atomicCAS(m.keys + s, (u64)QTR_VMAP_EMPTY, key);  // (the returning CAS is the probe)
+    if (old == QTR_VMAP_EMPTY) {
+      atomicAdd(a.ctr + VM_CTR_NEW, 1);
+      found = true;
+      break;
+    }
+    if (old == key) {
+      found = true;
+      break;
+    }
+    s = (s + 1) & m.mask;
+  }
+  if (!found) {  // every slot holds another key: more voxels than slots, the call is refused
+    atomicOr(a.ctr + VM_CTR_OVERFLOW, 1);
+    a.slot_of[i] = -1;
+    return;
+  }
+  a.slot_of[i] = (int)s;
+  a.rank[i] = atomicAdd(a.tcnt + s, 1);
+  atomicAdd(a.ctr + VM_CTR_MEMBERS, 1);
+}
+
+__global__ __launch_bounds__(256) void k_vmap_assign(VmapView m, VmapIns a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const int s = a.slot_of[i];
+  if (s < 0 || a.rank[i] != 0) return;
+  const int d = atomicAdd(a.ctr + VM_CTR_TOUCHED, 1);
+  a.did[s] = d;
+  a.dcnt[d] = a.tcnt[s];
+  a.dslot[d] = s;
+  a.tcnt[s] = 0;
+}
+
+// a refused insert: the slots it claimed (a key and still no member) are free again
+__global__ __launch_bounds__(256) void k_vmap_rollback(VmapView m, VmapIns a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const int s = a.slot_of[i];
+  if (s < 0 || a.rank[i] != 0) return;
+  if (m.cnt[s] == 0) m.keys[s] = QTR_VMAP_EMPTY;
+}
+
+__global__ __launch_bounds__(256) void k_vmap_place(VmapIns a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const int s = a.slot_of[i];
+  if (s < 0) return;
+  a.list[a.dstart[a.did[s]] + a.rank[i]] = i;
+}
+
+__global__ __launch_bounds__(256) void k_vmap_order(VmapIns a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const int s = a.slot_of[i];
+  if (s < 0) return;
+  const int d = a.did[s];
+  const int b = a.dstart[d], e = a.dstart[d + 1];
+  int r = 0;
+  for (int j = b; j < e; ++j) r += a.list[j] < i ? 1 : 0;
+  a.ord[b + r] = i;
+}
+
+__global__ __launch_bounds__(256) void k_vmap_fold(VmapView m, VmapIns a, int n_touched) {
+  const int d = blockIdx.x * blockDim.x + threadIdx.x;
+  if (d >= n_touched) return;
+  const int s = a.dslot[d];
+  const int b = a.dstart[d], e = a.dstart[d + 1];
+  int n = m.cnt[s];
+  double acc[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) acc[k] = n > 0 ? m.acc[(size_t)s * 9 + k] : 0.0;
+  for (int r = b; r < e; ++r) {
+    double X[3], w[3];
+    u64 key;
+    if (!d_vmap_member(m, a, a.ord[r], X, w, &key)) continue;  // (never: the list holds members)
+    qtr_vmap_add(acc, X, w);
+    ++n;
+  }
+#pragma unroll
+  for (int k = 0; k < 9; ++k) m.acc[(size_t)s * 9 + k] = acc[k];
+  m.cnt[s] = n;
+  QtrIcpVoxel vx;
+  qtr_icp_voxel_finish(acc, n, 0, &vx);
+  m.rec[s] = vx;
+}
+
+// the slot of a key written by an earlier launch (-1: no such voxel)
+__device__ __forceinline__ long long d_vmap_find(const VmapView& m, u64 key) {
+  u64 s = qtr_vmap_hash(key, m.mask);
+  for (u64 probe = 0; probe <= m.mask; ++probe) {
+    const u64 k = m.keys[s];
+    if (k == key) return (long long)s;
+    if (k == QTR_VMAP_EMPTY) return -1;
+    s = (s + 1) & m.mask;
+  }
+  return -1;
+}
+
+// one iteration of a registration against the map: d_icp_iter<3> with the hash lookup in place of the dense cell table
+__global__ __launch_bounds__(256) void k_vmap_iter(IcpView v, VmapView m) {
+  __shared__ double s_S[QTR_ICP_NT];
+  const QtrIcpState* st = v.st;
+  if (st->stop) return;  // (uniform: written by an earlier launch)
+  const int blk = (int)blockIdx.x, nblk = (int)gridDim.x;
+  double T[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) T[k] = st->T[k];
+  const int i = blk * QTR_ICP_CHUNK + threadIdx.x;
+  double o[QTR_ICP_NT];
+#pragma unroll
+  for (int k = 0; k < QTR_ICP_NT; ++k) o[k] = 0.0;
+  if (i < v.ns) {
+    const float4 p = v.src[i];
+    const float4 a = v.src_nrm[i];
+    double q[3];
+    u64 key = 0;
+    int best = -1;
+    if (qtr_vmap_query(T, p.x, p.y, p.z, a.x, a.y, a.z, m.side, q, &key)) {
+      const long long s = d_vmap_find(m, key);
+      if (s >= 0) {
+        const QtrIcpVoxel vx = m.rec[s];
+        if (m.cnt[s] > 0 && vx.n > 0) {
+          best = 0;
+          qtr_icp_vgicp_terms(T, q, a.x, a.y, a.z, &vx, o);
+        }
+      }
+    }
+    v.corr[i] = best;
+  }
+  constexpr int NT = QTR_ICP_T_W + 1;
+  if (!icp_reduce_tail<NT, QTR_ICP_NT>(o, v.partials, v.ticket, blk, nblk, s_S)) return;
+  if (threadIdx.x == 0) {
+    for (int k = NT; k < QTR_ICP_NT; ++k) s_S[k] = 0.0;  // (the padding terms)
+    QtrIcpState s = *v.st;
+    double* tr = (s.iterations < v.cfg.max_iterations) ? v.trace + (size_t)s.iterations * 18 : nullptr;
+    qtr_icp_step(&v.cfg, s_S, &s, tr);
+    *v.st = s;
+    __hip_atomic_store(v.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// a fetch section of the voxels at slots[0 .. n), in that order
+__global__ __launch_bounds__(256) void k_vmap_gather(VmapView m, const int* __restrict__ slots, int n, int what, void* out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int s = slots[j];
+  if (what == QTR_VMAP_SUMS) {
+    for (int k = 0; k < 9; ++k) ((double*)out)[(size_t)j * 9 + k] = m.acc[(size_t)s * 9 + k];
+  } else if (what == QTR_VMAP_RECORDS) {
+    const QtrIcpVoxel vx = m.rec[s];
+    for (int k = 0; k < 3; ++k) ((double*)out)[(size_t)j * 9 + k] = vx.mu[k];
+    for (int k = 0; k < 6; ++k) ((double*)out)[(size_t)j * 9 + 3 + k] = vx.C[k];
+  } else {  // QTR_VMAP_CLOUD
+    const QtrIcpVoxel vx = m.rec[s];
+    ((float4*)out)[j] = make_float4((float)vx.mu[0], (float)vx.mu[1], (float)vx.mu[2], (float)vx.n);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_vmap_clear(VmapView m, int* tcnt) {
+  for (u64 e = blockIdx.x * (u64)blockDim.x + threadIdx.x; e <= m.mask; e += (u64)gridDim.x * blockDim.x) {
+    m.keys[e] = QTR_VMAP_EMPTY;
+    m.cnt[e] = 0;
+    tcnt[e] = 0;
+  }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------
+struct qtr_voxel_map {
+  qtr_handle* owner = nullptr;
+  void* table = nullptr;    // keys, cnt, acc, rec, tcnt, did
+  void* scratch = nullptr;  // the insert's per-point arrays (max_points points), allocated on the first insert
+  int* pin = nullptr;       // pinned: the counters' read-back
+  VmapView v{};
+  VmapIns ins{};
+  hipStream_t stream = nullptr;  // clear and fetch, which take no slot
+  qtr_voxel_map_info info = {};
+};
+
+static bool vmap_pose_ok(const double* P) {
+  for (int k = 0; k < 12; ++k)
+    if (!icp_finite(P[k])) return false;
+  return true;
+}
+
+static int vmap_check(qtr_handle* h, const qtr_voxel_map* m) {
+  if (!m) {
+    snprintf(h->err, sizeof(h->err), "voxel map is NULL");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (m->owner != h) {
+    snprintf(h->err, sizeof(h->err), "voxel map belongs to another handle");
+    return QTR_ERR_BAD_ARG;
+  }
+  return QTR_OK;
+}
+
+static int vmap_check_kf(qtr_handle* h, const qtr_keyframe* kf) {
+  if (!kf) {
+    snprintf(h->err, sizeof(h->err), "keyframe is NULL");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (kf->owner != h) {
+    snprintf(h->err, sizeof(h->err), "keyframe belongs to another handle");
+    return QTR_ERR_BAD_ARG;
+  }
+  return QTR_OK;
+}
+
+static void vmap_release(qtr_voxel_map* m) {
+  if (m->stream) {
+    (void)hipStreamSynchronize(m->stream);
+    (void)hipStreamDestroy(m->stream);
+  }
+  if (m->table) (void)hipFree(m->table);
+  if (m->scratch) (void)hipFree(m->scratch);
+  if (m->pin) (void)hipHostFree(m->pin);
+  delete m;
+}
+
+// the maps the caller did not destroy (qtr_destroy)
+static void vmap_free_all(qtr_handle* h) {
+  for (qtr_voxel_map* m : h->voxel_maps) vmap_release(m);
+  h->voxel_maps.clear();
+}
+
+void qtr_default_voxel_map_params(qtr_voxel_map_params* p) {
+  if (!p) return;
+  memset(p, 0, sizeof(*p));
+  p->voxel_size = 1.0;
+  p->capacity = 1 << 20;
+}
+
+int qtr_voxel_map_create(qtr_handle* h, const qtr_voxel_map_params* params, qtr_voxel_map** out) {
+  if (out) *out = nullptr;
+  if (!h || !out) return QTR_ERR_BAD_ARG;
+  qtr_voxel_map_params prm;
+  qtr_default_voxel_map_params(&prm);
+  if (params) prm = *params;
+  if (!icp_finite(prm.voxel_size) || !(prm.voxel_size > 0)) {
+    snprintf(h->err, sizeof(h->err), "voxel map: voxel_size %g must be finite and positive", prm.voxel_size);
+    return QTR_ERR_BAD_ARG;
+  }
+  if (prm.capacity < 1 || prm.capacity > QTR_VMAP_MAX_CAPACITY) {
+    snprintf(h->err, sizeof(h->err), "voxel map: capacity %d (1 .. %d)", prm.capacity, QTR_VMAP_MAX_CAPACITY);
+    return QTR_ERR_BAD_ARG;
+  }
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  size_t S = 64;
+  while (S < (size_t)2 * (size_t)prm.capacity) S <<= 1;
+  qtr_voxel_map* m = new (std::nothrow) qtr_voxel_map();
+  if (!m) return QTR_ERR_CAPACITY;
+  const size_t rec_bytes = (S * sizeof(QtrIcpVoxel) + 255) & ~(size_t)255;
+  const size_t bytes = S * 8 + S * 72 + rec_bytes + 3 * S * 4 + 1024;
+  hipError_t e = hipMalloc(&m->table, bytes);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&m->pin, VM_CTR_INTS * sizeof(int));
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
+  if (e == hipSuccess) {
+    char* p = (char*)m->table;
+    m->v.keys = (u64*)p;
+    p += S * 8;
+    m->v.acc = (double*)p;
+    p += S * 72;
+    m->v.rec = (QtrIcpVoxel*)p;
+    p += rec_bytes;
+    m->v.cnt = (int*)p;
+    p += S * 4;
+    m->ins.tcnt = (int*)p;
+    p += S * 4;
+    m->ins.did = (int*)p;
+    m->v.mask = (u64)S - 1;
+    m->v.side = prm.voxel_size;
+    hipLaunchKernelGGL(k_vmap_clear, dim3(std::min(qtr_div_up((long long)S, 256), 2048)), dim3(256), 0, m->stream, m->v, m->ins.tcnt);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    snprintf(h->err, sizeof(h->err), "voxel map: %zu bytes for %d voxels: %s", bytes, prm.capacity, hipGetErrorString(e));
+    vmap_release(m);
+    return QTR_ERR_HIP;
+  }
+  m->owner = h;
+  m->info.voxel_size = prm.voxel_size;
+  m->info.capacity = prm.capacity;
+  {
+    std::lock_guard<std::mutex> lk(h->kf_mu);
+    h->voxel_maps.push_back(m);
+  }
+  *out = m;
+  return QTR_OK;
+}
+
+void qtr_voxel_map_destroy(qtr_handle* h, qtr_voxel_map* m) {
+  if (!h || !m || m->owner != h) return;
+  {
+    std::lock_guard<std::mutex> lk(h->kf_mu);
+    auto it = std::find(h->voxel_maps.begin(), h->voxel_maps.end(), m);
+    if (it == h->voxel_maps.end()) return;
+    h->voxel_maps.erase(it);
+  }
+  (void)hipSetDevice(h->device);
+  vmap_release(m);
+}
+
+int qtr_voxel_map_clear(qtr_handle* h, int slot, qtr_voxel_map* m) {
+  Slot* sp = peek_slot(h, slot);
+  if (!sp) return QTR_ERR_BAD_ARG;
+  QTR_TRY(vmap_check(h, m));
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  const size_t S = (size_t)m->v.mask + 1;
+  hipLaunchKernelGGL(k_vmap_clear, dim3(std::min(qtr_div_up((long long)S, 256), 2048)), dim3(256), 0, sp->stream, m->v, m->ins.tcnt);
+  QTR_HIP_TRY(h, hipGetLastError());
+  QTR_HIP_TRY(h, hipStreamSynchronize(sp->stream));
+  m->info.n_voxels = 0;
+  m->info.n_inserts = 0;
+  m->info.n_members = 0;
+  return QTR_OK;
+}
+
+int qtr_voxel_map_get_info(const qtr_voxel_map* m, qtr_voxel_map_info* info) {
+  if (!m || !info) return QTR_ERR_BAD_ARG;
+  *info = m->info;
+  return QTR_OK;
+}
+
+static int vmap_scratch(qtr_handle* h, qtr_voxel_map* m) {
+  if (m->scratch) return QTR_OK;
+  const size_t np = ((size_t)h->lim.max_points + 64 + 63) & ~(size_t)63;
+  QTR_HIP_TRY(h, hipMalloc(&m->scratch, 7 * np * 4 + VM_CTR_INTS * 4));
+  int* p = (int*)m->scratch;
+  m->ins.slot_of = p;
+  m->ins.rank = p + np;
+  m->ins.dcnt = p + 2 * np;
+  m->ins.dstart = p + 3 * np;
+  m->ins.dslot = p + 4 * np;
+  m->ins.list = p + 5 * np;
+  m->ins.ord = p + 6 * np;
+  m->ins.ctr = p + 7 * np;
+  return QTR_OK;
+}
+
+// the insert of n device-resident points with their normals
+static int vmap_insert_device(qtr_handle* h, Slot& s, qtr_voxel_map* m, const float4* d_pts, const float4* d_nrm, int n,
+                              const double* pose, qtr_voxel_map_insert_info* out) {
+  qtr_voxel_map_insert_info info = {};
+  info.n_points = n;
+  if (n > 0) {
+    QTR_TRY(vmap_scratch(h, m));
+    VmapIns& a = m->ins;
+    a.pts = d_pts;
+    a.nrm = d_nrm;
+    a.n = n;
+    for (int k = 0; k < 12; ++k) a.P[k] = pose ? pose[k] : kIcpIdentity[k];
+    const hipStream_t st = s.stream;
+    const dim3 grid(qtr_div_up(n, 256)), blk(256);
+    QTR_HIP_TRY(h, hipMemsetAsync(a.ctr, 0, VM_CTR_INTS * sizeof(int), st));
+    hipLaunchKernelGGL(k_vmap_claim, grid, blk, 0, st, m->v, a);
+    hipLaunchKernelGGL(k_vmap_assign, grid, blk, 0, st, m->v, a);
+    QTR_HIP_TRY(h, hipGetLastError());
+    QTR_HIP_TRY(h, hipMemcpyAsync(m->pin, a.ctr, VM_CTR_INTS * sizeof(int), hipMemcpyDeviceToHost, st));
+    QTR_HIP_TRY(h, hipStreamSynchronize(st));
+    const int n_new = m->pin[VM_CTR_NEW], n_touched = m->pin[VM_CTR_TOUCHED];
+    if (m->pin[VM_CTR_OVERFLOW] || (long long)m->info.n_voxels + n_new > (long long)m->info.capacity) {
+      hipLaunchKernelGGL(k_vmap_rollback, grid, blk, 0, st, m->v, a);
+      QTR_HIP_TRY(h, hipGetLastError());
+      QTR_HIP_TRY(h, hipStreamSynchronize(st));
+      if (m->pin[VM_CTR_OVERFLOW])
+        snprintf(h->err, sizeof(h->err), "voxel map: the insert needs more than %d new voxels on top of %d, which exceeds capacity=%d",
+                 n_new, m->info.n_voxels, m->info.capacity);
+      else
+        snprintf(h->err, sizeof(h->err), "voxel map: the insert needs %d new voxels on top of %d, which exceeds capacity=%d", n_new,
+                 m->info.n_voxels, m->info.capacity);
+      return QTR_ERR_CAPACITY;
+    }
+    if (n_touched > 0) {
+      QTR_HIP_TRY(h, exclusive_scan_i32(a.dcnt, a.dstart, n_touched, st));
+      hipLaunchKernelGGL(k_vmap_place, grid, blk, 0, st, a);
+      hipLaunchKernelGGL(k_vmap_order, grid, blk, 0, st, a);
+      hipLaunchKernelGGL(k_vmap_fold, dim3(qtr_div_up(n_touched, 256)), blk, 0, st, m->v, a, n_touched);
+      QTR_HIP_TRY(h, hipGetLastError());
+      QTR_HIP_TRY(h, hipStreamSynchronize(st));
+    }
+    info.n_members = m->pin[VM_CTR_MEMBERS];
+    info.n_new_voxels = n_new;
+    info.n_touched_voxels = n_touched;
+    m->info.n_voxels += n_new;
+    m->info.n_members += info.n_members;
+  }
+  m->info.n_inserts += 1;
+  if (out) *out = info;
+  return QTR_OK;
+}
+
+int qtr_voxel_map_insert(qtr_handle* h, int slot, qtr_voxel_map* m, const float* xyz4, const float* normals4, int n,
+                         const double pose[16], int mem, qtr_voxel_map_insert_info* out) {
+  if (out) memset(out, 0, sizeof(*out));
+  Slot* sp = get_slot(h, slot);
+  if (!sp) return QTR_ERR_BAD_ARG;
+  Slot& s = *sp;
+  QTR_TRY(vmap_check(h, m));
+  if (n < 0 || (n > 0 && !xyz4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) {
+    snprintf(h->err, sizeof(h->err), "bad voxel map insert arguments");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (!normals4) {
+    snprintf(h->err, sizeof(h->err), "voxel map insert: normals4 is NULL (the cloud entries do not compute normals)");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (pose && !vmap_pose_ok(pose)) {
+    snprintf(h->err, sizeof(h->err), "voxel map insert: the pose has a non-finite entry in rows 0 - 2");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (n > h->lim.max_points) {
+    snprintf(h->err, sizeof(h->err), "voxel map insert: n=%d exceeds max_points=%d", n, h->lim.max_points);
+    return QTR_ERR_CAPACITY;
+  }
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  const float4 *d_pts = (const float4*)xyz4, *d_nrm = (const float4*)normals4;
+  if (mem == QTR_MEM_HOST && n > 0) {
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, xyz4, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_tgt, normals4, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
+    d_pts = s.in_src;
+    d_nrm = s.in_tgt;
+  }
+  return vmap_insert_device(h, s, m, d_pts, d_nrm, n, pose, out);
+}
+
+int qtr_voxel_map_insert_keyframe(qtr_handle* h, int slot, qtr_voxel_map* m, const qtr_keyframe* kf, const double pose[16],
+                                  qtr_voxel_map_insert_info* out) {
+  if (out) memset(out, 0, sizeof(*out));
+  Slot* sp = get_slot(h, slot);
+  if (!sp) return QTR_ERR_BAD_ARG;
+  QTR_TRY(vmap_check(h, m));
+  QTR_TRY(vmap_check_kf(h, kf));
+  if (pose && !vmap_pose_ok(pose)) {
+    snprintf(h->err, sizeof(h->err), "voxel map insert: the pose has a non-finite entry in rows 0 - 2");
+    return QTR_ERR_BAD_ARG;
+  }
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  const KfLayout lay = kf_layout(kf->info.n_voxels);
+  return vmap_insert_device(h, *sp, m, (const float4*)((const char*)kf->dev + lay.vox),
+                            (const float4*)((const char*)kf->dev + lay.normals), kf->info.n_voxels, pose, out);
+}
+
+// the registration of ns device-resident points with their normals: icp_device's loop with k_vmap_iter
+static int vmap_register_device(qtr_handle* h, Slot& s, const qtr_voxel_map* m, const float4* d_src, int ns,
+                                const float4* d_nrm, const double* guess, const qtr_icp_params* prm, qtr_icp_result* res) {
+  QtrIcpState init;
+  qtr_icp_init(&init, guess);
+  init.reason = QTR_ICP_STOP_TOO_FEW;  // (what an empty cloud reports; the device state starts RUNNING)
+  icp_result_from(res, init);
+  res->status = QTR_OK;
+  s.icp_ns = 0;
+  s.icp_iters = 0;
+  s.icp_ms[0] = s.icp_ms[1] = 0.f;
+  if (ns == 0) return QTR_OK;
+  IcpBufs& B = s.icp;
+  QTR_HIP_TRY(h, icp_reserve(B, std::max(h->lim.max_voxels, h->lim.max_points), QTR_ICP_MAX_ITERATIONS));
+  IcpView& v = B.v;
+  v.src = d_src;
+  v.tgt = nullptr;
+  v.nrm = nullptr;
+  v.src_nrm = d_nrm;
+  v.ns = ns;
+  v.nt = 0;
+  v.ncell = v.dims[0] = v.dims[1] = v.dims[2] = 0;
+  v.cfg = icp_cfg_of(prm);
+  v.cfg.max_d2 = m->v.side * m->v.side;  // (not read: the side is the map's)
+  const hipStream_t st = s.stream;
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[0], st));
+  QtrIcpState st0;
+  qtr_icp_init(&st0, guess);
+  hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, v, st0);
+  QTR_HIP_TRY(h, hipGetLastError());
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[1], st));
+  const int nchunk = qtr_div_up(ns, QTR_ICP_CHUNK);
+  const int block = h->icp_block > 0 ? h->icp_block : prm->max_iterations;
+  for (int it = 0; it < prm->max_iterations;) {
+    const int k_end = std::min(block, prm->max_iterations - it);
+    for (int k = 0; k < k_end; ++k) hipLaunchKernelGGL(k_vmap_iter, dim3(nchunk), dim3(256), 0, st, v, m->v);
+    QTR_HIP_TRY(h, hipGetLastError());
+    it += k_end;
+    if (it >= prm->max_iterations) break;
+    QTR_HIP_TRY(h, hipMemcpyAsync(B.h_state, v.st, sizeof(QtrIcpState), hipMemcpyDeviceToHost, st));
+    QTR_HIP_TRY(h, hipStreamSynchronize(st));
+    if (B.h_state->stop) break;
+  }
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[2], st));
+  QTR_HIP_TRY(h, hipMemcpyAsync(B.h_state, v.st, sizeof(QtrIcpState), hipMemcpyDeviceToHost, st));
+  QTR_HIP_TRY(h, hipStreamSynchronize(st));
+  icp_result_from(res, *B.h_state);
+  s.icp_ns = ns;
+  s.icp_iters = B.h_state->iterations;
+  float ms = 0;
+  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.icp_ms[0] = ms;
+  if (hipEventElapsedTime(&ms, s.ev[1], s.ev[2]) == hipSuccess) s.icp_ms[1] = ms;
+  s.times_pending = 0;
+  s.times = qtr_stage_times{};
+  s.times.total = s.icp_ms[0] + s.icp_ms[1];
+  return QTR_OK;
+}
+
+static int vmap_check_register(qtr_handle* h, const qtr_voxel_map* m, const double* guess, const qtr_icp_params* prm) {
+  QTR_TRY(vmap_check(h, m));
+  QTR_TRY(check_icp_params(h, prm));
+  if (prm->method != QTR_ICP_VOXEL_PLANE_TO_PLANE) {
+    snprintf(h->err, sizeof(h->err), "voxel map register: method must be QTR_ICP_VOXEL_PLANE_TO_PLANE");
+    return QTR_ERR_BAD_ARG;
+  }
+  if (guess && !vmap_pose_ok(guess)) {
+    snprintf(h->err, sizeof(h->err), "voxel map register: the guess has a non-finite entry in rows 0 - 2");
+    return QTR_ERR_BAD_ARG;
+  }
+  return QTR_OK;
+}
+
+// the guess as the state takes it: rows 0 - 2 the caller's, row 3 (0 0 0 1)
+static void vmap_guess(const double* guess, double* g) {
+  for (int k = 0; k < 16; ++k) g[k] = kIcpIdentity[k];
+  if (guess)
+    for (int k = 0; k < 12; ++k) g[k] = guess[k];
+}
+
+int qtr_voxel_map_register(qtr_handle* h, int slot, const qtr_voxel_map* m, const float* src4, int n, const float* src_normals4,
+                           const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res, int mem) {
+  Slot* sp = get_slot(h, slot);
+  if (!sp || !res) return QTR_ERR_BAD_ARG;
+  memset(res, 0, sizeof(*res));
+  Slot& s = *sp;
+  int rc = vmap_check_register(h, m, guess, prm);
+  if (rc != QTR_OK) return res->status = rc;
+  if (n < 0 || (n > 0 && !src4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) {
+    snprintf(h->err, sizeof(h->err), "bad voxel map register arguments");
+    return res->status = QTR_ERR_BAD_ARG;
+  }
+  if (!src_normals4) {
+    snprintf(h->err, sizeof(h->err), "voxel map register: src_normals4 is NULL (the cloud entries do not compute normals)");
+    return res->status = QTR_ERR_BAD_ARG;
+  }
+  if (n > h->lim.max_points) {
+    snprintf(h->err, sizeof(h->err), "voxel map register: n=%d exceeds max_points=%d", n, h->lim.max_points);
+    return res->status = QTR_ERR_CAPACITY;
+  }
+  rc = [&]() -> int {
+    QTR_HIP_TRY(h, hipSetDevice(h->device));
+    const float4 *d_src = (const float4*)src4, *d_nrm = (const float4*)src_normals4;
+    if (mem == QTR_MEM_HOST && n > 0) {
+      QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, src4, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
+      QTR_HIP_TRY(h, hipMemcpyAsync(s.in_tgt, src_normals4, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
+      d_src = s.in_src;
+      d_nrm = s.in_tgt;
+    }
+    double g[16];
+    vmap_guess(guess, g);
+    return vmap_register_device(h, s, m, d_src, n, d_nrm, g, prm, res);
+  }();
+  return res->status = rc;
+}
+
+int qtr_voxel_map_register_keyframe(qtr_handle* h, int slot, const qtr_voxel_map* m, const qtr_keyframe* kf,
+                                    const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res) {
+  Slot* sp = get_slot(h, slot);
+  if (!sp || !res) return QTR_ERR_BAD_ARG;
+  memset(res, 0, sizeof(*res));
+  int rc = vmap_check_register(h, m, guess, prm);
+  if (rc == QTR_OK) rc = vmap_check_kf(h, kf);
+  if (rc != QTR_OK) return res->status = rc;
+  rc = [&]() -> int {
+    QTR_HIP_TRY(h, hipSetDevice(h->device));
+    const KfLayout lay = kf_layout(kf->info.n_voxels);
+    double g[16];
+    vmap_guess(guess, g);
+    return vmap_register_device(h, *sp, m, (const float4*)((const char*)kf->dev + lay.vox), kf->info.n_voxels,
+                                (const float4*)((const char*)kf->dev + lay.normals), g, prm, res);
+  }();
+  return res->status = rc;
+}
+
+long long qtr_voxel_map_fetch(qtr_handle* h, const qtr_voxel_map* m, int what, void* dst, size_t bytes) {
+  if (!h || !m || m->owner != h) return -1;
+  size_t per = 0;
+  switch (what) {
+    case QTR_VMAP_COORDS: per = 12; break;
+    case QTR_VMAP_COUNT: per = 4; break;
+    case QTR_VMAP_SUMS:
+    case QTR_VMAP_RECORDS: per = 72; break;
+    case QTR_VMAP_CLOUD: per = 16; break;
+    default: return -1;
+  }
+  const size_t nv = (size_t)m->info.n_voxels, have = nv * per;
+  const size_t want = have < bytes ? have : bytes;
+  if (!dst || want == 0) return (long long)have;
+  if (hipSetDevice(h->device) != hipSuccess) return -1;
+  // the occupied slots in ascending key order (sorted on the host: not a hot path)
+  const size_t S = (size_t)m->v.mask + 1;
+  std::vector<u64> keys(S);
+  std::vector<int> cnt(S);
+  if (hipMemcpy(keys.data(), m->v.keys, S * 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (hipMemcpy(cnt.data(), m->v.cnt, S * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  std::vector<int> slots;
+  slots.reserve(nv);
+  for (size_t s = 0; s < S; ++s)
+    if (keys[s] != QTR_VMAP_EMPTY && cnt[s] > 0) slots.push_back((int)s);
+  std::sort(slots.begin(), slots.end(), [&](int a, int b) { return keys[a] < keys[b]; });
+  if (slots.size() != nv) return -1;
+  std::vector<char> out(have);
+  if (what == QTR_VMAP_COORDS) {
+    for (size_t j = 0; j < nv; ++j) qtr_vmap_key_coords(keys[slots[j]], (int*)out.data() + 3 * j);
+  } else if (what == QTR_VMAP_COUNT) {
+    for (size_t j = 0; j < nv; ++j) ((int*)out.data())[j] = cnt[slots[j]];
+  } else {
+    void* d = nullptr;
+    if (hipMalloc(&d, have + nv * 4) != hipSuccess) return -1;
+    int* d_slots = (int*)((char*)d + have);
+    bool ok = hipMemcpy(d_slots, slots.data(), nv * 4, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+      hipLaunchKernelGGL(k_vmap_gather, dim3(qtr_div_up((long long)nv, 256)), dim3(256), 0, m->stream, m->v, d_slots, (int)nv,
+                         what, d);
+      ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(m->stream) == hipSuccess &&
+           hipMemcpy(out.data(), d, have, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(d);
+    if (!ok) return -1;
+  }
+  memcpy(dst, out.data(), want);
+  return (long long)have;
+}

@@ -146,7 +146,22 @@ class PlaceIndexInfo(C.Structure):
     _fields_ = [("params", PlaceParams), ("size", C.c_int), ("capacity", C.c_int), ("device_bytes", C.c_ulonglong)]
 
 
+class VoxelMapParams(C.Structure):
+    _fields_ = [("voxel_size", C.c_double), ("capacity", C.c_int), ("reserved", C.c_int * 5)]
+
+
+class VoxelMapInfo(C.Structure):
+    _fields_ = [("voxel_size", C.c_double), ("capacity", C.c_int), ("n_voxels", C.c_int), ("n_inserts", C.c_int),
+                ("n_members", C.c_longlong)]
+
+
+class VoxelMapInsertInfo(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("n_members", C.c_int), ("n_new_voxels", C.c_int), ("n_touched_voxels", C.c_int)]
+
+
 KF_VOX, KF_NORMALS, KF_FPFH, KF_MEAN = 1, 2, 3, 4
+VMAP_COORDS, VMAP_COUNT, VMAP_SUMS, VMAP_RECORDS, VMAP_CLOUD = 1, 2, 3, 4, 5
+VMAP_MAX_CAPACITY = 1 << 24
 PLACE_DESC, PLACE_COLNORM2 = 1, 2
 PLACE_MAX_K = 64
 SUBMAP_MAX_KEYFRAMES = 64
@@ -170,6 +185,12 @@ EXPORTS = [
     "qtr_default_eval_params", "qtr_evaluate", "qtr_evaluate_pair", "qtr_evaluate_keyframes",
     "qtr_evaluate_keyframes_batch",
     "qtr_default_pgo_params", "qtr_pgo_optimize",
+]
+# the C ABI of include/quatro_voxelmap.h: libquatro_voxelmap.so, a library of its own over the same handle
+VOXELMAP_EXPORTS = [
+    "qtr_default_voxel_map_params", "qtr_voxel_map_create", "qtr_voxel_map_destroy", "qtr_voxel_map_clear",
+    "qtr_voxel_map_get_info", "qtr_voxel_map_insert", "qtr_voxel_map_insert_keyframe", "qtr_voxel_map_register",
+    "qtr_voxel_map_register_keyframe", "qtr_voxel_map_fetch",
 ]
 
 _lib = None
@@ -378,6 +399,43 @@ def load(path: str | None = None):
     return lib
 
 
+VOXELMAP_LIB_PATH = os.environ.get("QTR_VOXELMAP_LIB") or os.path.join(_HERE, "libquatro_voxelmap.so")
+_vmap_lib = None
+
+
+def load_voxelmap():
+    """libquatro_voxelmap.so (include/quatro_voxelmap.h): the voxel map's entry points.  They take the handles of load()'s
+    library; both come from the same build (quatro_amd.build.build_voxelmap)."""
+    global _vmap_lib
+    if _vmap_lib is not None:
+        return _vmap_lib
+    load()  # (first: one HIP runtime per process)
+    if not os.path.exists(VOXELMAP_LIB_PATH):
+        raise FileNotFoundError(
+            f"{VOXELMAP_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
+            "(or __graft_entry__.build()) first.")
+    lib = C.CDLL(VOXELMAP_LIB_PATH)
+    lib.qtr_default_voxel_map_params.argtypes = [C.POINTER(VoxelMapParams)]
+    lib.qtr_default_voxel_map_params.restype = None
+    lib.qtr_voxel_map_create.argtypes = [C.c_void_p, C.POINTER(VoxelMapParams), C.POINTER(C.c_void_p)]
+    lib.qtr_voxel_map_destroy.restype = None
+    lib.qtr_voxel_map_destroy.argtypes = [C.c_void_p, C.c_void_p]
+    lib.qtr_voxel_map_clear.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    lib.qtr_voxel_map_get_info.argtypes = [C.c_void_p, C.POINTER(VoxelMapInfo)]
+    lib.qtr_voxel_map_insert.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                         C.POINTER(VoxelMapInsertInfo)]
+    lib.qtr_voxel_map_insert_keyframe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(VoxelMapInsertInfo)]
+    lib.qtr_voxel_map_register.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.POINTER(IcpParams), C.POINTER(IcpResult), C.c_int]
+    lib.qtr_voxel_map_register_keyframe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(IcpParams), C.POINTER(IcpResult)]
+    lib.qtr_voxel_map_fetch.restype = C.c_longlong
+    lib.qtr_voxel_map_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+    _vmap_lib = lib
+    return lib
+
+
 def comm_unique_id() -> bytes:
     """The rendezvous id rank 0 creates for qtr_comm_init (128 bytes)."""
     buf = C.create_string_buffer(128)
@@ -542,6 +600,111 @@ class Keyframe:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class VoxelMap:
+    """A persistent Gaussian voxel map on the device (qtr_voxel_map): made by Handle.voxel_map, freed by destroy() / the
+    context manager — or by the handle's close() at the latest.  Registrations only read it (any number of slots at once);
+    insert / insert_keyframe / clear are the caller's to serialise."""
+
+    def __init__(self, handle: "Handle", ptr: int):
+        self._handle, self._m, self._vlib = handle, C.c_void_p(ptr), load_voxelmap()
+
+    def info(self) -> dict:
+        info = VoxelMapInfo()
+        self._handle._check(self._vlib.qtr_voxel_map_get_info(self._m, C.byref(info)))
+        return {n: getattr(info, n) for n, _ in VoxelMapInfo._fields_}
+
+    def __len__(self) -> int:
+        return self.info()["n_voxels"]
+
+    @staticmethod
+    def _cloud(xyz4, normals4):
+        """(points pointer, normals pointer, n, mem) of numpy arrays (host) or torch tensors (all on the device)."""
+        if isinstance(xyz4, np.ndarray) or not hasattr(xyz4, "data_ptr"):
+            xyz4 = _f4(xyz4)
+            normals4 = None if normals4 is None else _f4(normals4)
+            assert normals4 is None or normals4.shape == xyz4.shape
+            return xyz4, normals4, xyz4.ctypes.data, None if normals4 is None else normals4.ctypes.data, MEM_HOST
+        (pp, m1), (pn, m2) = _ptr(xyz4), _ptr(normals4)
+        assert m1 == MEM_DEVICE and m2 in (None, MEM_DEVICE), "torch tensors must all be on the device"
+        assert xyz4.shape[-1] == 4 and (normals4 is None or normals4.shape == xyz4.shape)
+        return xyz4, normals4, pp, pn, MEM_DEVICE
+
+    @staticmethod
+    def _ins_dict(info: VoxelMapInsertInfo) -> dict:
+        return {n: getattr(info, n) for n, _ in VoxelMapInsertInfo._fields_}
+
+    def insert(self, xyz4, normals4, pose=None, slot: int = 0) -> dict:
+        """Folds the cloud's points under pose (4 x 4, cloud frame -> world; None = identity) into the map
+        (qtr_voxel_map_insert); returns n_points, n_members, n_new_voxels, n_touched_voxels."""
+        h = self._handle
+        keep_p, keep_n, pp, pn, mem = self._cloud(xyz4, normals4)
+        g, info = _guess16(pose), VoxelMapInsertInfo()
+        h._check(self._vlib.qtr_voxel_map_insert(h._h, slot, self._m, pp, pn, int(keep_p.shape[0]),
+                                             None if g is None else g.ctypes.data, mem, C.byref(info)))
+        return self._ins_dict(info)
+
+    def insert_keyframe(self, kf: Keyframe, pose=None, slot: int = 0) -> dict:
+        """insert of the keyframe's stored voxels and normals, read in place (qtr_voxel_map_insert_keyframe)."""
+        h = self._handle
+        g, info = _guess16(pose), VoxelMapInsertInfo()
+        h._check(self._vlib.qtr_voxel_map_insert_keyframe(h._h, slot, self._m, kf._kf, None if g is None else g.ctypes.data,
+                                                      C.byref(info)))
+        return self._ins_dict(info)
+
+    def register(self, src4, src_normals4, guess=None, params: IcpParams | None = None, slot: int = 0) -> dict:
+        """Voxelised plane-to-plane refinement of the scan against the map (qtr_voxel_map_register); params None = the
+        defaults with method = ICP_VOXEL_PLANE_TO_PLANE.  max_correspondence_distance is ignored: the side is the map's."""
+        h = self._handle
+        prm = params or default_icp_params(method=ICP_VOXEL_PLANE_TO_PLANE)
+        keep_p, keep_n, pp, pn, mem = self._cloud(src4, src_normals4)
+        g, res = _guess16(guess), IcpResult()
+        rc = self._vlib.qtr_voxel_map_register(h._h, slot, self._m, pp, int(keep_p.shape[0]), pn,
+                                           None if g is None else g.ctypes.data, C.byref(prm), C.byref(res), mem)
+        h._check(rc)
+        return _icp_dict(res)
+
+    def register_keyframe(self, kf: Keyframe, guess=None, params: IcpParams | None = None, slot: int = 0) -> dict:
+        """register of the keyframe's stored voxels and normals, read in place (qtr_voxel_map_register_keyframe)."""
+        h = self._handle
+        prm = params or default_icp_params(method=ICP_VOXEL_PLANE_TO_PLANE)
+        g, res = _guess16(guess), IcpResult()
+        rc = self._vlib.qtr_voxel_map_register_keyframe(h._h, slot, self._m, kf._kf, None if g is None else g.ctypes.data,
+                                                    C.byref(prm), C.byref(res))
+        h._check(rc)
+        return _icp_dict(res)
+
+    def fetch(self, what: int = VMAP_CLOUD) -> np.ndarray:
+        """In ascending key order: VMAP_COORDS -> int32 [n, 3], VMAP_COUNT -> int32 [n], VMAP_SUMS / VMAP_RECORDS ->
+        float64 [n, 9], VMAP_CLOUD -> float32 [n, 4] (the means, w = members)."""
+        h = self._handle
+        dtype, cols = {VMAP_COORDS: (np.int32, 3), VMAP_COUNT: (np.int32, 0), VMAP_SUMS: (np.float64, 9),
+                       VMAP_RECORDS: (np.float64, 9), VMAP_CLOUD: (np.float32, 4)}[what]
+        nbytes = self._vlib.qtr_voxel_map_fetch(h._h, self._m, what, None, 0)
+        if nbytes < 0:
+            raise QuatroHipError(-1, "qtr_voxel_map_fetch failed")
+        out = np.zeros(nbytes // np.dtype(dtype).itemsize, dtype=dtype)
+        if nbytes and self._vlib.qtr_voxel_map_fetch(h._h, self._m, what, out.ctypes.data, nbytes) < 0:
+            raise QuatroHipError(-1, "qtr_voxel_map_fetch failed")
+        return out.reshape(-1, cols) if cols else out
+
+    def clear(self, slot: int = 0) -> None:
+        """Empties the map; its voxel size and capacity stay (qtr_voxel_map_clear)."""
+        self._handle._check(self._vlib.qtr_voxel_map_clear(self._handle._h, slot, self._m))
+
+    def destroy(self):
+        if self._m and getattr(self._handle, "_h", None):
+            self._vlib.qtr_voxel_map_destroy(self._handle._h, self._m)
+        self._m = C.c_void_p()
+
+    close = destroy
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.destroy()
 
 
 class PlaceIndex:
@@ -1048,6 +1211,18 @@ class Handle:
         self._check(self._lib.qtr_place_index_create(self._h, None if params is None else C.byref(params), int(capacity),
                                                      C.byref(ix)))
         return PlaceIndex(self, ix.value)
+
+    def voxel_map(self, voxel_size: float = 1.0, capacity: int = 1 << 20) -> VoxelMap:
+        """A new, empty Gaussian voxel map of this handle (qtr_voxel_map_create): world-anchored voxels of side voxel_size,
+        room for `capacity` of them."""
+        if self._lib is not load():  # (another build of the library has other structures behind the handle)
+            raise QuatroHipError(QTR_ERR_BAD_ARG, "voxel maps belong to handles of the product library libquatro_hip.so")
+        vlib = load_voxelmap()
+        prm, out = VoxelMapParams(), C.c_void_p()
+        vlib.qtr_default_voxel_map_params(C.byref(prm))
+        prm.voxel_size, prm.capacity = float(voxel_size), int(capacity)
+        self._check(vlib.qtr_voxel_map_create(self._h, C.byref(prm), C.byref(out)))
+        return VoxelMap(self, out.value)
 
     def place_describe(self, xyz4, params: PlaceParams | None = None, slot: int = 0):
         """qtr_place_describe: the [num_rings, num_sectors] descriptor of a host cloud ([n, 4] float32 -> numpy) or of a
