@@ -198,11 +198,14 @@ def solve6(U21, b):
     return x, ok
 
 
-def precond(D, lam, r, free):
+def precond(D, lam, r, free, refusals=None):
+    """refusals (a list, optional) receives the number of free nodes whose block solve6 refused, once per call."""
     U = D.copy()
     for a in range(6):
         U[:, u(a, a)] = U[:, u(a, a)] + lam
     x, ok = solve6(U, r)
+    if refusals is not None:
+        refusals.append(int((~ok & free).sum()))
     z = np.where(ok[:, None], x, r)
     z[~free] = 0.0
     return z
@@ -256,13 +259,13 @@ def linearize(X, src, dst, Z, info, unc, mu, off, inc, free):
     return dict(A=A, w=w, D=D, g=ng, F=er.fold_sum(F.reshape(-1, 1))[0], max_diag=np.float64(md))
 
 
-def pcg(lin, lam, off, inc, src, dst, free, tol, max_its, rr_log=None):
+def pcg(lin, lam, off, inc, src, dst, free, tol, max_its, rr_log=None, refusals=None):
     """(x [N, 6], iterations) of (H + lambda I) x = -g by the header's loop."""
     N = free.size
     D, g, A = lin["D"], lin["g"], lin["A"]
     x = np.zeros((N, 6))
     r = np.where(free[:, None], -g, 0.0)
-    z = precond(D, lam, r, free)
+    z = precond(D, lam, r, free, refusals)
     p = z.copy()
     rz, rr = dot(r, z), dot(r, r)
     limit = (tol * tol) * rr
@@ -280,7 +283,7 @@ def pcg(lin, lam, off, inc, src, dst, free, tol, max_its, rr_log=None):
             rr_log.append(rr)
         if not rr > limit:
             break
-        z = precond(D, lam, r, free)
+        z = precond(D, lam, r, free, refusals)
         rzn = dot(r, z)
         beta = rzn / rz
         rz = rzn
@@ -288,9 +291,11 @@ def pcg(lin, lam, off, inc, src, dst, free, tol, max_its, rr_log=None):
     return x, its
 
 
-def optimize(poses, fixed, src, dst, Z, info, unc, rr_log=None, **params):
+def optimize(poses, fixed, src, dst, Z, info, unc, rr_log=None, refusals=None, **params):
     """The whole call.  poses [N, 16] or [N, 4, 4]; fixed None = node 0.  Returns a dict: poses [N, 16], weights [E], trace
-    [1 + iterations, 8] and the fields of qtr_pgo_result."""
+    [1 + iterations, 8] and the fields of qtr_pgo_result.  rr_log (a list) receives <r, r> before and after every iteration
+    of the first solve; refusals (a list) one count per preconditioner application of every solve: the free nodes whose
+    block solve6 refused (z_i = r_i)."""
     P = dict(DEFAULTS, **params)
     f64 = np.float64
     X0 = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 16))
@@ -324,7 +329,7 @@ def optimize(poses, fixed, src, dst, Z, info, unc, rr_log=None, **params):
         first = True
         while not reason:
             x, its = pcg(cur, lam, off, inc, src, dst, free, f64(P["pcg_tol"]), P["pcg_max_iterations"],
-                         rr_log if first else None)
+                         rr_log if first else None, refusals)
             first = False
             uvec = np.where(free[:, None], lam * x - cur["g"], 0.0)
             ms = f64(np.fmax.reduce(np.abs(x).reshape(-1), initial=0.0))
