@@ -146,7 +146,11 @@ typedef struct qtr_result {
   int n_corr;        /* correspondences handed to the solver */
 } qtr_result;
 
-/* Per-stage GPU time of the last call on a slot, milliseconds (hipEvent based). */
+/* Per-stage GPU time of the last call on a slot, milliseconds (hipEvent based).  qtr_register_pair_corr runs its back end
+ * BESIDE its front end (on a stream of its own): there graph is measured from the back end's start on that stream, clique
+ * and solve on that stream, total from the call's first event to the point where the two streams have joined — so the
+ * stage times of that entry point add up to MORE than total (under QTR_CORR_OVERLAP=0 graph starts at the matcher's end
+ * and they add up to it, as elsewhere). */
 typedef struct qtr_stage_times {
   float voxelize, fpfh, match, graph, clique, solve, total;
   float nn_kernel;  /* sum of the nearest-neighbour kernel launches of the last match (events on the launch stream) */
@@ -286,9 +290,14 @@ QTR_API int qtr_register_pair(qtr_handle* h, int slot, const float* src_raw4, in
  * FPFHManager::loadFeaturePair, include/fpfh_manager.hpp:211-232; another matcher) while the scans still go through the
  * front end — the single-pair form of a qtr_pair_desc with both scans and src_corr4 / tgt_corr4 set (see
  * qtr_submit_batch), and the unit of work BASELINE's metric is quoted on: a KITTI-64 pair's voxel grid + FPFH + matching
- * AND a ~5 k-correspondence computeTransformation, as ONE call (the back end is enqueued as soon as the matcher's counters
- * arrive; it starts after the front end like in qtr_register_pair — nothing overlaps that a registration would
- * serialise).  res->n_src / n_tgt report the voxel counts, res->n_corr = n_corr; n_matched (optional) receives the
+ * AND a ~5 k-correspondence computeTransformation, as ONE call.  The back end reads the caller's correspondences alone,
+ * so it is enqueued on a stream of its own as soon as the voxel grid is on its way and runs BESIDE the front end; the
+ * call returns when both are done (a front end that fails returns its status and counts, after the back end has let go
+ * of the correspondences).  The back end is still ordered behind whatever the slot's stream (qtr_slot_stream) held when
+ * the call was made: device correspondences written there — the device outputs of an earlier call, a caller's own
+ * matcher — need not be complete, only enqueued.  QTR_CORR_OVERLAP=0 in the environment at qtr_create keeps the serial order — the back end
+ * enqueued when the matcher's counters arrive, behind the front end as in qtr_register_pair; results are the same bit for
+ * bit.  res->n_src / n_tgt report the voxel counts, res->n_corr = n_corr; n_matched (optional) receives the
  * matcher's own correspondence count.  corr_*4: n_corr 16-byte records each, same `mem` as the scans. */
 QTR_API int qtr_register_pair_corr(qtr_handle* h, int slot, const float* src_raw4, int Ps, const float* tgt_raw4, int Pt,
                                    const qtr_frontend_params* fp, const float* corr_src4, const float* corr_tgt4, int n_corr,

@@ -23,6 +23,13 @@ struct Slot {
   hipStream_t stream2 = nullptr;  // second cloud's front end runs concurrently
   hipEvent_t ev[8] = {};
   hipEvent_t ev_vox = nullptr;    // voxel centroids complete (stream) -> Matcher means may start (stream2)
+  // qtr_register_pair_corr: the back end of the caller's correspondences runs BESIDE the front end, on a third stream
+  // (created on the slot's first such call: ensure_stream3)
+  hipStream_t stream3 = nullptr;
+  hipEvent_t ev_be0 = nullptr;    // the back end's start on stream3 (stage times)
+  hipEvent_t ev_end = nullptr;    // the call's end on `stream`, behind the join (stage times)
+  hipEvent_t ev_fork = nullptr;   // stream -> stream3 at the call's start: what the slot's stream held before it (no timing)
+  hipEvent_t ev_join = nullptr;   // stream3 -> stream (no timing)
   void* solver_arena = nullptr;
   void* front_arena = nullptr;
   SolverBufs sb;
@@ -44,7 +51,8 @@ struct Slot {
   int seq = 0;                   // last sequence number handed to a phase-ending kernel
   unsigned long long exact_nodes = 0;  // search-tree nodes of the last PMC_EXACT run
   int exact_aborted = 0;               // 1: its time limit was hit (heuristic clique returned)
-  int times_pending = 0;         // 1: qtr_solve, 2: qtr_register_pair, 5: qtr_register_keyframes — stage times are read off the events lazily
+  int times_pending = 0;         // 1: qtr_solve, 2: qtr_register_pair, 5: qtr_register_keyframes, 6: qtr_register_pair_corr with the
+                                 // back end beside the front end — stage times are read off the events lazily
   int nn_pending = 0;            // the nearest-neighbour events of the last match have not been added to the totals yet
   int nn_timed_last = 0;         // the last match had its event pairs attached (qtr_set_nn_event_stride)
   long long n_matches = 0;       // matches this slot has run
@@ -156,6 +164,7 @@ struct qtr_handle {
   std::atomic<int> gen_inflight[4] = {};  // chains in flight per generation of the share (gen & 3)
   unsigned long long uid = 0;     // process-unique id of this handle (a thread remembers the handle it registered with)
   int stage_events = 1;  // QTR_STAGE_EVENTS=0: only the first/last event of a call are recorded (stage times read 0)
+  int corr_overlap = 1;  // QTR_CORR_OVERLAP=0: qtr_register_pair_corr runs its back end BEHIND the front end, as before
   int nn_event_stride = 1;  // every n-th match of a slot carries the nearest-neighbour event pairs (0: none)
   int icp_block = 0;  // QTR_ICP_BLOCK=n: ICP launches enqueued between two read-backs of the stop flag (0: all at once)
   std::mutex kf_mu;                    // guards `keyframes` (qtr_keyframe_create / _destroy from several threads)
@@ -435,9 +444,12 @@ void qtr_destroy(qtr_handle* h) {
   for (auto& s : h->slots) {
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.stream2) (void)hipStreamSynchronize(s.stream2);
+    if (s.stream3) (void)hipStreamSynchronize(s.stream3);
     for (auto& e : s.ev)
       if (e) (void)hipEventDestroy(e);
     if (s.ev_vox) (void)hipEventDestroy(s.ev_vox);
+    for (hipEvent_t e : {s.ev_be0, s.ev_end, s.ev_fork, s.ev_join})
+      if (e) (void)hipEventDestroy(e);
     for (auto& e : s.fb.ev_nn)
       if (e) (void)hipEventDestroy(e);
     if (s.solver_arena) (void)hipFree(s.solver_arena);
@@ -465,6 +477,7 @@ void qtr_destroy(qtr_handle* h) {
     if (s.merge_dev) (void)hipFree(s.merge_dev);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.stream2) (void)hipStreamDestroy(s.stream2);
+    if (s.stream3) (void)hipStreamDestroy(s.stream3);
   }
   delete h;
 }
@@ -574,6 +587,8 @@ int qtr_create(int device, const qtr_limits* limits, qtr_handle** out) {
     const char* se = getenv("QTR_STAGE_EVENTS");
     h->stage_events = (se && atoi(se) == 0) ? 0 : 1;
     h->nn_event_stride = h->stage_events ? 1 : 0;
+    const char* co = getenv("QTR_CORR_OVERLAP");
+    h->corr_overlap = (co && atoi(co) == 0) ? 0 : 1;
     const char* ib = getenv("QTR_ICP_BLOCK");
     h->icp_block = ib ? std::max(0, atoi(ib)) : 0;
   }
@@ -714,6 +729,21 @@ static void compute_times(Slot& s) {
     if (hipEventElapsedTime(&ms, s.ev[1], s.ev[6]) == hipSuccess) s.times.fpfh = ms;
     if (hipEventElapsedTime(&ms, s.ev[6], s.ev[7]) == hipSuccess) s.times.match = ms;
     if (hipEventElapsedTime(&ms, s.ev[0], s.ev[7]) == hipSuccess) s.times.total = ms;
+    fill_nn_times(s);
+    (void)hipGetLastError();
+    s.times_pending = 0;
+    return;
+  }
+  if (s.times_pending == 6) {  // qtr_register_pair_corr, back end beside the front end: graph / clique / solve were measured on
+    (void)hipEventSynchronize(s.ev_end);  // the third stream WHILE voxelize / fpfh / match ran: they add up to more than total
+    s.times = qtr_stage_times{};
+    if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.times.voxelize = ms;
+    if (hipEventElapsedTime(&ms, s.ev[1], s.ev[6]) == hipSuccess) s.times.fpfh = ms;
+    if (hipEventElapsedTime(&ms, s.ev[6], s.ev[7]) == hipSuccess) s.times.match = ms;
+    if (hipEventElapsedTime(&ms, s.ev_be0, s.ev[2]) == hipSuccess) s.times.graph = ms;
+    if (hipEventElapsedTime(&ms, s.ev[2], s.ev[3]) == hipSuccess) s.times.clique = ms;
+    if (hipEventElapsedTime(&ms, s.ev[3], s.ev[4]) == hipSuccess) s.times.solve = ms;
+    if (hipEventElapsedTime(&ms, s.ev[0], s.ev_end) == hipSuccess) s.times.total = ms;
     fill_nn_times(s);
     (void)hipGetLastError();
     s.times_pending = 0;
@@ -990,8 +1020,10 @@ static void result_from_mail(const Slot& s, qtr_result* res) {
 }
 
 // The caller's n correspondences where the back end reads them: device pointers as they are, host clouds copied into the
-// slot's matched-cloud buffers on `st` (the lanes: lead.stream).  Whoever runs a front end on the slot stages BEHIND it:
-// its matcher writes m_src / m_tgt.
+// slot's matched-cloud buffers on `st` (the lanes: lead.stream).  A matcher that runs on the slot gathers its own matched
+// clouds into m_src / m_tgt (the fused tails of match.hip, through FrontBufs::m_src), so whoever stages on the stream of a
+// front end stages BEHIND it; qtr_register_pair_corr stages BESIDE its front end, on the third stream, and takes the
+// buffers away from that front end's matcher for the call (front_device, CorrEarly: nobody reads its gathered clouds).
 static int corr_stage(qtr_handle* h, Slot& s, const float* src4, const float* tgt4, int n, int mem, hipStream_t st,
                       const float4** cs, const float4** ct) {
   *cs = (const float4*)src4;
@@ -1670,8 +1702,9 @@ int qtr_fpfh(qtr_handle* h, int slot, const float* xyz4, int n, float r_normal, 
 }
 
 // Matching on device-resident clouds/descriptors held in fb.cloud[0] (source) and fb.cloud[1] (target).
+// gather: the fused tail also leaves the matched clouds in s.m_src / s.m_tgt (match.hip, match_enqueue)
 static int match_device(qtr_handle* h, Slot& s, int ns, int nt, const qtr_frontend_params* fp, int* L_out,
-                        bool init_done = false, bool prep_done = false, bool tolerate_tail = false) {
+                        bool init_done = false, bool prep_done = false, bool tolerate_tail = false, bool gather = true) {
   flush_nn_totals(s);
   // (an event pair attached to a launch costs ~5 us of queue time on either side of it: a caller that only wants the
   // average duration of the launches — the bench's roofline — has every n-th match timed, qtr_set_nn_event_stride)
@@ -1680,7 +1713,7 @@ static int match_device(qtr_handle* h, Slot& s, int ns, int nt, const qtr_fronte
   s.nn_timed_last = (s.fb.nn_events && s.fb.nn_engine != 0) ? 1 : 0;
   s.nn_pending = s.nn_timed_last;
   s.fb.mail_seq = ++s.seq;
-  QTR_HIP_TRY(h, match_enqueue(s.fb, ns, nt, *fp, s.stream, init_done, prep_done));
+  QTR_HIP_TRY(h, match_enqueue(s.fb, ns, nt, *fp, s.stream, init_done, prep_done, gather));
   QTR_TRY(wait_mail(h, s, MAIL_SEQ_MATCH, s.seq));  // k_corr_compact2 left the counters in the mailbox
   *L_out = s.mail[MAIL_MATCH + MC_NCORR];
   if (*L_out < 0) {  // a multi-workgroup compaction of the tail gave up waiting for a predecessor's count (match.hip)
@@ -1735,6 +1768,57 @@ int qtr_match(qtr_handle* h, int slot, const float* xyz4_s, int n_s, const float
   return QTR_OK;
 }
 
+// The slot's third stream and its events, on the slot's first qtr_register_pair_corr (not in every slot of a batch handle).
+// The front end is the critical path and the second stream already has the highest priority: this one takes the LOWEST
+// (a queue pool of its own, and the front end's workgroups go first wherever both wait for a unit).
+static int ensure_stream3(qtr_handle* h, Slot& s) {
+  if (s.stream3) return QTR_OK;
+  int prio_least = 0, prio_greatest = 0;
+  QTR_HIP_TRY(h, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+  if (!s.ev_be0) QTR_HIP_TRY(h, hipEventCreate(&s.ev_be0));
+  if (!s.ev_end) QTR_HIP_TRY(h, hipEventCreate(&s.ev_end));
+  if (!s.ev_fork) QTR_HIP_TRY(h, hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming));
+  if (!s.ev_join) QTR_HIP_TRY(h, hipEventCreateWithFlags(&s.ev_join, hipEventDisableTiming));
+  if (prio_greatest != prio_least) QTR_HIP_TRY(h, hipStreamCreateWithPriority(&s.stream3, hipStreamNonBlocking, prio_least));
+  else QTR_HIP_TRY(h, hipStreamCreateWithFlags(&s.stream3, hipStreamNonBlocking));
+  return QTR_OK;
+}
+
+// qtr_register_pair_corr's back end, enqueued by front_device right behind the voxel stage's launches: it reads the
+// caller's correspondences alone, so it runs on the third stream while the front end runs on the other two.
+struct CorrEarly {
+  const float* src = nullptr;  // the caller's correspondences (mem: where they live)
+  const float* tgt = nullptr;
+  int n = 0, mem = QTR_MEM_HOST;
+  const qtr_params* prm = nullptr;
+  bool enqueued = false;       // once per call: not again when the voxel sort or the long-list verdict goes round
+  int seq = 0;                 // the sequence number its k_finalize publishes (the front end advances s.seq afterwards)
+  const float4 *cs = nullptr, *ct = nullptr;  // where the back end reads them
+  std::unique_ptr<InFlight> in_flight;        // held until its mail is in (or the chain has drained)
+};
+static int corr_early_enqueue(qtr_handle* h, Slot& s, CorrEarly& ce) {
+  ce.enqueued = true;
+  const bool ev_on = h->stage_events != 0;
+  // The back end used to run on s.stream, behind everything the slot's stream already held: the device outputs of an earlier
+  // call on the slot (qtr_feature_pair's keypoints, still being copied out of m_src / m_tgt), a caller's own matcher that
+  // writes the correspondences on qtr_slot_stream.  It still does: the third stream waits for the event front_device
+  // recorded on s.stream at the call's start — earlier work on the slot, not this call's voxel stage.
+  QTR_HIP_TRY(h, hipStreamWaitEvent(s.stream3, s.ev_fork, 0));
+  if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev_be0, s.stream3));
+  QTR_TRY(corr_stage(h, s, ce.src, ce.tgt, ce.n, ce.mem, s.stream3, &ce.cs, &ce.ct));
+  // (the slot's record of its last solve follows the solver's buffers, which this chain fills even when the front end
+  // then fails and the call returns counts and status only; the serial order leaves it untouched on such a failure)
+  s.last_L = ce.n;
+  s.last_Wb = (((ce.n + 63) / 64) + 3) & ~3;
+  s.sb.mail_seq = ce.seq = ++s.seq;
+  ce.in_flight.reset(new InFlight(h));
+  // (the state's clean slate rides on the graph build, as in qtr_solve: the matcher's k_match_init leaves it alone)
+  QTR_HIP_TRY(h, solver_enqueue(s.sb, ce.cs, ce.ct, ce.n, *ce.prm, s.stream3, s.pinned_i32, ev_on ? s.ev[2] : nullptr,
+                                ev_on ? s.ev[3] : nullptr, false, true));
+  if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev[4], s.stream3));
+  return QTR_OK;
+}
+
 // Front end of one pair on one slot: voxel grid x2 -> FPFH x2 -> reciprocal matching -> matched keypoint clouds gathered
 // into s.m_src / s.m_tgt (device).  What the reference does in `voxelize` x2 (include/quatro.hpp:49-68) +
 // FPFHManager::setFeaturePair (include/fpfh_manager.hpp:98-153).  Counts go to *ns_out / *nt_out / *L_out; with
@@ -1742,10 +1826,13 @@ int qtr_match(qtr_handle* h, int slot, const float* xyz4_s, int n_s, const float
 // nothing in flight that still reads the caller's scans.
 static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, const float* tgt_raw4, int Pt,
                         const qtr_frontend_params* fp, int mem, bool for_solver, int* ns_out, int* nt_out, int* L_out,
-                        bool corr_given = false) {
+                        bool corr_given = false, CorrEarly* early = nullptr) {
   // corr_given: the back end will run on the CALLER's correspondences — the matcher's list is only counted (*L_out; -1 when
   // its tail gave up), so neither a list longer than max_corr nor a tail failure fails the registration, and the matched
   // clouds are not gathered.
+  // early (with corr_given, for_solver = false): that back end is enqueued HERE, on the third stream, behind the first voxel
+  // stage's launches — after every check that returns with nothing in flight, and while the host would only wait for the
+  // voxel mail.  The caller waits for its mail, joins the streams and drains the third one on an error return.
   int rc = QTR_OK;
   if (fp->normal_radius > fp->fpfh_radius) {
     snprintf(h->err, sizeof(h->err), "[FPFHManager]: Normal should be lower than fpfh_radius!!!!");
@@ -1760,6 +1847,10 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
     return QTR_ERR_CAPACITY;
   }
   QTR_HIP_TRY(h, hipSetDevice(h->device));
+  if (early && !early->enqueued) {  // the fork of the third stream: in front of everything this call puts on s.stream
+    QTR_TRY(ensure_stream3(h, s));
+    QTR_HIP_TRY(h, hipEventRecord(s.ev_fork, s.stream));
+  }
   const float4 *d_s = (const float4*)src_raw4, *d_t = (const float4*)tgt_raw4;
   if (mem == QTR_MEM_HOST) {
     QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, src_raw4, (size_t)Ps * 16, hipMemcpyHostToDevice, s.stream));
@@ -1781,7 +1872,7 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
     const int Ps2[2] = {Ps, Pt};
     for (int attempt = 0;; ++attempt) {  // (the voxel sort's radix passes are speculated: vox_passes_next)
       const int launched = s.fb.vox_passes;
-      s.fb.mail_seq = ++s.seq;
+      const int vox_seq = s.fb.mail_seq = ++s.seq;  // (kept: the back end enqueued below takes the next number)
       QTR_HIP_TRY(h, voxelize_enqueue(s.fb, 2, raws, Ps2, fp->voxel_size, s.stream, launched, fp->fpfh_radius * 1.001f));
       // block 0 of k2_vox_centroids publishes the counters while other blocks are still writing centroids: anything
       // that reads the centroids from another stream has to wait for the kernel itself
@@ -1794,8 +1885,9 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
         QTR_HIP_TRY(h, hipStreamWaitEvent(s.stream2, s.ev_vox, 0));
         QTR_HIP_TRY(h, mean_enqueue(s.fb, 0, 2, on_device, s.stream2, h->lim.max_voxels));
       }
+      if (early && !early->enqueued) QTR_TRY(corr_early_enqueue(h, s, *early));
       // k2_vox_centroids leaves both clouds' counters in the mailbox
-      if ((rc = wait_mail(h, s, MAIL_SEQ_VOX0, s.seq)) != QTR_OK || (rc = wait_mail(h, s, MAIL_SEQ_VOX1, s.seq)) != QTR_OK)
+      if ((rc = wait_mail(h, s, MAIL_SEQ_VOX0, vox_seq)) != QTR_OK || (rc = wait_mail(h, s, MAIL_SEQ_VOX1, vox_seq)) != QTR_OK)
         return fail_drained(rc);
       const int bits = std::max(s.mail[MAIL_VOX0 + CNT_SORT_BITS], s.mail[MAIL_VOX1 + CNT_SORT_BITS]);
       if (!vox_passes_next(s.fb.vox_passes, s.fb.vox_fewer, bits, launched, attempt)) break;
@@ -1849,7 +1941,9 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
   }
   if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[6], s.stream));
   int L = 0;
-  rc = match_device(h, s, ns, nt, fp, &L, true, true, corr_given);
+  // (with the back end beside this chain the matcher's tail does not gather its matched clouds: nobody reads them, and
+  // host correspondences are staged in m_src / m_tgt while it runs)
+  rc = match_device(h, s, ns, nt, fp, &L, true, true, corr_given, early == nullptr);
   if (rc != QTR_OK) return rc;
   switch (lists_verdict(s.mail + MAIL_CNT0, s.mail + MAIL_CNT1, h->long_lists)) {  // (the matcher's tail mails the lines)
     case LISTS_TILE_ERROR:
@@ -1862,11 +1956,14 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
       return QTR_ERR_CAPACITY;
     case LISTS_NEED_LONG:  // from now on the handle's chains include k2_neighbors_big; this pair goes round again
       h->long_lists = true;
-      return front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem, for_solver, ns_out, nt_out, L_out, corr_given);
+      return front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem, for_solver, ns_out, nt_out, L_out, corr_given, early);
     case LISTS_OK: break;
   }
   *L_out = L;
-  if (corr_given) return QTR_OK;
+  if (corr_given) {
+    if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[7], s.stream));  // (stage times: the matcher's end)
+    return QTR_OK;
+  }
   s.last_L = L;
   QTR_TRY(check_max_corr(h, L));
   QTR_HIP_TRY(h, gather_matched_enqueue(s.fb, L, s.m_src, s.m_tgt, s.stream));
@@ -1883,15 +1980,71 @@ static void mark_registration(Slot& s, int rc, const qtr_result* res) {
 
 // The whole path on one slot.  mem_in: where the scans live; mem_out: where the index lists go and where the caller's
 // correspondences are.  corr_src / corr_tgt (n_corr >= 0): the back end runs on THESE matched clouds instead of the
-// matcher's output (qtr_register_pair_corr, the batched entry's "scans + pre-matched correspondences" pairs), staged behind
-// the front end, and the record's n_corr is n_corr whatever happens; *n_matched (may be null) then receives the matcher's
-// count (-1: its tail gave up — its list is not used).  n_corr < 0: the matcher's own correspondences.
+// matcher's output (qtr_register_pair_corr, the batched entry's "scans + pre-matched correspondences" pairs), and the
+// record's n_corr is n_corr whatever happens; *n_matched (may be null) then receives the matcher's count (-1: its tail gave
+// up — its list is not used).  n_corr < 0: the matcher's own correspondences.
+// That back end needs nothing of the front end, so it is enqueued on the slot's third stream as soon as the voxel stage
+// is on its way (front_device, CorrEarly) and the two chains share the device; the streams are joined before anything on
+// s.stream reads the solver's buffers, and before every return.  QTR_CORR_OVERLAP=0 (read at qtr_create) keeps the serial
+// order: staged and enqueued behind the front end, on s.stream.
 static int register_pair_impl(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, const float* tgt_raw4, int Pt,
                               const qtr_frontend_params* fp, const qtr_params* prm, qtr_result* res, int* clique,
                               int* final_inliers, int cap, int mem_in, int mem_out, const float* corr_src,
                               const float* corr_tgt, int n_corr, int* n_matched = nullptr) {
   const bool given = n_corr >= 0;
   int L = 0;
+  if (given && h->corr_overlap) {
+    CorrEarly ce;
+    ce.src = corr_src;
+    ce.tgt = corr_tgt;
+    ce.n = n_corr;
+    ce.mem = mem_out;
+    ce.prm = prm;
+    int rc = front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem_in, false, &res->n_src, &res->n_tgt, &L, true, &ce);
+    if (n_matched) *n_matched = L;
+    res->n_corr = n_corr;
+    if (!ce.enqueued) return res->status = rc;  // (a check in front of the first launch: nothing is in flight)
+    // every return from here on leaves the third stream drained: the caller may free or overwrite the correspondences,
+    // and nothing else on the slot waits for that stream (the successful return has synchronised s.stream behind the join)
+    struct DrainOnReturn {
+      hipStream_t st;
+      bool armed = true;
+      ~DrainOnReturn() {
+        if (armed) (void)hipStreamSynchronize(st);
+      }
+    } drain{s.stream3};
+    // from here on the third stream's work is waited for and watched there (wait_mail's liveness check, exact_phase)
+    struct StreamSwap {
+      Slot& s;
+      hipStream_t keep;
+      StreamSwap(Slot& s_, hipStream_t st) : s(s_), keep(s_.stream) { s.stream = st; }
+      ~StreamSwap() { s.stream = keep; }
+    };
+    if (rc == QTR_OK) {
+      StreamSwap on_stream3(s, s.stream3);
+      rc = wait_mail(h, s, MAIL_SEQ_SOLVE, ce.seq);
+      if (rc == QTR_OK) rc = solve_followup(h, s, ce.cs, ce.ct, n_corr, prm, s.stream3, h->stage_events != 0);
+    }
+    if (rc != QTR_OK) {
+      // The front end failed behind the back end's enqueue (capacity, a look-back timeout, the long-list arena), or a wait
+      // did: today's record — counts and status — and nothing of the solver.  The abandoned chain drains before the
+      // caller gets its correspondences back (drain), and its mail carries a sequence number no later call waits for.
+      return res->status = rc;
+    }
+    ce.in_flight.reset();
+    result_from_mail(s, res);
+    rc = res->status;
+    // the next call on the slot, qtr_refine_pair and device outputs are ordered on s.stream: it sees the finished back end
+    QTR_HIP_TRY(h, hipEventRecord(s.ev_join, s.stream3));
+    QTR_HIP_TRY(h, hipStreamWaitEvent(s.stream, s.ev_join, 0));
+    if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev_end, s.stream));
+    if (rc != QTR_OK && rc != QTR_ERR_CLIQUE_TOO_SMALL) return rc;
+    s.times_pending = h->stage_events ? 6 : 4;
+    const int rc2 = copy_out_lists(h, s, res, clique, nullptr, final_inliers, cap, mem_out);
+    if (rc2 != QTR_OK) return res->status = rc2;
+    drain.armed = false;  // (copy_out_lists synchronised s.stream, which waited for the join)
+    return rc;
+  }
   int rc = front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem_in, true, &res->n_src, &res->n_tgt, &L, given);
   if (n_matched) *n_matched = L;
   res->n_corr = given ? n_corr : L;

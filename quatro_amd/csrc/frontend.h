@@ -248,8 +248,9 @@ hipError_t mean_enqueue(FrontBufs& F, int first, int nc, const int* n, hipStream
 // FPFH chain, which takes one launch off the critical path
 // prep_done: the clouds' k2_fpfh did k_desc_prep's work (fpfh_enqueue* with desc_prep) — then the init may not clear the
 // duplicate tables (k2_normals did, before they were filled)
+// gather = false: the fused tail writes the correspondence list alone, not the matched clouds into F.m_src / F.m_tgt
 hipError_t match_enqueue(FrontBufs& F, int ns, int nt, const qtr_frontend_params& fp, hipStream_t st, bool init_done = false,
-                         bool prep_done = false);
+                         bool prep_done = false, bool gather = true);
 hipError_t match_init_enqueue(FrontBufs& F, int ns, int nt, const qtr_frontend_params& fp, hipStream_t st,
                               bool clear_tables, int* zero_words = nullptr, int n_zero = 0);  // zero_words: n_zero ints the launch clears for the caller
 hipError_t gather_matched_enqueue(FrontBufs& F, int L, float4* m_src, float4* m_tgt, hipStream_t st);

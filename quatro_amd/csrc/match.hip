@@ -2706,11 +2706,12 @@ hipError_t match_init_enqueue(FrontBufs& F, int ns, int nt, const qtr_frontend_p
   return hipGetLastError();
 }
 hipError_t match_enqueue(FrontBufs& F, int ns, int nt, const qtr_frontend_params& fp, hipStream_t st, bool init_done,
-                         bool prep_done) {
+                         bool prep_done, bool gather) {
   (void)hipGetLastError();
-  const MatchView V = make_match_view(F, ns, nt, fp, (unsigned long long)fp.seed);
+  MatchView V = make_match_view(F, ns, nt, fp, (unsigned long long)fp.seed);
+  if (!gather) V.m_src = V.m_tgt = nullptr;  // the list alone: F.m_src / F.m_tgt are somebody else's for this chain
   const bool fused_tail = tail_is_fused(V.crosscheck != 0, V.n_large, ns);
-  F.gathered = fused_tail && F.m_src != nullptr;
+  F.gathered = fused_tail && V.m_src != nullptr;
   const bool evs = F.nn_events != 0;
   return match_launch(&V, 1, F.nn_engine, F.n_cu, nullptr, st, evs ? F.ev_nn : nullptr, init_done, prep_done);
 }

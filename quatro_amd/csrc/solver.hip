@@ -3799,6 +3799,12 @@ __global__ __launch_bounds__(FIN_THREADS) void k_finalize(ViewExt<SolverView> x,
 // inside a launch at most ONE pair per launch is partly resident at any time, so share x nwg <= compute units means some
 // pair is always complete and makes progress.  (If the promise is broken — another process on the device — the kernel's
 // own residency timeout sends the pair to the peeling workgroup: slower, never wrong.)
+// k_hcore_async beside another chain of the same call (clique_stage_launch, shares_device): its share of the compute units,
+// its LDS budget, and the largest graph that takes the shape
+#define HCA_SHARED_WGS_NUM 1
+#define HCA_SHARED_WGS_DEN 4
+#define HCA_SHARED_LDS_KB 88
+#define HCA_SHARED_MAX_L 8192
 static thread_local int t_hca_share = 1;
 void solver_set_hca_share(int share) { t_hca_share = share < 1 ? 1 : share; }
 
@@ -3975,8 +3981,11 @@ static bool hcore_async_planned(int L) { return hcore_planned(L) && !kcore_sweep
 // argument (0: nothing left to replay)
 // exact_cores: k_hcore_async without its floor (the second run of a pair whose first came back empty; the k-core
 // heuristic, which reads every core number)
+// shares_device: another launch chain of the SAME call runs beside this one (qtr_register_pair_corr's front end):
+// k_hcore_async takes the shape that leaves room for it, see below
 static int clique_stage_launch(const SolverArgs& a, int G, int L, int mode, double kcore_thr, hipStream_t stream,
-                               bool hcore_prepared, bool defer_last_scan, bool exact_cores = false) {
+                               bool hcore_prepared, bool defer_last_scan, bool exact_cores = false,
+                               bool shares_device = false) {
   int deferred = 0;
   const int W = (L + 63) / 64;
   static const bool dbg_sync = QTR_ENGINE_ENV("QTR_DEBUG_SYNC") != nullptr;  // name every kernel as it completes
@@ -4011,6 +4020,23 @@ static int clique_stage_launch(const SolverArgs& a, int G, int L, int mode, doub
         // one resident workgroup per compute unit at most (they wait for one another); a group of pairs shares the device
         int nwg = min(min(hca_max_workgroups(), HCA_MAXWG), max(1, (L + 15) / 16));
         nwg = max(1, min(nwg, hca_max_workgroups() / t_hca_share));
+        // Beside a front end (one pair, L up to HCA_SHARED_MAX_L): one workgroup on EVERY unit with the unit's whole LDS
+        // would keep each front-end kernel that needs LDS off the device while it runs, and front-end workgroups that are
+        // resident already can keep part of this launch out until the residency verdict sends it to the peeling
+        // workgroup.  The group path's answer, fewer and larger workgroups with a smaller pool, serves here too: at most
+        // HCA_SHARED_WGS_NUM / HCA_SHARED_WGS_DEN of the units (times the callers' share) and HCA_SHARED_LDS_KB of LDS.
+        // (Sweep on the headline step: profiles/corr_overlap_ab.txt.  Core numbers, floors and results do not depend on
+        // the shape.)
+        static const int shared_max_l = [] {  // (QTR_HCA_SHARED_MAX_L: the test build's measurement of the threshold)
+          const char* e = QTR_ENGINE_ENV("QTR_HCA_SHARED_MAX_L");
+          return e ? atoi(e) : HCA_SHARED_MAX_L;
+        }();
+        const bool shared_shape = shares_device && G == 1 && L <= shared_max_l;
+        if (shared_shape) {
+          int cap = hca_max_workgroups() * HCA_SHARED_WGS_NUM / (HCA_SHARED_WGS_DEN * t_hca_share);
+          if (const char* e = QTR_ENGINE_ENV("QTR_HCA_SHARED_WGS")) cap = atoi(e) / t_hca_share;
+          nwg = max(1, min(nwg, max(1, cap)));
+        }
         static const bool no_floor = [] {  // (QTR_HCORE_FLOOR=0: comparison runs of the test build)
           const char* e = QTR_ENGINE_ENV("QTR_HCORE_FLOOR");
           return e && atoi(e) == 0;
@@ -4055,6 +4081,11 @@ static int clique_stage_launch(const SolverArgs& a, int G, int L, int mode, doub
           lds_budget = (size_t)88 * 1024;
           if (const char* e = QTR_ENGINE_ENV("QTR_HCA_GROUP_LDS_KB")) lds_budget = (size_t)max(32, atoi(e)) * 1024;
           lds_budget = max(lds_budget, fixed + 4096);
+        }
+        if (shared_shape) {
+          lds_budget = (size_t)HCA_SHARED_LDS_KB * 1024;
+          if (const char* e = QTR_ENGINE_ENV("QTR_HCA_SHARED_LDS_KB")) lds_budget = (size_t)min(150, max(32, atoi(e))) * 1024;
+          lds_budget = min((size_t)150 * 1024, max(lds_budget, fixed + 4096));
         }
         const int pool_entries = (int)((lds_budget - fixed) / 2) & ~7;
         if (!hcore_prepared) LAUNCH_SV(k_hcore_async_init, a, dim3((max(L, 4096) + 255) / 256, 1, G), dim3(256), 0, stream);
@@ -4254,7 +4285,8 @@ static hipError_t ensure_range_table(const SolverBufs& B, const qtr_params& prm)
 // The whole back end of the G pairs of `views` on `stream` (L known on the host).  The clique heuristic normally
 // terminates after the first two batches (see k_clique_batch); the host checks `done` with the result record.
 static hipError_t solver_launch(const SolverView* views, int G, const qtr_params& prm, ViewStage* stage,
-                                hipStream_t stream, hipEvent_t ev_graph, hipEvent_t ev_clique, bool reset_done = false) {
+                                hipStream_t stream, hipEvent_t ev_graph, hipEvent_t ev_clique, bool reset_done = false,
+                                bool shares_device = false) {
   hipError_t e;
   (void)hipGetLastError();  // a stale sticky error (e.g. timing query on an unrecorded event) is not ours
   SolverArgs a;
@@ -4292,7 +4324,8 @@ static hipError_t solver_launch(const SolverView* views, int G, const qtr_params
         LAUNCH_SV(k_graph_build, a, dim3(nsb, nb, G), dim3(GB2_THREADS), 0, stream, beta, graph_margin(beta), prep);
     }
     if (ev_graph) hipEventRecord(ev_graph, stream);
-    scan_batch = clique_stage_launch(a, G, L, prm.inlier_selection_mode, prm.kcore_heuristic_threshold, stream, prep_hcore, true);
+    scan_batch = clique_stage_launch(a, G, L, prm.inlier_selection_mode, prm.kcore_heuristic_threshold, stream, prep_hcore, true,
+                                     false, shares_device);
   }
   if (ev_clique) hipEventRecord(ev_clique, stream);
   launch_finalize(a, G, prm, stream, scan_batch);
@@ -4301,12 +4334,12 @@ static hipError_t solver_launch(const SolverView* views, int G, const qtr_params
 
 hipError_t solver_enqueue(const SolverBufs& B, const float4* src, const float4* tgt, int L, const qtr_params& prm,
                           hipStream_t stream, int* pinned_state /* unused */, hipEvent_t ev_graph, hipEvent_t ev_clique,
-                          bool reset_done) {
+                          bool reset_done, bool shares_device) {
   (void)pinned_state;
   const hipError_t e = ensure_range_table(B, prm);
   if (e != hipSuccess) return e;
   const SolverView V = make_solver_view(B, src, tgt, L);
-  return solver_launch(&V, 1, prm, nullptr, stream, ev_graph, ev_clique, reset_done);
+  return solver_launch(&V, 1, prm, nullptr, stream, ev_graph, ev_clique, reset_done, shares_device);
 }
 // the state reset of a run, for callers that can issue it early (the whole-path driver: beside the FPFH chain)
 __global__ void k_state_reset(SolverState* st) {
