@@ -3022,23 +3022,16 @@ static int lane_enqueue_refine(qtr_handle* h, Lane& ln) {
   }
   ln.active.swap(ref);
   if (ln.active.empty()) return lane_start_chunk(h, ln);
-  const QtrIcpCfg cfg = icp_cfg_of(&J.icp);
-  const bool gicp = J.icp.method == QTR_ICP_PLANE_TO_PLANE || J.icp.method == QTR_ICP_VOXEL_PLANE_TO_PLANE;  // (needs source normals)
-  const bool plane = J.icp.method == QTR_ICP_POINT_TO_PLANE || gicp;
   ln.iv.clear();
   std::vector<int> seqs;
   int max_nt = 1;
   for (int g : ln.active) {
     Slot& s = h->slots[ln.first_slot + g];
     IcpView v = s.icp.v;  // (the slot's arena; the single-pair calls' own view is left as it is)
-    // cloud[0] / cloud[1] hold the caller's source / target (as qtr_refine_pair reads them)
-    v.src = s.fb.cloud[0].vox;
-    v.tgt = s.fb.cloud[1].vox;
-    v.nrm = plane ? s.fb.cloud[1].normals : nullptr;
-    v.src_nrm = gicp ? s.fb.cloud[0].normals : nullptr;  // (the FPFH stage's; nothing writes them after it)
-    v.ns = ln.ns[g];
-    v.nt = ln.nt[g];
-    v.cfg = cfg;
+    // cloud[0] / cloud[1] hold the caller's source / target (as qtr_refine_pair reads them); the normals are the FPFH
+    // stage's, nothing writes them after it
+    icp_view_bind(v, &J.icp, s.fb.cloud[0].vox, ln.ns[g], s.fb.cloud[0].normals, s.fb.cloud[1].vox, ln.nt[g],
+                  s.fb.cloud[1].normals);
     v.cell_cnt = s.icp.cells;
     v.cell_start = s.icp.cells + s.icp.cap_cells + 1;
     v.mail = s.fb.mail;
@@ -3086,7 +3079,7 @@ static int lane_refine_grids(qtr_handle* h, Lane& ln) {
   std::vector<IcpView> V;
   std::vector<QtrIcpState> init;
   int max_nt = 1, max_ncell = 1, max_nchunk = 1;
-  const bool voxels = J.icp.method == QTR_ICP_VOXEL_PLANE_TO_PLANE;
+  const bool voxels = icp_voxel_grid(J.icp.method);
   for (size_t k = 0; k < ln.active.size(); ++k) {
     const int g = ln.active[k], pair = ln.first_pair + g;
     Slot& s = h->slots[ln.first_slot + g];
@@ -3098,8 +3091,7 @@ static int lane_refine_grids(qtr_handle* h, Lane& ln) {
     const int grid = voxels ? icp_voxel_grid_of(v, s.mail + MAIL_ICP_BOX, J.icp.max_correspondence_distance, h->err, sizeof(h->err))
                             : (int)icp_grid_of(v, s.mail + MAIL_ICP_BOX, J.icp.max_correspondence_distance, s.icp.cap_cells);
     if (grid <= 0) {
-      st0.reason = QTR_ICP_STOP_TOO_FEW;
-      icp_result_from(&J.refined[pair], st0);
+      icp_result_empty(&J.refined[pair], J.results[pair].T);
       J.refined[pair].status = grid < 0 ? QTR_ERR_CAPACITY : QTR_OK;
       J.ref_state[pair] = 2;
       continue;
@@ -3413,7 +3405,7 @@ static int submit_batch_impl(qtr_handle* h, const qtr_pair_desc* pairs, int B, c
     for (auto& sl : h->slots) {
       QTR_HIP_TRY(h, icp_reserve(sl.icp, h->lim.max_voxels, QTR_ICP_MAX_ITERATIONS));
       QTR_HIP_TRY(h, icp_reserve_cells(sl.icp, QTR_ICP_BATCH_CELLS));
-      if (icp->method == QTR_ICP_VOXEL_PLANE_TO_PLANE) QTR_HIP_TRY(h, icp_reserve_vox(sl.icp, h->lim.max_voxels));
+      if (icp_voxel_grid(icp->method)) QTR_HIP_TRY(h, icp_reserve_vox(sl.icp, h->lim.max_voxels));
     }
   BatchJob& J = h->job;
   J.pairs = pairs;
@@ -3577,8 +3569,7 @@ static int check_icp_params(qtr_handle* h, const qtr_icp_params* p) {
   if (!p || !icp_finite(p->max_correspondence_distance) || !(p->max_correspondence_distance > 0) ||
       !icp_finite(p->transformation_epsilon) || p->transformation_epsilon < 0 || !icp_finite(p->euclidean_fitness_epsilon) ||
       p->euclidean_fitness_epsilon < 0 || p->max_iterations < 1 || p->max_iterations > QTR_ICP_MAX_ITERATIONS ||
-      (p->method != QTR_ICP_POINT_TO_PLANE && p->method != QTR_ICP_POINT_TO_POINT && p->method != QTR_ICP_PLANE_TO_PLANE &&
-       p->method != QTR_ICP_VOXEL_PLANE_TO_PLANE) || p->min_correspondences < 0 ||
+      !icp_method_known(p->method) || p->min_correspondences < 0 ||
       !icp_finite((double)p->normal_radius) || !(p->normal_radius > 0)) {
     snprintf(h->err, sizeof(h->err), "invalid ICP parameter");
     return QTR_ERR_BAD_ARG;
@@ -3586,65 +3577,34 @@ static int check_icp_params(qtr_handle* h, const qtr_icp_params* p) {
   return QTR_OK;
 }
 
-// The loop on device-resident clouds: grid over the target, then the iterations, one launch each, with no host read-back
-// inside a block of h->icp_block launches (0: all max_iterations of them in one go).
-static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const float4* d_tgt, int nt, const float4* d_nrm,
-                      const float4* d_src_nrm, const double* guess, const qtr_icp_params* prm, qtr_icp_result* res) {
-  QtrIcpState init;
-  qtr_icp_init(&init, guess);
-  init.reason = QTR_ICP_STOP_TOO_FEW;  // (what an empty cloud reports; the device state starts RUNNING)
-  icp_result_from(res, init);
+// The single-call loop on the slot's ICP arena, which icp_device and the voxel map's registration (voxelmap.hip) share: the
+// empty result, the slot's debug / timing fields, then - unless `empty`: there is nothing to refine - bind() (the caller's
+// checks, reservations and view), before(&go) (what precedes the loop and ends with the initial state on the device, between
+// ev[0] and ev[1]; go = false: nothing to refine after all), launch(v) per iteration with no host read-back inside a block
+// of QTR_ICP_BLOCK launches (0: all max_iterations of them in one go), the final read-back, the result and the times.
+extern "C++" {  // (a template, inside this file's extern "C")
+template <class Bind, class Before, class Launch>
+static int icp_loop(qtr_handle* h, Slot& s, int ns, bool empty, const double* guess, const qtr_icp_params* prm,
+                    qtr_icp_result* res, Bind bind, Before before, Launch launch) {
+  icp_result_empty(res, guess);
   res->status = QTR_OK;
   s.icp_ns = 0;
   s.icp_iters = 0;
   s.icp_ms[0] = s.icp_ms[1] = 0.f;
-  if (ns == 0 || nt == 0) return QTR_OK;
-  const bool voxels = prm->method == QTR_ICP_VOXEL_PLANE_TO_PLANE;
-  const bool gicp = prm->method == QTR_ICP_PLANE_TO_PLANE || voxels;  // (needs source normals)
-  if (gicp && (!d_nrm || !d_src_nrm)) {
-    snprintf(h->err, sizeof(h->err), "plane-to-plane needs the normals of both clouds");
-    return QTR_ERR_BAD_ARG;
-  }
+  if (empty) return QTR_OK;
+  QTR_TRY(bind());
   IcpBufs& B = s.icp;
-  QTR_HIP_TRY(h, icp_reserve(B, h->lim.max_voxels, QTR_ICP_MAX_ITERATIONS));
-  if (voxels) QTR_HIP_TRY(h, icp_reserve_vox(B, h->lim.max_voxels));
-  IcpView& v = B.v;
-  v.src = d_src;
-  v.tgt = d_tgt;
-  v.nrm = (prm->method == QTR_ICP_POINT_TO_PLANE || gicp) ? d_nrm : nullptr;
-  v.src_nrm = gicp ? d_src_nrm : nullptr;
-  v.ns = ns;
-  v.nt = nt;
-  v.cfg = icp_cfg_of(prm);
+  const IcpView& v = B.v;
   const hipStream_t st = s.stream;
   QTR_HIP_TRY(h, hipEventRecord(s.ev[0], st));
-  // bounding box of the finite target points (one read-back per call: it sizes the cell table)
-  QTR_HIP_TRY(h, icp_box_enqueue(v, B.h_bbox, st));
-  QTR_HIP_TRY(h, hipMemcpyAsync(B.h_bbox, v.bbox, 24, hipMemcpyDeviceToHost, st));
-  QTR_HIP_TRY(h, hipStreamSynchronize(st));
-  if (voxels) {
-    const int grid = icp_voxel_grid_of(v, B.h_bbox, prm->max_correspondence_distance, h->err, sizeof(h->err));
-    if (grid < 0) return QTR_ERR_CAPACITY;
-    if (grid == 0) return QTR_OK;
-  } else if (!icp_grid_of(v, B.h_bbox, prm->max_correspondence_distance, QTR_ICP_CELL_CAP)) {
-    return QTR_OK;  // no finite target point
-  }
-  QTR_HIP_TRY(h, icp_reserve_cells(B, v.ncell));
-  v.cell_cnt = B.cells;
-  v.cell_start = B.cells + B.cap_cells + 1;
-  QtrIcpState st0;
-  qtr_icp_init(&st0, guess);
-  QTR_HIP_TRY(h, icp_grid_enqueue(v, st0, st, voxels));
+  bool go = true;
+  QTR_TRY(before(&go));
+  if (!go) return QTR_OK;
   QTR_HIP_TRY(h, hipEventRecord(s.ev[1], st));
-  const int nchunk = qtr_div_up(ns, QTR_ICP_CHUNK);
   const int block = h->icp_block > 0 ? h->icp_block : prm->max_iterations;
   for (int it = 0; it < prm->max_iterations;) {
     const int m = std::min(block, prm->max_iterations - it);
-    for (int k = 0; k < m; ++k) {
-      if (voxels) hipLaunchKernelGGL(k_icp_iter_vgicp, dim3(nchunk), dim3(256), 0, st, v);
-      else if (gicp) hipLaunchKernelGGL(k_icp_iter_gicp, dim3(nchunk), dim3(256), 0, st, v);
-      else hipLaunchKernelGGL(k_icp_iter, dim3(nchunk), dim3(256), 0, st, v);
-    }
+    for (int k = 0; k < m; ++k) launch(v);
     QTR_HIP_TRY(h, hipGetLastError());
     it += m;
     if (it >= prm->max_iterations) break;
@@ -3665,6 +3625,49 @@ static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const
   s.times = qtr_stage_times{};
   s.times.total = s.icp_ms[0] + s.icp_ms[1];
   return QTR_OK;
+}
+}  // extern "C++"
+
+// icp_loop on two device-resident clouds: before the loop the grid over the target (box, one read-back that sizes the cell
+// table, counting sort, method 3's records).
+static int icp_device(qtr_handle* h, Slot& s, const float4* d_src, int ns, const float4* d_tgt, int nt, const float4* d_nrm,
+                      const float4* d_src_nrm, const double* guess, const qtr_icp_params* prm, qtr_icp_result* res) {
+  const bool voxels = icp_voxel_grid(prm->method);
+  const hipStream_t st = s.stream;
+  IcpBufs& B = s.icp;
+  IcpView& v = B.v;
+  const auto bind = [&]() -> int {
+    if (icp_reads_src_normals(prm->method) && (!d_nrm || !d_src_nrm)) {
+      snprintf(h->err, sizeof(h->err), "plane-to-plane needs the normals of both clouds");
+      return QTR_ERR_BAD_ARG;
+    }
+    QTR_HIP_TRY(h, icp_reserve(B, h->lim.max_voxels, QTR_ICP_MAX_ITERATIONS));
+    if (voxels) QTR_HIP_TRY(h, icp_reserve_vox(B, h->lim.max_voxels));
+    icp_view_bind(v, prm, d_src, ns, d_src_nrm, d_tgt, nt, d_nrm);
+    return QTR_OK;
+  };
+  const auto before = [&](bool* go) -> int {
+    QTR_HIP_TRY(h, icp_box_enqueue(v, B.h_bbox, st));
+    QTR_HIP_TRY(h, hipMemcpyAsync(B.h_bbox, v.bbox, 24, hipMemcpyDeviceToHost, st));
+    QTR_HIP_TRY(h, hipStreamSynchronize(st));
+    const int grid = voxels ? icp_voxel_grid_of(v, B.h_bbox, prm->max_correspondence_distance, h->err, sizeof(h->err))
+                            : (int)icp_grid_of(v, B.h_bbox, prm->max_correspondence_distance, QTR_ICP_CELL_CAP);
+    if (grid < 0) return QTR_ERR_CAPACITY;
+    if (grid == 0) {  // no finite target point
+      *go = false;
+      return QTR_OK;
+    }
+    QTR_HIP_TRY(h, icp_reserve_cells(B, v.ncell));
+    v.cell_cnt = B.cells;
+    v.cell_start = B.cells + B.cap_cells + 1;
+    QtrIcpState st0;
+    qtr_icp_init(&st0, guess);
+    QTR_HIP_TRY(h, icp_grid_enqueue(v, st0, st, voxels));
+    return QTR_OK;
+  };
+  const dim3 chunks(qtr_div_up(ns, QTR_ICP_CHUNK));
+  return icp_loop(h, s, ns, ns == 0 || nt == 0, guess, prm, res, bind, before,
+                  [&](const IcpView& w) { icp_iter_launch(prm->method, chunks, st, w); });
 }
 
 static const double kIcpIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
@@ -3742,9 +3745,9 @@ int qtr_icp(qtr_handle* h, int slot, const float* src4, int n_s, const float* tg
   Slot& s = *sp;
   int rc = check_icp_params(h, prm);
   if (rc != QTR_OK) return res->status = rc;
-  if (prm->method == QTR_ICP_PLANE_TO_PLANE || prm->method == QTR_ICP_VOXEL_PLANE_TO_PLANE)  // (the source normals at normal_radius)
+  if (icp_reads_src_normals(prm->method))  // (at normal_radius)
     return qtr_gicp(h, slot, src4, n_s, nullptr, tgt4, n_t, tgt_normals4, guess, prm, res, mem);
-  const bool plane = prm->method == QTR_ICP_POINT_TO_PLANE, run = n_s > 0 && n_t > 0;
+  const bool plane = icp_reads_tgt_normals(prm->method), run = n_s > 0 && n_t > 0;
   const int n[2] = {n_s, n_t};
   const float4* pts[2] = {(const float4*)src4, (const float4*)tgt4};
   const float4* nrm[2] = {nullptr, plane ? (const float4*)tgt_normals4 : nullptr};
@@ -3766,7 +3769,7 @@ int qtr_gicp(qtr_handle* h, int slot, const float* src4, int n_s, const float* s
   Slot& s = *sp;
   int rc = check_icp_params(h, prm);
   if (rc != QTR_OK) return res->status = rc;
-  if (prm->method != QTR_ICP_PLANE_TO_PLANE && prm->method != QTR_ICP_VOXEL_PLANE_TO_PLANE) {
+  if (!icp_reads_src_normals(prm->method)) {
     snprintf(h->err, sizeof(h->err), "qtr_gicp: method must be QTR_ICP_PLANE_TO_PLANE or QTR_ICP_VOXEL_PLANE_TO_PLANE");
     return res->status = QTR_ERR_BAD_ARG;
   }

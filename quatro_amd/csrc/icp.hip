@@ -16,7 +16,12 @@
 // partial per workgroup; the LAST workgroup to finish (atomic ticket) adds the partials in workgroup order
 // (icp_reduce_tail, which the evaluation shares), solves, updates T and decides whether to stop.  Nobody waits for
 // anybody, so no co-residency is assumed.  A launch that finds the stop flag set returns at once, so the host can enqueue
-// iterations without reading anything back.
+// iterations without reading anything back.  The frame around the terms is icp_iter_begin / icp_iter_finish; d_icp_iter
+// and the voxel map's k_vmap_iter (voxelmap.hip) state only where their terms come from.
+//
+// What a method reads (target normals, source normals, a voxel grid) is asked of three predicates on the host side below;
+// icp_iter_launch picks the iteration kernel, icp_view_bind fills a view, icp_result_empty is the result of a pair with
+// nothing to refine.  The single-call host loop is icp_loop (capi.hip).
 //
 // Batched refinement (qtr_submit_batch_refine): the same kernels in grouped form, blockIdx.y = pair of the lane's group,
 // the per-pair IcpViews in device memory (ViewExt).  Every pair runs the per-pair body the single-pair kernel runs
@@ -253,22 +258,43 @@ __device__ __forceinline__ void d_icp_voxel_stats(const IcpView& v, int i) {
 __global__ __launch_bounds__(256) void k_icp_voxel_order(IcpView v) { d_icp_voxel_order(v, blockIdx.x * blockDim.x + threadIdx.x); }
 __global__ __launch_bounds__(256) void k_icp_voxel_stats(IcpView v) { d_icp_voxel_stats(v, blockIdx.x * blockDim.x + threadIdx.x); }
 
+// The frame every iteration kernel shares (d_icp_iter below, k_vmap_iter of voxelmap.hip); a kernel states only where its
+// terms come from.  icp_iter_begin: the early return on the stop flag (false: stopped), the current T, the zeroed terms.
+__device__ __forceinline__ bool icp_iter_begin(const IcpView& v, double* T, double* o) {
+  const QtrIcpState* st = v.st;
+  if (st->stop) return false;  // (uniform: written by an earlier launch)
+#pragma unroll
+  for (int k = 0; k < 16; ++k) T[k] = st->T[k];
+#pragma unroll
+  for (int k = 0; k < QTR_ICP_NT; ++k) o[k] = 0.0;
+  return true;
+}
+
+// icp_iter_finish, called by every thread of the workgroup with its terms o[0 .. NT): the reduction tail; in the last
+// workgroup the padding terms, the step with its trace row, the ticket's reset.
+template <int NT>
+__device__ __forceinline__ void icp_iter_finish(const IcpView& v, const double* o, int blk, int nblk) {
+  __shared__ double s_S[QTR_ICP_NT];
+  if (!icp_reduce_tail<NT, QTR_ICP_NT>(o, v.partials, v.ticket, blk, nblk, s_S)) return;
+  if (threadIdx.x == 0) {
+    for (int k = NT; k < QTR_ICP_NT; ++k) s_S[k] = 0.0;  // (the padding terms)
+    QtrIcpState s = *v.st;
+    double* tr = (s.iterations < v.cfg.max_iterations) ? v.trace + (size_t)s.iterations * 18 : nullptr;
+    qtr_icp_step(&v.cfg, s_S, &s, tr);
+    *v.st = s;
+    __hip_atomic_store(v.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // One workgroup (chunk `blk` of `nblk`) of one iteration of one pair.  METHOD 2: the plane-to-plane body (cfg.method == 2);
 // 3: its voxelised form, a lookup in place of the search (cfg.method == 3); 0: the instantiation the other two methods
 // always shared.
 template <int METHOD>
 __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) {
   constexpr bool GICP = METHOD == 2, VGICP = METHOD == 3;
-  __shared__ double s_S[QTR_ICP_NT];
-  const QtrIcpState* st = v.st;
-  if (st->stop) return;  // (uniform: written by an earlier launch)
-  double T[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) T[k] = st->T[k];
+  double T[16], o[QTR_ICP_NT];
+  if (!icp_iter_begin(v, T, o)) return;
   const int i = blk * QTR_ICP_CHUNK + threadIdx.x;
-  double o[QTR_ICP_NT];
-#pragma unroll
-  for (int k = 0; k < QTR_ICP_NT; ++k) o[k] = 0.0;
   if (i < v.ns) {
     const float4 p = v.src[i];
     int best = -1, bat = -1;
@@ -321,16 +347,7 @@ __device__ __forceinline__ void d_icp_iter(const IcpView& v, int blk, int nblk) 
       }
     }
   }
-  constexpr int NT = VGICP ? QTR_ICP_T_W + 1 : QTR_ICP_T_CNT + 1;
-  if (!icp_reduce_tail<NT, QTR_ICP_NT>(o, v.partials, v.ticket, blk, nblk, s_S)) return;
-  if (threadIdx.x == 0) {
-    for (int k = NT; k < QTR_ICP_NT; ++k) s_S[k] = 0.0;  // (the padding terms)
-    QtrIcpState s = *v.st;
-    double* tr = (s.iterations < v.cfg.max_iterations) ? v.trace + (size_t)s.iterations * 18 : nullptr;
-    qtr_icp_step(&v.cfg, s_S, &s, tr);
-    *v.st = s;
-    __hip_atomic_store(v.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  icp_iter_finish<VGICP ? QTR_ICP_T_W + 1 : QTR_ICP_T_CNT + 1>(v, o, blk, nblk);
 }
 
 __global__ __launch_bounds__(256) void k_icp_iter(IcpView v) { d_icp_iter<0>(v, (int)blockIdx.x, (int)gridDim.x); }
@@ -558,6 +575,13 @@ static void icp_free(IcpBufs& B) {
   B = IcpBufs{};
 }
 
+// What a method reads.  These three are the only place that knows: the entry points, the view binding, the grid build and
+// the choice of the iteration kernel (icp_iter_launch) all ask them.
+static bool icp_method_known(int method) { return method >= QTR_ICP_POINT_TO_PLANE && method <= QTR_ICP_VOXEL_PLANE_TO_PLANE; }
+static bool icp_voxel_grid(int method) { return method == QTR_ICP_VOXEL_PLANE_TO_PLANE; }  // (records in place of the search)
+static bool icp_reads_src_normals(int method) { return method == QTR_ICP_PLANE_TO_PLANE || icp_voxel_grid(method); }
+static bool icp_reads_tgt_normals(int method) { return method == QTR_ICP_POINT_TO_PLANE || icp_reads_src_normals(method); }
+
 static QtrIcpCfg icp_cfg_of(const qtr_icp_params* prm) {
   QtrIcpCfg c;
   c.max_d2 = prm->max_correspondence_distance * prm->max_correspondence_distance;
@@ -566,9 +590,9 @@ static QtrIcpCfg icp_cfg_of(const qtr_icp_params* prm) {
   c.max_iterations = prm->max_iterations;
   c.method = prm->method;
   c.min_corr = prm->min_correspondences > 0 ? prm->min_correspondences
-               : prm->method == QTR_ICP_POINT_TO_PLANE ? 6
-               : (prm->method == QTR_ICP_PLANE_TO_PLANE || prm->method == QTR_ICP_VOXEL_PLANE_TO_PLANE) ? 4  // (pcl GICP's min_number_correspondences_)
-                                                       : 3;
+               : icp_reads_src_normals(prm->method) ? 4  // (pcl GICP's min_number_correspondences_)
+               : icp_reads_tgt_normals(prm->method) ? 6
+                                                    : 3;
   c.pad = 0;
   return c;
 }
@@ -634,6 +658,38 @@ static void icp_result_from(qtr_icp_result* res, const QtrIcpState& st) {
   res->rmse = st.rmse;
 }
 
+// what a pair with nothing to refine reports: the guess, no correspondence, reason TOO_FEW (the device state starts RUNNING)
+static void icp_result_empty(qtr_icp_result* res, const double* guess) {
+  QtrIcpState init;
+  qtr_icp_init(&init, guess);
+  init.reason = QTR_ICP_STOP_TOO_FEW;
+  icp_result_from(res, init);
+}
+
+// the clouds of a refinement and the normal sets its method reads (the others: null), into a view
+static void icp_view_bind(IcpView& v, const qtr_icp_params* prm, const float4* src, int ns, const float4* src_nrm,
+                          const float4* tgt, int nt, const float4* tgt_nrm) {
+  v.src = src;
+  v.tgt = tgt;
+  v.nrm = icp_reads_tgt_normals(prm->method) ? tgt_nrm : nullptr;
+  v.src_nrm = icp_reads_src_normals(prm->method) ? src_nrm : nullptr;
+  v.ns = ns;
+  v.nt = nt;
+  v.cfg = icp_cfg_of(prm);
+}
+
+// one iteration of a method: of one pair (grid = its chunks), of a group (grid = (chunks of the largest pair, pairs))
+static void icp_iter_launch(int method, dim3 grid, hipStream_t st, const IcpView& v) {
+  if (icp_voxel_grid(method)) hipLaunchKernelGGL(k_icp_iter_vgicp, grid, dim3(256), 0, st, v);
+  else if (icp_reads_src_normals(method)) hipLaunchKernelGGL(k_icp_iter_gicp, grid, dim3(256), 0, st, v);
+  else hipLaunchKernelGGL(k_icp_iter, grid, dim3(256), 0, st, v);
+}
+static void icp_iter_launch(int method, dim3 grid, hipStream_t st, const ViewExt<IcpView>& x) {
+  if (icp_voxel_grid(method)) hipLaunchKernelGGL(k_icp_iter_vgicp_group, grid, dim3(256), 0, st, x);
+  else if (icp_reads_src_normals(method)) hipLaunchKernelGGL(k_icp_iter_gicp_group, grid, dim3(256), 0, st, x);
+  else hipLaunchKernelGGL(k_icp_iter_group, grid, dim3(256), 0, st, x);
+}
+
 // ---- single-pair launches (icp_device and the single evaluations, capi.hip) ----------------------------------------------
 // the box of the finite target points into v.bbox; h_bbox: 6 pinned ints, which the caller reads the box back into
 static hipError_t icp_box_enqueue(const IcpView& v, int* h_bbox, hipStream_t st) {
@@ -693,11 +749,7 @@ static hipError_t icp_grid_enqueue_group(const IcpView* dv, const QtrIcpState* d
 static hipError_t icp_iter_enqueue_group(const IcpView* dv, int G, int max_nchunk, int launches, const int* dseqs,
                                          hipStream_t st, int method) {
   const ViewExt<IcpView> x{dv, {0, 0, 0}};
-  for (int k = 0; k < launches; ++k) {
-    if (method == QTR_ICP_VOXEL_PLANE_TO_PLANE) hipLaunchKernelGGL(k_icp_iter_vgicp_group, dim3(max_nchunk, G), dim3(256), 0, st, x);
-    else if (method == QTR_ICP_PLANE_TO_PLANE) hipLaunchKernelGGL(k_icp_iter_gicp_group, dim3(max_nchunk, G), dim3(256), 0, st, x);
-    else hipLaunchKernelGGL(k_icp_iter_group, dim3(max_nchunk, G), dim3(256), 0, st, x);
-  }
+  for (int k = 0; k < launches; ++k) icp_iter_launch(method, dim3(max_nchunk, G), st, x);
   hipLaunchKernelGGL(k_icp_publish_group, dim3(G), dim3(64), 0, st, x, dseqs);
   return hipGetLastError();
 }

@@ -28,9 +28,10 @@
 //                  the count and the finished record
 // No kernel waits for another workgroup, none is launched cooperatively, all stores are plain vector stores.
 //
-// Registration: k_vmap_iter is d_icp_iter<3> (icp.hip) with the hash lookup in place of the dense cell table: the slot's
-// IcpBufs state, partials, ticket, trace and corr, icp_reduce_tail<QTR_ICP_T_W + 1, QTR_ICP_NT>, qtr_icp_step, the stop
-// flag's early return.  Lookups are plain loads: the table was written by earlier launches.
+// Registration: k_vmap_iter states only where its terms come from, the hash lookup in place of method 3's dense cell table,
+// between the iteration frame of icp.hip (icp_iter_begin / icp_iter_finish: the stop flag's early return, T, the reduction
+// tail, the step, the trace row, the ticket); the host side is capi.hip's icp_loop on the slot's IcpBufs with the empty grid
+// and this kernel as its launch.  Lookups are plain loads: the table was written by earlier launches.
 #ifndef QTR_VOXELMAP_LIB  // libquatro_hip.so carries this code (its handle frees the maps) but exports none of it
 #define QTR_VMAP_API __attribute__((visibility("hidden")))
 #endif
@@ -185,19 +186,12 @@ __device__ __forceinline__ long long d_vmap_find(const VmapView& m, u64 key) {
   return -1;
 }
 
-// one iteration of a registration against the map: d_icp_iter<3> with the hash lookup in place of the dense cell table
+// one iteration of a registration against the map: d_icp_iter<3>'s frame around the hash lookup
 __global__ __launch_bounds__(256) void k_vmap_iter(IcpView v, VmapView m) {
-  __shared__ double s_S[QTR_ICP_NT];
-  const QtrIcpState* st = v.st;
-  if (st->stop) return;  // (uniform: written by an earlier launch)
   const int blk = (int)blockIdx.x, nblk = (int)gridDim.x;
-  double T[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) T[k] = st->T[k];
+  double T[16], o[QTR_ICP_NT];
+  if (!icp_iter_begin(v, T, o)) return;
   const int i = blk * QTR_ICP_CHUNK + threadIdx.x;
-  double o[QTR_ICP_NT];
-#pragma unroll
-  for (int k = 0; k < QTR_ICP_NT; ++k) o[k] = 0.0;
   if (i < v.ns) {
     const float4 p = v.src[i];
     const float4 a = v.src_nrm[i];
@@ -216,16 +210,7 @@ __global__ __launch_bounds__(256) void k_vmap_iter(IcpView v, VmapView m) {
     }
     v.corr[i] = best;
   }
-  constexpr int NT = QTR_ICP_T_W + 1;
-  if (!icp_reduce_tail<NT, QTR_ICP_NT>(o, v.partials, v.ticket, blk, nblk, s_S)) return;
-  if (threadIdx.x == 0) {
-    for (int k = NT; k < QTR_ICP_NT; ++k) s_S[k] = 0.0;  // (the padding terms)
-    QtrIcpState s = *v.st;
-    double* tr = (s.iterations < v.cfg.max_iterations) ? v.trace + (size_t)s.iterations * 18 : nullptr;
-    qtr_icp_step(&v.cfg, s_S, &s, tr);
-    *v.st = s;
-    __hip_atomic_store(v.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  icp_iter_finish<QTR_ICP_T_W + 1>(v, o, blk, nblk);
 }
 
 // a fetch section of the voxels at slots[0 .. n), in that order
@@ -265,10 +250,14 @@ struct qtr_voxel_map {
   qtr_voxel_map_info info = {};
 };
 
-static bool vmap_pose_ok(const double* P) {
-  for (int k = 0; k < 12; ++k)
-    if (!icp_finite(P[k])) return false;
-  return true;
+// rows 0 - 2 of an entry's (verb: "insert" / "register") pose or guess (noun); null: the identity
+static int vmap_check_pose(qtr_handle* h, const char* verb, const char* noun, const double* P) {
+  for (int k = 0; P && k < 12; ++k)
+    if (!icp_finite(P[k])) {
+      snprintf(h->err, sizeof(h->err), "voxel map %s: the %s has a non-finite entry in rows 0 - 2", verb, noun);
+      return QTR_ERR_BAD_ARG;
+    }
+  return QTR_OK;
 }
 
 static int vmap_check(qtr_handle* h, const qtr_voxel_map* m) {
@@ -480,6 +469,34 @@ static int vmap_insert_device(qtr_handle* h, Slot& s, qtr_voxel_map* m, const fl
   return QTR_OK;
 }
 
+// What the two cloud entries do with their cloud before anything runs: the argument checks in the entry's own words (verb:
+// "insert" / "register"; nrm_name: its normals' argument; pose: the insert's, null for a registration, whose guess is checked
+// before), then a host cloud and its normals into in_src / in_tgt.  pts / nrm come back as device pointers.
+static int vmap_stage(qtr_handle* h, Slot& s, const char* verb, const char* nrm_name, const double* pose, int mem, int n,
+                      const float4** pts, const float4** nrm) {
+  if (n < 0 || (n > 0 && !*pts) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) {
+    snprintf(h->err, sizeof(h->err), "bad voxel map %s arguments", verb);
+    return QTR_ERR_BAD_ARG;
+  }
+  if (!*nrm) {
+    snprintf(h->err, sizeof(h->err), "voxel map %s: %s is NULL (the cloud entries do not compute normals)", verb, nrm_name);
+    return QTR_ERR_BAD_ARG;
+  }
+  QTR_TRY(vmap_check_pose(h, verb, "pose", pose));
+  if (n > h->lim.max_points) {
+    snprintf(h->err, sizeof(h->err), "voxel map %s: n=%d exceeds max_points=%d", verb, n, h->lim.max_points);
+    return QTR_ERR_CAPACITY;
+  }
+  QTR_HIP_TRY(h, hipSetDevice(h->device));
+  if (mem == QTR_MEM_HOST && n > 0) {
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, *pts, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
+    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_tgt, *nrm, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
+    *pts = s.in_src;
+    *nrm = s.in_tgt;
+  }
+  return QTR_OK;
+}
+
 int qtr_voxel_map_insert(qtr_handle* h, int slot, qtr_voxel_map* m, const float* xyz4, const float* normals4, int n,
                          const double pose[16], int mem, qtr_voxel_map_insert_info* out) {
   if (out) memset(out, 0, sizeof(*out));
@@ -487,30 +504,8 @@ int qtr_voxel_map_insert(qtr_handle* h, int slot, qtr_voxel_map* m, const float*
   if (!sp) return QTR_ERR_BAD_ARG;
   Slot& s = *sp;
   QTR_TRY(vmap_check(h, m));
-  if (n < 0 || (n > 0 && !xyz4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) {
-    snprintf(h->err, sizeof(h->err), "bad voxel map insert arguments");
-    return QTR_ERR_BAD_ARG;
-  }
-  if (!normals4) {
-    snprintf(h->err, sizeof(h->err), "voxel map insert: normals4 is NULL (the cloud entries do not compute normals)");
-    return QTR_ERR_BAD_ARG;
-  }
-  if (pose && !vmap_pose_ok(pose)) {
-    snprintf(h->err, sizeof(h->err), "voxel map insert: the pose has a non-finite entry in rows 0 - 2");
-    return QTR_ERR_BAD_ARG;
-  }
-  if (n > h->lim.max_points) {
-    snprintf(h->err, sizeof(h->err), "voxel map insert: n=%d exceeds max_points=%d", n, h->lim.max_points);
-    return QTR_ERR_CAPACITY;
-  }
-  QTR_HIP_TRY(h, hipSetDevice(h->device));
   const float4 *d_pts = (const float4*)xyz4, *d_nrm = (const float4*)normals4;
-  if (mem == QTR_MEM_HOST && n > 0) {
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, xyz4, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
-    QTR_HIP_TRY(h, hipMemcpyAsync(s.in_tgt, normals4, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
-    d_pts = s.in_src;
-    d_nrm = s.in_tgt;
-  }
+  QTR_TRY(vmap_stage(h, s, "insert", "normals4", pose, mem, n, &d_pts, &d_nrm));
   return vmap_insert_device(h, s, m, d_pts, d_nrm, n, pose, out);
 }
 
@@ -521,72 +516,36 @@ int qtr_voxel_map_insert_keyframe(qtr_handle* h, int slot, qtr_voxel_map* m, con
   if (!sp) return QTR_ERR_BAD_ARG;
   QTR_TRY(vmap_check(h, m));
   QTR_TRY(vmap_check_kf(h, kf));
-  if (pose && !vmap_pose_ok(pose)) {
-    snprintf(h->err, sizeof(h->err), "voxel map insert: the pose has a non-finite entry in rows 0 - 2");
-    return QTR_ERR_BAD_ARG;
-  }
+  QTR_TRY(vmap_check_pose(h, "insert", "pose", pose));
   QTR_HIP_TRY(h, hipSetDevice(h->device));
   const KfLayout lay = kf_layout(kf->info.n_voxels);
   return vmap_insert_device(h, *sp, m, (const float4*)((const char*)kf->dev + lay.vox),
                             (const float4*)((const char*)kf->dev + lay.normals), kf->info.n_voxels, pose, out);
 }
 
-// the registration of ns device-resident points with their normals: icp_device's loop with k_vmap_iter
+// the registration of ns device-resident points with their normals: icp_loop (capi.hip) with the empty grid, only the
+// state's initialisation before the loop, and k_vmap_iter as its launch
 static int vmap_register_device(qtr_handle* h, Slot& s, const qtr_voxel_map* m, const float4* d_src, int ns,
                                 const float4* d_nrm, const double* guess, const qtr_icp_params* prm, qtr_icp_result* res) {
-  QtrIcpState init;
-  qtr_icp_init(&init, guess);
-  init.reason = QTR_ICP_STOP_TOO_FEW;  // (what an empty cloud reports; the device state starts RUNNING)
-  icp_result_from(res, init);
-  res->status = QTR_OK;
-  s.icp_ns = 0;
-  s.icp_iters = 0;
-  s.icp_ms[0] = s.icp_ms[1] = 0.f;
-  if (ns == 0) return QTR_OK;
-  IcpBufs& B = s.icp;
-  QTR_HIP_TRY(h, icp_reserve(B, std::max(h->lim.max_voxels, h->lim.max_points), QTR_ICP_MAX_ITERATIONS));
-  IcpView& v = B.v;
-  v.src = d_src;
-  v.tgt = nullptr;
-  v.nrm = nullptr;
-  v.src_nrm = d_nrm;
-  v.ns = ns;
-  v.nt = 0;
-  v.ncell = v.dims[0] = v.dims[1] = v.dims[2] = 0;
-  v.cfg = icp_cfg_of(prm);
-  v.cfg.max_d2 = m->v.side * m->v.side;  // (not read: the side is the map's)
   const hipStream_t st = s.stream;
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[0], st));
-  QtrIcpState st0;
-  qtr_icp_init(&st0, guess);
-  hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, v, st0);
-  QTR_HIP_TRY(h, hipGetLastError());
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[1], st));
-  const int nchunk = qtr_div_up(ns, QTR_ICP_CHUNK);
-  const int block = h->icp_block > 0 ? h->icp_block : prm->max_iterations;
-  for (int it = 0; it < prm->max_iterations;) {
-    const int k_end = std::min(block, prm->max_iterations - it);
-    for (int k = 0; k < k_end; ++k) hipLaunchKernelGGL(k_vmap_iter, dim3(nchunk), dim3(256), 0, st, v, m->v);
+  IcpView& v = s.icp.v;
+  const auto bind = [&]() -> int {
+    QTR_HIP_TRY(h, icp_reserve(s.icp, std::max(h->lim.max_voxels, h->lim.max_points), QTR_ICP_MAX_ITERATIONS));
+    icp_view_bind(v, prm, d_src, ns, d_nrm, nullptr, 0, nullptr);
+    v.ncell = v.dims[0] = v.dims[1] = v.dims[2] = 0;
+    v.cfg.max_d2 = m->v.side * m->v.side;  // (not read: the side is the map's)
+    return QTR_OK;
+  };
+  const auto before = [&](bool*) -> int {
+    QtrIcpState st0;
+    qtr_icp_init(&st0, guess);
+    hipLaunchKernelGGL(k_icp_init, dim3(1), dim3(64), 0, st, v, st0);
     QTR_HIP_TRY(h, hipGetLastError());
-    it += k_end;
-    if (it >= prm->max_iterations) break;
-    QTR_HIP_TRY(h, hipMemcpyAsync(B.h_state, v.st, sizeof(QtrIcpState), hipMemcpyDeviceToHost, st));
-    QTR_HIP_TRY(h, hipStreamSynchronize(st));
-    if (B.h_state->stop) break;
-  }
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[2], st));
-  QTR_HIP_TRY(h, hipMemcpyAsync(B.h_state, v.st, sizeof(QtrIcpState), hipMemcpyDeviceToHost, st));
-  QTR_HIP_TRY(h, hipStreamSynchronize(st));
-  icp_result_from(res, *B.h_state);
-  s.icp_ns = ns;
-  s.icp_iters = B.h_state->iterations;
-  float ms = 0;
-  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.icp_ms[0] = ms;
-  if (hipEventElapsedTime(&ms, s.ev[1], s.ev[2]) == hipSuccess) s.icp_ms[1] = ms;
-  s.times_pending = 0;
-  s.times = qtr_stage_times{};
-  s.times.total = s.icp_ms[0] + s.icp_ms[1];
-  return QTR_OK;
+    return QTR_OK;
+  };
+  const dim3 chunks(qtr_div_up(ns, QTR_ICP_CHUNK));
+  return icp_loop(h, s, ns, ns == 0, guess, prm, res, bind, before,
+                  [&](const IcpView& w) { hipLaunchKernelGGL(k_vmap_iter, chunks, dim3(256), 0, st, w, m->v); });
 }
 
 static int vmap_check_register(qtr_handle* h, const qtr_voxel_map* m, const double* guess, const qtr_icp_params* prm) {
@@ -596,11 +555,7 @@ static int vmap_check_register(qtr_handle* h, const qtr_voxel_map* m, const doub
     snprintf(h->err, sizeof(h->err), "voxel map register: method must be QTR_ICP_VOXEL_PLANE_TO_PLANE");
     return QTR_ERR_BAD_ARG;
   }
-  if (guess && !vmap_pose_ok(guess)) {
-    snprintf(h->err, sizeof(h->err), "voxel map register: the guess has a non-finite entry in rows 0 - 2");
-    return QTR_ERR_BAD_ARG;
-  }
-  return QTR_OK;
+  return vmap_check_pose(h, "register", "guess", guess);
 }
 
 // the guess as the state takes it: rows 0 - 2 the caller's, row 3 (0 0 0 1)
@@ -618,32 +573,12 @@ int qtr_voxel_map_register(qtr_handle* h, int slot, const qtr_voxel_map* m, cons
   Slot& s = *sp;
   int rc = vmap_check_register(h, m, guess, prm);
   if (rc != QTR_OK) return res->status = rc;
-  if (n < 0 || (n > 0 && !src4) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) {
-    snprintf(h->err, sizeof(h->err), "bad voxel map register arguments");
-    return res->status = QTR_ERR_BAD_ARG;
-  }
-  if (!src_normals4) {
-    snprintf(h->err, sizeof(h->err), "voxel map register: src_normals4 is NULL (the cloud entries do not compute normals)");
-    return res->status = QTR_ERR_BAD_ARG;
-  }
-  if (n > h->lim.max_points) {
-    snprintf(h->err, sizeof(h->err), "voxel map register: n=%d exceeds max_points=%d", n, h->lim.max_points);
-    return res->status = QTR_ERR_CAPACITY;
-  }
-  rc = [&]() -> int {
-    QTR_HIP_TRY(h, hipSetDevice(h->device));
-    const float4 *d_src = (const float4*)src4, *d_nrm = (const float4*)src_normals4;
-    if (mem == QTR_MEM_HOST && n > 0) {
-      QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, src4, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
-      QTR_HIP_TRY(h, hipMemcpyAsync(s.in_tgt, src_normals4, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
-      d_src = s.in_src;
-      d_nrm = s.in_tgt;
-    }
-    double g[16];
-    vmap_guess(guess, g);
-    return vmap_register_device(h, s, m, d_src, n, d_nrm, g, prm, res);
-  }();
-  return res->status = rc;
+  const float4 *d_src = (const float4*)src4, *d_nrm = (const float4*)src_normals4;
+  rc = vmap_stage(h, s, "register", "src_normals4", nullptr, mem, n, &d_src, &d_nrm);
+  if (rc != QTR_OK) return res->status = rc;
+  double g[16];
+  vmap_guess(guess, g);
+  return res->status = vmap_register_device(h, s, m, d_src, n, d_nrm, g, prm, res);
 }
 
 int qtr_voxel_map_register_keyframe(qtr_handle* h, int slot, const qtr_voxel_map* m, const qtr_keyframe* kf,

@@ -1,7 +1,7 @@
 """The persistent Gaussian voxel map on the MI355X (qtr_voxel_map_*): bit-parity with the host restatement
 (tests/vmap_ref/vmap_ref.cpp) of the records after every insert and of every iteration of a registration, a crowded table
-whose probe chains wrap, the capacity refusal, the equality with the merged method 3 on positive-octant targets, the path
-equalities, scan-to-map odometry and build_map, the refusals, the C++ demo and the two libraries' symbol tables.  Everything
+whose probe chains wrap, the capacity refusal, the equality with the merged method 3 on positive-octant targets, the
+single-call loops in blocks (QTR_ICP_BLOCK) against the unblocked ones, the path equalities, scan-to-map odometry and build_map, the refusals, the C++ demo and the two libraries' symbol tables.  Everything
 goes through the C ABI (quatro_amd.lib; the map's entry points are libquatro_voxelmap.so's, include/quatro_voxelmap.h)."""
 import os
 import subprocess
@@ -190,6 +190,56 @@ def test_map_registration_equals_method_3_bit_for_bit(hip, vox_pair):
     shift = (t2[0, :3] - vt[0, :3]).astype(np.float64)
     G0 = R.rigid(np.eye(3), shift) @ Tgt @ R.rigid(R.rot(0.012, -0.009, 0.015), [0.25, -0.3, 0.08]) @ R.rigid(np.eye(3), -shift)
     _against_method_3(hip, s2, ns, t2, tn2, G0, 12, "kitti64_pair(2) in the positive octant")
+
+
+def _handle(n_slots, **env):
+    """A handle created under these environment variables (the handle reads them once, when it is made)."""
+    from quatro_amd import lib as ql
+    keep = {k: os.environ.get(k) for k in env}
+    os.environ.update(env)
+    try:
+        return ql.Handle(0, n_slots=n_slots)
+    finally:
+        for k, v in keep.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def test_single_call_loops_in_blocks_equal_the_unblocked_loops(hip):
+    """QTR_ICP_BLOCK=4 against all launches at once, through both single-call entries of the one host loop: qtr_gicp method 3
+    and VoxelMap.register on a map of the targets under no pose (300 sources: two workgroups per launch, so the last-arriver
+    path is live).  10 fixed updates are the blocks 4 + 4 + 2, the last one short; with transformation_epsilon = 1e-2 both
+    restatements stop after 6 updates (reason 2) on this input, inside the second block, so the host leaves the loop at its
+    second read-back."""
+    from quatro_amd import lib as ql
+    s, sn, t, tn = K.octant_hand_built()
+    assert s.shape[0] == 300 and t.shape[0] == 500
+    blocked = _handle(1, QTR_ICP_BLOCK="4")
+    maps = []
+    try:
+        for h in (hip, blocked):
+            maps.append(h.voxel_map(1.0, 1 << 16))
+            maps[-1].insert(t, tn, None)
+        for kw, iters in ((dict(max_iterations=10, transformation_epsilon=0.0, euclidean_fitness_epsilon=0.0), 10),
+                          (dict(max_iterations=30, transformation_epsilon=1e-2, euclidean_fitness_epsilon=0.0), 6)):
+            prm = _vg(max_correspondence_distance=1.0, **kw)
+            for what in ("qtr_gicp method 3", "VoxelMap.register"):
+                got = []
+                for h, vm in zip((hip, blocked), maps):
+                    g = h.gicp(s, t, sn, tn, K.GUESS, prm) if what.startswith("qtr_gicp") else vm.register(s, sn, K.GUESS, prm)
+                    got.append((g, h.debug_fetch(ql.DBG_ICP_TRACE, np.float64).reshape(-1, 18), h.debug_fetch(ql.DBG_ICP_CORR, np.int32)))
+                (g0, trace0, corr0), (g1, trace1, corr1) = got
+                print(f"{what}, {kw}: {g0['iterations']} / {g1['iterations']} iterations, stop {g0['stop_reason']} / {g1['stop_reason']}")
+                assert g0["iterations"] == iters and g0["valid"], (what, kw, g0)
+                _same_icp(g1, g0, f"{what}, {kw}: blocked against unblocked")
+                assert trace1.shape == trace0.shape == (iters, 18) and np.array_equal(_bits(trace1), _bits(trace0)), (what, kw)
+                assert np.array_equal(corr1, corr0), (what, kw)
+    finally:
+        for m in maps:
+            m.destroy()
+        blocked.close()
 
 
 def test_path_equalities(hip, vox_pair):
