@@ -13,6 +13,7 @@
 #include "common.h"
 #include "frontend.h"
 #include "solver.h"
+#include "stage_times.h"
 
 struct RcclIdByValue {  // ncclUniqueId: passed by value to ncclCommInitRank
   char internal[QTR_COMM_ID_BYTES];
@@ -21,13 +22,11 @@ struct RcclIdByValue {  // ncclUniqueId: passed by value to ncclCommInitRank
 struct Slot {
   hipStream_t stream = nullptr;
   hipStream_t stream2 = nullptr;  // second cloud's front end runs concurrently
-  hipEvent_t ev[8] = {};
+  hipEvent_t ev[EV_COUNT] = {};  // by name: SlotEvent (stage_times.h)
   hipEvent_t ev_vox = nullptr;    // voxel centroids complete (stream) -> Matcher means may start (stream2)
   // qtr_register_pair_corr: the back end of the caller's correspondences runs BESIDE the front end, on a third stream
   // (created on the slot's first such call: ensure_stream3)
   hipStream_t stream3 = nullptr;
-  hipEvent_t ev_be0 = nullptr;    // the back end's start on stream3 (stage times)
-  hipEvent_t ev_end = nullptr;    // the call's end on `stream`, behind the join (stage times)
   hipEvent_t ev_fork = nullptr;   // stream -> stream3 at the call's start: what the slot's stream held before it (no timing)
   hipEvent_t ev_join = nullptr;   // stream3 -> stream (no timing)
   void* solver_arena = nullptr;
@@ -51,8 +50,8 @@ struct Slot {
   int seq = 0;                   // last sequence number handed to a phase-ending kernel
   unsigned long long exact_nodes = 0;  // search-tree nodes of the last PMC_EXACT run
   int exact_aborted = 0;               // 1: its time limit was hit (heuristic clique returned)
-  int times_pending = 0;         // 1: qtr_solve, 2: qtr_register_pair, 5: qtr_register_keyframes, 6: qtr_register_pair_corr with the
-                                 // back end beside the front end — stage times are read off the events lazily
+  TimesShape times_pending = TIMES_NONE;  // the shape of the last call: its stage times are read off the events lazily, by
+                                          // the table of stage_times.h (compute_times)
   int nn_pending = 0;            // the nearest-neighbour events of the last match have not been added to the totals yet
   int nn_timed_last = 0;         // the last match had its event pairs attached (qtr_set_nn_event_stride)
   long long n_matches = 0;       // matches this slot has run
@@ -448,7 +447,7 @@ void qtr_destroy(qtr_handle* h) {
     for (auto& e : s.ev)
       if (e) (void)hipEventDestroy(e);
     if (s.ev_vox) (void)hipEventDestroy(s.ev_vox);
-    for (hipEvent_t e : {s.ev_be0, s.ev_end, s.ev_fork, s.ev_join})
+    for (hipEvent_t e : {s.ev_fork, s.ev_join})
       if (e) (void)hipEventDestroy(e);
     for (auto& e : s.fb.ev_nn)
       if (e) (void)hipEventDestroy(e);
@@ -641,7 +640,8 @@ static void fill_nn_times(Slot& s) {
 // Waits until the phase-ending kernel has published `seq` in mailbox word `idx` (frontend.h MAIL_SEQ_*).  The
 // default is to WATCH the pinned word — the store crosses PCIe in ~1-2 us, the runtime's stream wait costs
 // 20-30 us per phase boundary (three per registration) — and to fall back to the runtime every 64k polls so
-// that a failed launch or a lost device ends the wait.  QTR_HOST_WAIT=block uses hipStreamSynchronize only.
+// that a failed launch or a lost device ends the wait.  QTR_HOST_WAIT=block uses hipStreamSynchronize only.  `st`: the stream
+// the phase-ending kernel was enqueued on — the one that is queried and synchronised, whichever slot or lane owns it.
 // the payload a sequence word announces is consumed only once its tag matches (common.h, mail_store_line): the
 // sequence word can reach host memory before the counters
 static bool mail_payload_ok(const Slot& s, int idx, int seq) {
@@ -675,15 +675,15 @@ static bool mail_ready(const Slot& s, int idx, int seq) {
   return mail_payload_ok(s, idx, seq);
 }
 
-static int wait_mail(qtr_handle* h, Slot& s, int idx, int seq) {
+static int wait_mail(qtr_handle* h, Slot& s, hipStream_t st, int idx, int seq) {
   volatile int* p = s.mail + idx;
   if (!h->spin_wait) {
-    QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
+    QTR_HIP_TRY(h, hipStreamSynchronize(st));
   } else {
     for (unsigned long spins = 1;; ++spins) {
       if (__atomic_load_n(p, __ATOMIC_ACQUIRE) == seq) break;  // now make sure the payload it announces is complete
       if ((spins & 0xffff) == 0) {
-        const hipError_t q = hipStreamQuery(s.stream);
+        const hipError_t q = hipStreamQuery(st);
         if (q == hipSuccess) break;  // stream drained: the word must be there now (checked below)
         if (q != hipErrorNotReady) QTR_HIP_TRY(h, q);
         (void)hipGetLastError();  // hipErrorNotReady is not an error of ours
@@ -702,7 +702,7 @@ static int wait_mail(qtr_handle* h, Slot& s, int idx, int seq) {
     if (payload_ok()) return QTR_OK;
     if ((spins & 0x3fff) == 0) {
       if (drained) break;  // the stream was idle one round ago and the payload still does not add up
-      const hipError_t q = hipStreamSynchronize(s.stream);
+      const hipError_t q = hipStreamSynchronize(st);
       if (q != hipSuccess) QTR_HIP_TRY(h, q);
       drained = true;
     }
@@ -712,71 +712,29 @@ static int wait_mail(qtr_handle* h, Slot& s, int idx, int seq) {
   return QTR_ERR_HIP;
 }
 
+// The stage times of the slot's last call, read off its events by the rows of its shape (stage_times.h).
 static void compute_times(Slot& s) {
-  if (!s.times_pending) return;
-  float ms = 0;
-  if (s.times_pending == 4) {  // the call ran with the stage events off: nothing was recorded
-    s.times = qtr_stage_times{};
-    fill_nn_times(s);
-    (void)hipGetLastError();
-    s.times_pending = 0;
-    return;
-  }
-  if (s.times_pending == 3) {  // qtr_feature_pair: the front end alone
-    (void)hipEventSynchronize(s.ev[7]);
-    s.times = qtr_stage_times{};
-    if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.times.voxelize = ms;
-    if (hipEventElapsedTime(&ms, s.ev[1], s.ev[6]) == hipSuccess) s.times.fpfh = ms;
-    if (hipEventElapsedTime(&ms, s.ev[6], s.ev[7]) == hipSuccess) s.times.match = ms;
-    if (hipEventElapsedTime(&ms, s.ev[0], s.ev[7]) == hipSuccess) s.times.total = ms;
-    fill_nn_times(s);
-    (void)hipGetLastError();
-    s.times_pending = 0;
-    return;
-  }
-  if (s.times_pending == 6) {  // qtr_register_pair_corr, back end beside the front end: graph / clique / solve were measured on
-    (void)hipEventSynchronize(s.ev_end);  // the third stream WHILE voxelize / fpfh / match ran: they add up to more than total
-    s.times = qtr_stage_times{};
-    if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.times.voxelize = ms;
-    if (hipEventElapsedTime(&ms, s.ev[1], s.ev[6]) == hipSuccess) s.times.fpfh = ms;
-    if (hipEventElapsedTime(&ms, s.ev[6], s.ev[7]) == hipSuccess) s.times.match = ms;
-    if (hipEventElapsedTime(&ms, s.ev_be0, s.ev[2]) == hipSuccess) s.times.graph = ms;
-    if (hipEventElapsedTime(&ms, s.ev[2], s.ev[3]) == hipSuccess) s.times.clique = ms;
-    if (hipEventElapsedTime(&ms, s.ev[3], s.ev[4]) == hipSuccess) s.times.solve = ms;
-    if (hipEventElapsedTime(&ms, s.ev[0], s.ev_end) == hipSuccess) s.times.total = ms;
-    fill_nn_times(s);
-    (void)hipGetLastError();
-    s.times_pending = 0;
-    return;
-  }
-  (void)hipEventSynchronize(s.ev[4]);
+  if (s.times_pending == TIMES_NONE) return;
+  static float qtr_stage_times::*const field[SF_COUNT] = {
+      &qtr_stage_times::voxelize, &qtr_stage_times::fpfh,  &qtr_stage_times::match, &qtr_stage_times::graph,
+      &qtr_stage_times::clique,   &qtr_stage_times::solve, &qtr_stage_times::total};
+  const ShapeTimes& sh = k_shape_times[s.times_pending];
+  if (sh.sync >= 0) (void)hipEventSynchronize(s.ev[sh.sync]);
   s.times = qtr_stage_times{};
-  if (s.times_pending == 1) {
-    if (hipEventElapsedTime(&ms, s.ev[1], s.ev[2]) == hipSuccess) s.times.graph = ms;
-  } else if (s.times_pending == 5) {  // qtr_register_keyframes: no voxel grid, no FPFH chain (both read 0); match = load + matcher
-    if (hipEventElapsedTime(&ms, s.ev[0], s.ev[7]) == hipSuccess) s.times.match = ms;
-    if (hipEventElapsedTime(&ms, s.ev[7], s.ev[2]) == hipSuccess) s.times.graph = ms;
-    fill_nn_times(s);
-  } else {
-    if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.times.voxelize = ms;
-    if (hipEventElapsedTime(&ms, s.ev[1], s.ev[6]) == hipSuccess) s.times.fpfh = ms;
-    if (hipEventElapsedTime(&ms, s.ev[6], s.ev[7]) == hipSuccess) s.times.match = ms;
-    if (hipEventElapsedTime(&ms, s.ev[7], s.ev[2]) == hipSuccess) s.times.graph = ms;
-    fill_nn_times(s);
-  }
-  if (hipEventElapsedTime(&ms, s.ev[2], s.ev[3]) == hipSuccess) s.times.clique = ms;
-  if (hipEventElapsedTime(&ms, s.ev[3], s.ev[4]) == hipSuccess) s.times.solve = ms;
-  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[4]) == hipSuccess) s.times.total = ms;
+  float ms = 0;
+  for (int r = 0; r < sh.nrows; ++r)
+    if (hipEventElapsedTime(&ms, s.ev[sh.rows[r].from], s.ev[sh.rows[r].to]) == hipSuccess) s.times.*field[sh.rows[r].field] = ms;
+  if (sh.nn) fill_nn_times(s);
   (void)hipGetLastError();
-  s.times_pending = 0;
+  s.times_pending = TIMES_NONE;
 }
 
-// the stage times of a call that is ONE stage: the slot's events 0 -> 1, into `field` (null: none) and the total
+// the stage times of a call that is ONE stage: EV_STAGE_BEGIN -> EV_STAGE_END, into `field` (null: none) and the total
 static void times_one_stage(Slot& s, float qtr_stage_times::*field) {
   float ms = 0;
-  s.times_pending = 0;
+  s.times_pending = TIMES_NONE;
   s.times = qtr_stage_times{};
-  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) != hipSuccess) return;
+  if (hipEventElapsedTime(&ms, s.ev[EV_STAGE_BEGIN], s.ev[EV_STAGE_END]) != hipSuccess) return;
   s.times.total = ms;
   if (field) s.times.*field = ms;
 }
@@ -855,7 +813,9 @@ static int check_max_corr(qtr_handle* h, int L) {
 // PMC_EXACT after the heuristic has finished (state `hs` = the device SolverState as the host last saw it): proves the
 // heuristic clique maximum or replaces it (exact.hip).  *improved tells the caller that st->mc / best_r / picks changed.
 // time_limit: Params::max_clique_time_limit of THIS call, seconds (reference include/quatro.hpp:267,800; <= 0: none).
-static int exact_phase(qtr_handle* h, Slot& s, int L, const SolverState& hs, bool* improved, double time_limit) {
+// Enqueued and waited for on `st`, the stream of the chain that left the state.
+static int exact_phase(qtr_handle* h, Slot& s, hipStream_t st, int L, const SolverState& hs, bool* improved,
+                       double time_limit) {
   *improved = false;
   s.exact_nodes = 0;
   s.exact_aborted = 0;
@@ -880,24 +840,24 @@ static int exact_phase(qtr_handle* h, Slot& s, int L, const SolverState& hs, boo
   }
   exact_carve(s.exb, s.ex_arena, depth_cap, nwaves);
   const long long ticks = time_limit > 0 ? (long long)(time_limit * 1e8) : 0;  // 100 MHz counter
-  hipLaunchKernelGGL(k_exact_init, dim3(1), dim3(1), 0, s.stream, s.sb.Kp, L, s.sb.st, s.exb.ctl);
-  exact_launch_search(s.sb, s.exb, L, depth_cap, nwaves, 0, ticks, s.stream, hs.t0, small_lds);
+  hipLaunchKernelGGL(k_exact_init, dim3(1), dim3(1), 0, st, s.sb.Kp, L, s.sb.st, s.exb.ctl);
+  exact_launch_search(s.sb, s.exb, L, depth_cap, nwaves, 0, ticks, st, hs.t0, small_lds);
   ExactCtl* hc = (ExactCtl*)(s.pinned_i32 + 192);
-  QTR_HIP_TRY(h, hipMemcpyAsync(hc, s.exb.ctl, sizeof(ExactCtl), hipMemcpyDeviceToHost, s.stream));
-  QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
+  QTR_HIP_TRY(h, hipMemcpyAsync(hc, s.exb.ctl, sizeof(ExactCtl), hipMemcpyDeviceToHost, st));
+  QTR_HIP_TRY(h, hipStreamSynchronize(st));
   s.exact_nodes = hc->nodes;
   if (hc->abort) {  // time limit: the heuristic clique stands (the reference returns PMC's best so far)
     s.exact_aborted = 1;
     return QTR_OK;
   }
   if (hc->gbest <= hs.mc) return QTR_OK;
-  QTR_HIP_TRY(h, hipMemsetAsync(s.exb.cliq, 0xff, (size_t)nwaves * (depth_cap + 2) * sizeof(int), s.stream));
-  hipLaunchKernelGGL(k_exact_phase_b, dim3(1), dim3(1), 0, s.stream, s.sb.Kp, L, s.exb.ctl);
-  exact_launch_search(s.sb, s.exb, L, depth_cap, nwaves, 1, ticks, s.stream, hs.t0, small_lds);
-  hipLaunchKernelGGL(k_exact_commit, dim3(1), dim3(256), 0, s.stream, s.exb.ctl, s.exb.cliq, nwaves, depth_cap, s.sb.st,
+  QTR_HIP_TRY(h, hipMemsetAsync(s.exb.cliq, 0xff, (size_t)nwaves * (depth_cap + 2) * sizeof(int), st));
+  hipLaunchKernelGGL(k_exact_phase_b, dim3(1), dim3(1), 0, st, s.sb.Kp, L, s.exb.ctl);
+  exact_launch_search(s.sb, s.exb, L, depth_cap, nwaves, 1, ticks, st, hs.t0, small_lds);
+  hipLaunchKernelGGL(k_exact_commit, dim3(1), dim3(256), 0, st, s.exb.ctl, s.exb.cliq, nwaves, depth_cap, s.sb.st,
                      s.sb.picks);
-  QTR_HIP_TRY(h, hipMemcpyAsync(hc, s.exb.ctl, sizeof(ExactCtl), hipMemcpyDeviceToHost, s.stream));
-  QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
+  QTR_HIP_TRY(h, hipMemcpyAsync(hc, s.exb.ctl, sizeof(ExactCtl), hipMemcpyDeviceToHost, st));
+  QTR_HIP_TRY(h, hipStreamSynchronize(st));
   s.exact_nodes += hc->nodes;
   if (hc->abort || hc->winner < 0) {
     s.exact_aborted = 1;
@@ -986,28 +946,28 @@ struct InFlight {
 
 // What follows the solver's mail for one pair (k_finalize left the record and the state in the slot's mailbox): more clique
 // rounds when the state says so (rare), PMC_EXACT's search and a second estimate when it found a larger clique.  Everything
-// is enqueued on `st`, and s.stream must BE `st` while this runs (wait_mail's liveness check and exact_phase look at it:
-// the batch lanes swap it); record_ev4: the end of each follow-up chain is the call's s.ev[4].
+// is enqueued on `st` and waited for there — the stream of the solver chain, which need not be the slot's own (a lane's, the
+// third stream); record_end: the end of each follow-up chain is the call's EV_SOLVE.
 static int solve_followup(qtr_handle* h, Slot& s, const float4* c_src, const float4* c_tgt, int L, const qtr_params* prm,
-                          hipStream_t st, bool record_ev4) {
+                          hipStream_t st, bool record_end) {
   if (L <= 0) return QTR_OK;
   const SolverState* ms = (const SolverState*)(s.mail + MAIL_SOLVER + 64);
   if (!ms->done) {
     s.sb.mail_seq = ++s.seq;
     QTR_HIP_TRY(h, solver_continue(s.sb, c_src, c_tgt, L, *prm, st, s.pinned_i32 + 128, ms->redo_cores));
-    if (record_ev4) QTR_HIP_TRY(h, hipEventRecord(s.ev[4], st));
-    QTR_TRY(wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq));
+    if (record_end) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_SOLVE], st));
+    QTR_TRY(wait_mail(h, s, st, MAIL_SEQ_SOLVE, s.seq));
   }
   if (prm->inlier_selection_mode != QTR_INLIER_PMC_EXACT) return QTR_OK;
   SolverState hs;
   memcpy(&hs, ms, sizeof(hs));
   bool improved = false;
-  QTR_TRY(exact_phase(h, s, L, hs, &improved, prm->max_clique_time_limit));
+  QTR_TRY(exact_phase(h, s, st, L, hs, &improved, prm->max_clique_time_limit));
   if (!improved) return QTR_OK;
   s.sb.mail_seq = ++s.seq;  // estimate again from the larger clique
   QTR_HIP_TRY(h, solver_refinalize(s.sb, c_src, c_tgt, L, *prm, st));
-  if (record_ev4) QTR_HIP_TRY(h, hipEventRecord(s.ev[4], st));
-  return wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq);
+  if (record_end) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_SOLVE], st));
+  return wait_mail(h, s, st, MAIL_SEQ_SOLVE, s.seq);
 }
 
 // the result record out of the slot's mailbox; the counts the front end wrote into *res stay
@@ -1047,32 +1007,44 @@ static int solve_device(qtr_handle* h, Slot& s, const float4* d_src, const float
   // k_hcore_async's workgroups have to be resident together: a chain that starts while another slot's is in flight (calls
   // from several threads) takes its share of the compute units only (solver.hip, solver_set_hca_share)
   InFlight in_flight(h);
-  QTR_HIP_TRY(h, solver_enqueue(s.sb, d_src, d_tgt, L, *prm, s.stream, s.pinned_i32, h->stage_events ? s.ev[2] : nullptr,
-                                h->stage_events ? s.ev[3] : nullptr, reset_done));
-  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[4], s.stream));
-  QTR_TRY(wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq));
+  QTR_HIP_TRY(h, solver_enqueue(s.sb, d_src, d_tgt, L, *prm, s.stream, h->stage_events ? s.ev[EV_GRAPH] : nullptr,
+                                h->stage_events ? s.ev[EV_CLIQUE] : nullptr, reset_done));
+  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_SOLVE], s.stream));
+  QTR_TRY(wait_mail(h, s, s.stream, MAIL_SEQ_SOLVE, s.seq));
   QTR_TRY(solve_followup(h, s, d_src, d_tgt, L, prm, s.stream, h->stage_events != 0));
   result_from_mail(s, res);
   return res->status;
 }
 
-static int copy_out_lists(qtr_handle* h, Slot& s, const qtr_result* res, int* clique, int* rot_inliers,
-                          int* final_inliers, int cap, int mem) {
+// One index list of a record to where the caller wants it, enqueued on `st`: QTR_ERR_CAPACITY when its n entries do not
+// fit `cap` (nothing is enqueued then); *copies counts the copies enqueued.
+static int list_out_enqueue(qtr_handle* h, int* dst, const int* src, int n, int cap, int mem, hipStream_t st, int* copies) {
+  if (!dst || n <= 0) return QTR_OK;
+  if (n > cap) return QTR_ERR_CAPACITY;
   const hipMemcpyKind kind = (mem == QTR_MEM_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  if (clique && res->n_clique > 0) {
-    if (res->n_clique > cap) return QTR_ERR_CAPACITY;
-    QTR_HIP_TRY(h, hipMemcpyAsync(clique, s.sb.clique, sizeof(int) * (size_t)res->n_clique, kind, s.stream));
-  }
-  if (rot_inliers && res->n_rot_inliers > 0) {
-    if (res->n_rot_inliers > cap) return QTR_ERR_CAPACITY;
-    QTR_HIP_TRY(h, hipMemcpyAsync(rot_inliers, s.sb.rot_inl, sizeof(int) * (size_t)res->n_rot_inliers, kind, s.stream));
-  }
-  if (final_inliers && res->n_final > 0) {
-    if (res->n_final > cap) return QTR_ERR_CAPACITY;
-    QTR_HIP_TRY(h, hipMemcpyAsync(final_inliers, s.sb.final_inl, sizeof(int) * (size_t)res->n_final, kind, s.stream));
-  }
-  QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
+  QTR_HIP_TRY(h, hipMemcpyAsync(dst, src, sizeof(int) * (size_t)n, kind, st));
+  ++*copies;
   return QTR_OK;
+}
+
+// The tail every blocking registration shares once its record is in *res (rc = its status): QTR_OK or
+// QTR_ERR_CLIQUE_TOO_SMALL goes on, anything else is returned as it is.  The call's shape for the stage times; the lists out
+// on `st`, complete on return, stopping at the first one that does not fit (it becomes the record's status).  (A lane marks
+// the pair, goes on with the next list and synchronises once for its group: lane_after_solve.)
+static int finish_registration(qtr_handle* h, Slot& s, int rc, TimesShape shape, qtr_result* res, int* clique,
+                               int* rot_inliers, int* final_inliers, int cap, int mem, hipStream_t st) {
+  if (rc != QTR_OK && rc != QTR_ERR_CLIQUE_TOO_SMALL) return rc;
+  s.times_pending = h->stage_events ? shape : TIMES_EVENTS_OFF;
+  auto lists_out = [&]() -> int {
+    int copies = 0;
+    QTR_TRY(list_out_enqueue(h, clique, s.sb.clique, res->n_clique, cap, mem, st, &copies));
+    QTR_TRY(list_out_enqueue(h, rot_inliers, s.sb.rot_inl, res->n_rot_inliers, cap, mem, st, &copies));
+    QTR_TRY(list_out_enqueue(h, final_inliers, s.sb.final_inl, res->n_final, cap, mem, st, &copies));
+    QTR_HIP_TRY(h, hipStreamSynchronize(st));
+    return QTR_OK;
+  };
+  const int rc2 = lists_out();
+  return rc2 != QTR_OK ? (res->status = rc2) : rc;
 }
 
 int qtr_solve(qtr_handle* h, int slot, const float* src4, const float* tgt4, int L, const qtr_params* prm,
@@ -1093,16 +1065,12 @@ int qtr_solve(qtr_handle* h, int slot, const float* src4, const float* tgt4, int
   // (an event record is a marker packet the queue has to retire before the next launch starts: with the stage events
   // off a call records none at all, and every field of qtr_stage_times reads 0)
   const bool ev_on = h->stage_events != 0;
-  if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev[0], s.stream));
+  if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_BEGIN], s.stream));
   QTR_TRY(corr_stage(h, s, src4, tgt4, L, mem, s.stream, &d_src, &d_tgt));
-  if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
+  if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGED], s.stream));
   res->n_corr = L;
   rc = solve_device(h, s, d_src, d_tgt, L, prm, res);
-  if (rc != QTR_OK && rc != QTR_ERR_CLIQUE_TOO_SMALL) return rc;
-  s.times_pending = ev_on ? 1 : 4;
-  const int rc2 = copy_out_lists(h, s, res, clique, rot_inliers, final_inliers, cap, mem);
-  if (rc2 != QTR_OK) return res->status = rc2;
-  return rc;
+  return finish_registration(h, s, rc, TIMES_SOLVE, res, clique, rot_inliers, final_inliers, cap, mem, s.stream);
 }
 
 int qtr_max_clique(qtr_handle* h, int slot, const unsigned long long* adj, int L, int mode, double kcore_thr,
@@ -1141,11 +1109,11 @@ int qtr_max_clique(qtr_handle* h, int slot, const unsigned long long* adj, int L
     SolverState hs;
     memcpy(&hs, s.pinned_i32 + 128, sizeof(hs));
     bool improved = false;
-    QTR_TRY(exact_phase(h, s, L, hs, &improved, time_limit));
+    QTR_TRY(exact_phase(h, s, s.stream, L, hs, &improved, time_limit));
   }
   s.sb.mail_seq = ++s.seq;
   QTR_HIP_TRY(h, clique_only_finish(s.sb, L, s.stream));
-  QTR_TRY(wait_mail(h, s, MAIL_SEQ_SOLVE, s.seq));
+  QTR_TRY(wait_mail(h, s, s.stream, MAIL_SEQ_SOLVE, s.seq));
   memcpy(s.pinned_res, s.mail + MAIL_SOLVER, sizeof(qtr_result));
   const int M = s.pinned_res->n_clique;
   if (max_core_out) *max_core_out = s.pinned_res->max_core;
@@ -1336,8 +1304,8 @@ void qtr_pw_default_params(qtr_pw_params* p) {  // reference config/patchwork_pa
 }
 
 // Ground segmentation of one scan in two halves, so that a batch can keep several slots' scans in flight: pw_begin
-// validates and enqueues (the two output counts follow the kernels into the slot's pinned words, s.ev[1] marks the end),
-// pw_end reads them once the stream has got there.
+// validates and enqueues (the two output counts follow the kernels into the slot's pinned words, EV_STAGE_END marks the
+// end), pw_end reads them once the stream has got there.
 static int pw_begin(qtr_handle* h, Slot& s, const float* xyz4, int P, const qtr_pw_params* pw, int mem) {
   if (!pw || P < 0 || (P > 0 && !xyz4)) return QTR_ERR_BAD_ARG;
   // check_input_parameters_are_correct (:588-614) + what the kernels rely on
@@ -1404,13 +1372,13 @@ static int pw_begin(qtr_handle* h, Slot& s, const float* xyz4, int P, const qtr_
     d.elevation_thr[i] = pw->elevation_thr[i];
     d.flatness_thr[i] = pw->flatness_thr[i];
   }
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[0], s.stream));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGE_BEGIN], s.stream));
   QTR_HIP_TRY(h, patchwork_enqueue(s.fb, s.pwb, d_in, P, d, s.stream));
   QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32, s.pwb.offs + 2 * 1024, 2 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGE_END], s.stream));
   return QTR_OK;
 }
-static void pw_end(Slot& s, int* n_ground, int* n_nonground) {  // (after s.ev[1] has completed)
+static void pw_end(Slot& s, int* n_ground, int* n_nonground) {  // (after s.ev[EV_STAGE_END] has completed)
   *n_ground = s.pinned_i32[0];
   *n_nonground = s.pinned_i32[1];
 }
@@ -1517,11 +1485,11 @@ static int seg_begin(qtr_handle* h, Slot& s, const float* xyz4, int P, const qtr
     qm_sincosf(ax, &d.sx, &d.cx);
     qm_sincosf(ay, &d.sy, &d.cy);
   }
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[0], s.stream));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGE_BEGIN], s.stream));
   int* d_tot = s.seg.blk + 3 * ((NP + 1023) / 1024 + 1);
   QTR_HIP_TRY(h, segment_enqueue(s.seg, d_in, P, d, d_tot, s.stream));
   QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32, d_tot, 3 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGE_END], s.stream));
   return QTR_OK;
 }
 
@@ -1620,14 +1588,14 @@ int qtr_voxelize(qtr_handle* h, int slot, const float* xyz4, int P, float leaf, 
     QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, xyz4, (size_t)P * 16, hipMemcpyHostToDevice, s.stream));
     d_in = s.in_src;
   }
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[0], s.stream));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGE_BEGIN], s.stream));
   CloudBufs& cb = s.fb.cloud[0];
   {
     const float4* raws[1] = {d_in};
     const int Ps[1] = {P};
     QTR_HIP_TRY(h, voxelize_enqueue(s.fb, 1, raws, Ps, leaf, s.stream));
   }
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGE_END], s.stream));
   QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32, cb.counts, 16 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
   QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
   const VoxVerdict v = vox_verdict(s.pinned_i32, P, h->lim.max_voxels);
@@ -1678,14 +1646,14 @@ int qtr_fpfh(qtr_handle* h, int slot, const float* xyz4, int n, float r_normal, 
   QTR_HIP_TRY(h, hipMemcpyAsync(cb.vox, xyz4, (size_t)n * 16, kin, s.stream));
   QTR_HIP_TRY(h, hipMemsetAsync(cb.counts, 0, 16 * sizeof(int), s.stream));
   QTR_HIP_TRY(h, set_count_enqueue(cb, CNT_NVOX, n, s.stream));
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[0], s.stream));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGE_BEGIN], s.stream));
   {
     const int ns1[1] = {n};
     // an arbitrary cloud (dense mode: no voxel grid in front): lists of any length
     QTR_TRY(ensure_long_arenas(h, s));
     QTR_HIP_TRY(h, fpfh_enqueue(s.fb, 0, 1, ns1, r_normal, r_fpfh, s.stream, true, false, true));
   }
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGE_END], s.stream));
   QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32, cb.counts, 16 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
   QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
   if (s.pinned_i32[CNT_NBR_CAPACITY]) {
@@ -1714,7 +1682,7 @@ static int match_device(qtr_handle* h, Slot& s, int ns, int nt, const qtr_fronte
   s.nn_pending = s.nn_timed_last;
   s.fb.mail_seq = ++s.seq;
   QTR_HIP_TRY(h, match_enqueue(s.fb, ns, nt, *fp, s.stream, init_done, prep_done, gather));
-  QTR_TRY(wait_mail(h, s, MAIL_SEQ_MATCH, s.seq));  // k_corr_compact2 left the counters in the mailbox
+  QTR_TRY(wait_mail(h, s, s.stream, MAIL_SEQ_MATCH, s.seq));  // k_corr_compact2 left the counters in the mailbox
   *L_out = s.mail[MAIL_MATCH + MC_NCORR];
   if (*L_out < 0) {  // a multi-workgroup compaction of the tail gave up waiting for a predecessor's count (match.hip)
     if (tolerate_tail) return QTR_OK;  // (nobody reads the matcher's list: the caller reports -1 as the matched count)
@@ -1747,7 +1715,7 @@ int qtr_match(qtr_handle* h, int slot, const float* xyz4_s, int n_s, const float
   QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[1].vox, xyz4_t, (size_t)n_t * 16, kin, s.stream));
   QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[0].fpfh, desc33_s, (size_t)n_s * 132, kin, s.stream));
   QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[1].fpfh, desc33_t, (size_t)n_t * 132, kin, s.stream));
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[0], s.stream));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGE_BEGIN], s.stream));
   {
     const int n2[2] = {n_s, n_t};  // Matcher::normalizePoints means of the two clouds handed in
     QTR_HIP_TRY(h, mean_enqueue(s.fb, 0, 2, n2, s.stream));
@@ -1755,7 +1723,7 @@ int qtr_match(qtr_handle* h, int slot, const float* xyz4_s, int n_s, const float
   int L = 0;
   int rc = match_device(h, s, n_s, n_t, fp, &L);
   if (rc != QTR_OK) return rc;
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGE_END], s.stream));
   *L_out = L;
   if (L > cap) {
     snprintf(h->err, sizeof(h->err), "L=%d exceeds output capacity %d", L, cap);
@@ -1775,8 +1743,6 @@ static int ensure_stream3(qtr_handle* h, Slot& s) {
   if (s.stream3) return QTR_OK;
   int prio_least = 0, prio_greatest = 0;
   QTR_HIP_TRY(h, hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-  if (!s.ev_be0) QTR_HIP_TRY(h, hipEventCreate(&s.ev_be0));
-  if (!s.ev_end) QTR_HIP_TRY(h, hipEventCreate(&s.ev_end));
   if (!s.ev_fork) QTR_HIP_TRY(h, hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming));
   if (!s.ev_join) QTR_HIP_TRY(h, hipEventCreateWithFlags(&s.ev_join, hipEventDisableTiming));
   if (prio_greatest != prio_least) QTR_HIP_TRY(h, hipStreamCreateWithPriority(&s.stream3, hipStreamNonBlocking, prio_least));
@@ -1804,7 +1770,7 @@ static int corr_early_enqueue(qtr_handle* h, Slot& s, CorrEarly& ce) {
   // writes the correspondences on qtr_slot_stream.  It still does: the third stream waits for the event front_device
   // recorded on s.stream at the call's start — earlier work on the slot, not this call's voxel stage.
   QTR_HIP_TRY(h, hipStreamWaitEvent(s.stream3, s.ev_fork, 0));
-  if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev_be0, s.stream3));
+  if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_BE0], s.stream3));
   QTR_TRY(corr_stage(h, s, ce.src, ce.tgt, ce.n, ce.mem, s.stream3, &ce.cs, &ce.ct));
   // (the slot's record of its last solve follows the solver's buffers, which this chain fills even when the front end
   // then fails and the call returns counts and status only; the serial order leaves it untouched on such a failure)
@@ -1813,9 +1779,89 @@ static int corr_early_enqueue(qtr_handle* h, Slot& s, CorrEarly& ce) {
   s.sb.mail_seq = ce.seq = ++s.seq;
   ce.in_flight.reset(new InFlight(h));
   // (the state's clean slate rides on the graph build, as in qtr_solve: the matcher's k_match_init leaves it alone)
-  QTR_HIP_TRY(h, solver_enqueue(s.sb, ce.cs, ce.ct, ce.n, *ce.prm, s.stream3, s.pinned_i32, ev_on ? s.ev[2] : nullptr,
-                                ev_on ? s.ev[3] : nullptr, false, true));
-  if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev[4], s.stream3));
+  QTR_HIP_TRY(h, solver_enqueue(s.sb, ce.cs, ce.ct, ce.n, *ce.prm, s.stream3, ev_on ? s.ev[EV_GRAPH] : nullptr,
+                                ev_on ? s.ev[EV_CLIQUE] : nullptr, false, true));
+  if (ev_on) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_SOLVE], s.stream3));
+  return QTR_OK;
+}
+
+// ---- what the pair path (front_device) and the one-cloud path (front_one_chain) share: nc = 2 or 1 clouds ----
+// the counts of a front end's nc clouds for a refusal's text: "a", or the pair's form of "a" and "b"
+struct CountsText {
+  char s[40];
+  CountsText(int nc, int a, int b, const char* pair_form = "%d / %d") { snprintf(s, sizeof(s), nc > 1 ? pair_form : "%d", a, b); }
+};
+
+// The voxel stage of nc clouds on the slot's stream, the radix passes of the voxel sort speculated (vox_passes_next): the
+// launch, behind() once per attempt right behind it (what the caller runs beside the stage), the wait for the nc voxel
+// mails.  k2_vox_centroids publishes the counters from its first block while other blocks may still be reading the raw
+// scans: a failed wait drains the stream before it hands the scans back to the caller (who may free them).
+extern "C++" {  // (a template, inside this file's extern "C")
+template <class Behind>
+static int voxel_stage(qtr_handle* h, Slot& s, int nc, const float4* const* raws, const int* P, const qtr_frontend_params* fp,
+                       Behind behind) {
+  for (int attempt = 0;; ++attempt) {
+    const int launched = s.fb.vox_passes;
+    const int vox_seq = s.fb.mail_seq = ++s.seq;  // (kept: behind() may take the next number)
+    QTR_HIP_TRY(h, voxelize_enqueue(s.fb, nc, raws, P, fp->voxel_size, s.stream, launched, fp->fpfh_radius * 1.001f));
+    QTR_TRY(behind());
+    int bits = 0;
+    for (int c = 0; c < nc; ++c) {
+      const int rc = wait_mail(h, s, s.stream, c ? MAIL_SEQ_VOX1 : MAIL_SEQ_VOX0, vox_seq);
+      if (rc != QTR_OK) {
+        (void)hipStreamSynchronize(s.stream);
+        return rc;
+      }
+      const int b = s.mail[(c ? MAIL_VOX1 : MAIL_VOX0) + CNT_SORT_BITS];
+      bits = c ? std::max(bits, b) : b;
+    }
+    if (!vox_passes_next(s.fb.vox_passes, s.fb.vox_fewer, bits, launched, attempt)) return QTR_OK;
+  }
+}
+}  // extern "C++"
+
+// The voxel stage's refusal from the verdicts of its nc clouds of P[] points, the reasons in vox_verdict's order (QTR_OK:
+// none).  empty_is_error: an empty result is one — a keyframe; the pair path does not look at it.  A refusal drains the
+// stream first, like a failed wait above.
+static int vox_refusal(qtr_handle* h, Slot& s, int nc, const VoxVerdict* v, const int* P, bool empty_is_error) {
+  auto any = [&](VoxReason r) { return v[0].reason == r || v[nc - 1].reason == r; };
+  int rc = QTR_OK;
+  if (any(VOX_TIMEOUT)) {
+    snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out");
+    rc = QTR_ERR_HIP;
+  } else if (any(VOX_PASS_TOO_LARGE)) {
+    snprintf(h->err, sizeof(h->err), "voxel grid would overflow int32 (leaf too small): the cloud passes through as it "
+             "is (pcl::VoxelGrid), and its %s points exceed max_voxels=%d", CountsText(nc, P[0], P[nc - 1]).s, h->lim.max_voxels);
+    rc = QTR_ERR_CAPACITY;
+  } else if (any(VOX_TOO_MANY)) {
+    snprintf(h->err, sizeof(h->err), "voxel count %s exceeds max_voxels=%d", CountsText(nc, v[0].n, v[nc - 1].n, "(%d,%d)").s,
+             h->lim.max_voxels);
+    rc = QTR_ERR_CAPACITY;
+  } else if (empty_is_error && any(VOX_EMPTY)) {
+    snprintf(h->err, sizeof(h->err), "Invalid or empty point cloud dataset given!");
+    rc = QTR_ERR_BAD_ARG;
+  }
+  if (rc != QTR_OK) (void)hipStreamSynchronize(s.stream);
+  return rc;
+}
+
+// The neighbour lists' refusal after an FPFH chain, from the counter lines of its nc clouds (lists_verdict).  *again: a
+// point has more than QTR_KMAX neighbours and the chain ran without k2_neighbors_big — from now on the handle's chains
+// include it, and the caller goes round again (its input is where it was: nothing of the chain writes it).
+static int lists_refusal(qtr_handle* h, int nc, const int* cnt0, const int* cnt1, bool* again) {
+  *again = false;
+  switch (lists_verdict(cnt0, nc > 1 ? cnt1 : nullptr, h->long_lists)) {
+    case LISTS_TILE_ERROR:
+      snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out in a tile (centroids incomplete)");
+      return QTR_ERR_HIP;
+    case LISTS_CAPACITY:
+      snprintf(h->err, sizeof(h->err), "radius-neighbour lists longer than %d entries (longest %s) exceed the long-list "
+               "arena: qtr_limits.max_long_neighbors is %d", QTR_KMAX,
+               CountsText(nc, cnt0[CNT_KMAX], nc > 1 ? cnt1[CNT_KMAX] : 0).s, h->lim.max_long_neighbors);
+      return QTR_ERR_CAPACITY;
+    case LISTS_NEED_LONG: h->long_lists = *again = true; break;
+    case LISTS_OK: break;
+  }
   return QTR_OK;
 }
 
@@ -1833,7 +1879,6 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
   // early (with corr_given, for_solver = false): that back end is enqueued HERE, on the third stream, behind the first voxel
   // stage's launches — after every check that returns with nothing in flight, and while the host would only wait for the
   // voxel mail.  The caller waits for its mail, joins the streams and drains the third one on an error return.
-  int rc = QTR_OK;
   if (fp->normal_radius > fp->fpfh_radius) {
     snprintf(h->err, sizeof(h->err), "[FPFHManager]: Normal should be lower than fpfh_radius!!!!");
     return QTR_ERR_BAD_ARG;
@@ -1858,68 +1903,40 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
     d_s = s.in_src;
     d_t = s.in_tgt;
   }
-  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[0], s.stream));
-  // k2_vox_centroids publishes the voxel counters from its first block while other blocks may still be reading the raw
-  // scans: an error return taken right after the mail must not hand the scans back to the caller (who may free them)
-  // before the stream has drained
-  auto fail_drained = [&](int code) {
-    (void)hipStreamSynchronize(s.stream);
-    return code;
-  };
+  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_BEGIN], s.stream));
   // both clouds go through every front-end kernel together (blockIdx.y = cloud)
-  {
-    const float4* raws[2] = {d_s, d_t};
-    const int Ps2[2] = {Ps, Pt};
-    for (int attempt = 0;; ++attempt) {  // (the voxel sort's radix passes are speculated: vox_passes_next)
-      const int launched = s.fb.vox_passes;
-      const int vox_seq = s.fb.mail_seq = ++s.seq;  // (kept: the back end enqueued below takes the next number)
-      QTR_HIP_TRY(h, voxelize_enqueue(s.fb, 2, raws, Ps2, fp->voxel_size, s.stream, launched, fp->fpfh_radius * 1.001f));
-      // block 0 of k2_vox_centroids publishes the counters while other blocks are still writing centroids: anything
-      // that reads the centroids from another stream has to wait for the kernel itself
-      QTR_HIP_TRY(h, hipEventRecord(s.ev_vox, s.stream));
-      // The matcher's sequential means (70 us of one dependent chain per cloud: as long as the whole FPFH chain since round
-      // 6's cuts) start right behind the centroids, on the second stream, with the voxel counts read on the device — not
-      // after the mail, the host's checks and the FPFH chain's ten launches.
-      {
-        const int on_device[2] = {-1, -1};
-        QTR_HIP_TRY(h, hipStreamWaitEvent(s.stream2, s.ev_vox, 0));
-        QTR_HIP_TRY(h, mean_enqueue(s.fb, 0, 2, on_device, s.stream2, h->lim.max_voxels));
-      }
-      if (early && !early->enqueued) QTR_TRY(corr_early_enqueue(h, s, *early));
-      // k2_vox_centroids leaves both clouds' counters in the mailbox
-      if ((rc = wait_mail(h, s, MAIL_SEQ_VOX0, vox_seq)) != QTR_OK || (rc = wait_mail(h, s, MAIL_SEQ_VOX1, vox_seq)) != QTR_OK)
-        return fail_drained(rc);
-      const int bits = std::max(s.mail[MAIL_VOX0 + CNT_SORT_BITS], s.mail[MAIL_VOX1 + CNT_SORT_BITS]);
-      if (!vox_passes_next(s.fb.vox_passes, s.fb.vox_fewer, bits, launched, attempt)) break;
-    }
-  }
+  const float4* raws[2] = {d_s, d_t};
+  const int P2[2] = {Ps, Pt};
+  auto beside_voxels = [&]() -> int {
+    // block 0 of k2_vox_centroids publishes the counters while other blocks are still writing centroids: anything
+    // that reads the centroids from another stream has to wait for the kernel itself
+    QTR_HIP_TRY(h, hipEventRecord(s.ev_vox, s.stream));
+    // The matcher's sequential means (70 us of one dependent chain per cloud: as long as the whole FPFH chain since round
+    // 6's cuts) start right behind the centroids, on the second stream, with the voxel counts read on the device — not
+    // after the mail, the host's checks and the FPFH chain's ten launches.
+    const int on_device[2] = {-1, -1};
+    QTR_HIP_TRY(h, hipStreamWaitEvent(s.stream2, s.ev_vox, 0));
+    QTR_HIP_TRY(h, mean_enqueue(s.fb, 0, 2, on_device, s.stream2, h->lim.max_voxels));
+    if (early && !early->enqueued) QTR_TRY(corr_early_enqueue(h, s, *early));
+    return QTR_OK;
+  };
+  QTR_TRY(voxel_stage(h, s, 2, raws, P2, fp, beside_voxels));
   // (a cloud that passes through is BASELINE's dense mode — "no voxel downsample" — through the whole-path entry; an empty
   // voxel result is not looked at on this path)
-  const VoxVerdict vs = vox_verdict(s.mail + MAIL_VOX0, Ps, h->lim.max_voxels),
-                   vt = vox_verdict(s.mail + MAIL_VOX1, Pt, h->lim.max_voxels);
+  const VoxVerdict v2[2] = {vox_verdict(s.mail + MAIL_VOX0, Ps, h->lim.max_voxels),
+                            vox_verdict(s.mail + MAIL_VOX1, Pt, h->lim.max_voxels)};
+  QTR_TRY(vox_refusal(h, s, 2, v2, P2, false));
+  const VoxVerdict &vs = v2[0], &vt = v2[1];
   const int ns = vs.n, nt = vt.n;
   const bool passed_through = vs.passed || vt.passed;
-  if (vs.reason == VOX_TIMEOUT || vt.reason == VOX_TIMEOUT) {
-    snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out");
-    return fail_drained(QTR_ERR_HIP);
-  }
-  if (vs.reason == VOX_PASS_TOO_LARGE || vt.reason == VOX_PASS_TOO_LARGE) {
-    snprintf(h->err, sizeof(h->err), "voxel grid would overflow int32 (leaf too small): the cloud passes through as it "
-             "is (pcl::VoxelGrid), and its %d / %d points exceed max_voxels=%d", Ps, Pt, h->lim.max_voxels);
-    return fail_drained(QTR_ERR_CAPACITY);
-  }
   if (vs.passed) QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[0].vox, d_s, (size_t)Ps * 16, hipMemcpyDeviceToDevice, s.stream));
   if (vt.passed) QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[1].vox, d_t, (size_t)Pt * 16, hipMemcpyDeviceToDevice, s.stream));
   if (passed_through) QTR_HIP_TRY(h, hipEventRecord(s.ev_vox, s.stream));  // (the second stream's means wait for the clouds)
-  if (vs.reason == VOX_TOO_MANY || vt.reason == VOX_TOO_MANY) {
-    snprintf(h->err, sizeof(h->err), "voxel count (%d,%d) exceeds max_voxels=%d", ns, nt, h->lim.max_voxels);
-    return fail_drained(QTR_ERR_CAPACITY);
-  }
   *ns_out = ns;
   *nt_out = nt;
   s.last_ns = ns;
   s.last_nt = nt;
-  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
+  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_VOX], s.stream));
   {
     const int n2[2] = {ns, nt};
     // Beside the FPFH chain, on the second stream: the matcher's sequential means (already running: enqueued behind the
@@ -1936,38 +1953,27 @@ static int front_device(qtr_handle* h, Slot& s, const float* src_raw4, int Ps, c
     // (the solver's clean slate rides in the matcher's: one launch fewer beside the FPFH chain)
     QTR_HIP_TRY(h, match_init_enqueue(s.fb, ns, nt, *fp, s.stream2, false, for_solver ? (int*)s.sb.st : nullptr,
                                       (int)(sizeof(SolverState) / 4)));
-    QTR_HIP_TRY(h, hipEventRecord(s.ev[5], s.stream2));
-    QTR_HIP_TRY(h, hipStreamWaitEvent(s.stream, s.ev[5], 0));
+    QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_JOIN2], s.stream2));
+    QTR_HIP_TRY(h, hipStreamWaitEvent(s.stream, s.ev[EV_JOIN2], 0));
   }
-  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[6], s.stream));
+  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_FPFH], s.stream));
   int L = 0;
   // (with the back end beside this chain the matcher's tail does not gather its matched clouds: nobody reads them, and
   // host correspondences are staged in m_src / m_tgt while it runs)
-  rc = match_device(h, s, ns, nt, fp, &L, true, true, corr_given, early == nullptr);
-  if (rc != QTR_OK) return rc;
-  switch (lists_verdict(s.mail + MAIL_CNT0, s.mail + MAIL_CNT1, h->long_lists)) {  // (the matcher's tail mails the lines)
-    case LISTS_TILE_ERROR:
-      snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out in a tile (centroids incomplete)");
-      return QTR_ERR_HIP;
-    case LISTS_CAPACITY:
-      snprintf(h->err, sizeof(h->err), "radius-neighbour lists longer than %d entries (longest %d / %d) exceed the long-list "
-               "arena: qtr_limits.max_long_neighbors is %d", QTR_KMAX, s.mail[MAIL_CNT0 + CNT_KMAX],
-               s.mail[MAIL_CNT1 + CNT_KMAX], h->lim.max_long_neighbors);
-      return QTR_ERR_CAPACITY;
-    case LISTS_NEED_LONG:  // from now on the handle's chains include k2_neighbors_big; this pair goes round again
-      h->long_lists = true;
-      return front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem, for_solver, ns_out, nt_out, L_out, corr_given, early);
-    case LISTS_OK: break;
-  }
+  QTR_TRY(match_device(h, s, ns, nt, fp, &L, true, true, corr_given, early == nullptr));
+  bool again = false;
+  QTR_TRY(lists_refusal(h, 2, s.mail + MAIL_CNT0, s.mail + MAIL_CNT1, &again));  // (the matcher's tail mails the lines)
+  if (again)  // (the early back end is not enqueued a second time: CorrEarly::enqueued)
+    return front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem, for_solver, ns_out, nt_out, L_out, corr_given, early);
   *L_out = L;
   if (corr_given) {
-    if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[7], s.stream));  // (stage times: the matcher's end)
+    if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_MATCH], s.stream));  // (stage times: the matcher's end)
     return QTR_OK;
   }
   s.last_L = L;
   QTR_TRY(check_max_corr(h, L));
   QTR_HIP_TRY(h, gather_matched_enqueue(s.fb, L, s.m_src, s.m_tgt, s.stream));
-  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[7], s.stream));
+  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_MATCH], s.stream));
   return QTR_OK;
 }
 
@@ -1994,12 +2000,7 @@ static int register_pair_impl(qtr_handle* h, Slot& s, const float* src_raw4, int
   const bool given = n_corr >= 0;
   int L = 0;
   if (given && h->corr_overlap) {
-    CorrEarly ce;
-    ce.src = corr_src;
-    ce.tgt = corr_tgt;
-    ce.n = n_corr;
-    ce.mem = mem_out;
-    ce.prm = prm;
+    CorrEarly ce{corr_src, corr_tgt, n_corr, mem_out, prm};
     int rc = front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem_in, false, &res->n_src, &res->n_tgt, &L, true, &ce);
     if (n_matched) *n_matched = L;
     res->n_corr = n_corr;
@@ -2013,18 +2014,9 @@ static int register_pair_impl(qtr_handle* h, Slot& s, const float* src_raw4, int
         if (armed) (void)hipStreamSynchronize(st);
       }
     } drain{s.stream3};
-    // from here on the third stream's work is waited for and watched there (wait_mail's liveness check, exact_phase)
-    struct StreamSwap {
-      Slot& s;
-      hipStream_t keep;
-      StreamSwap(Slot& s_, hipStream_t st) : s(s_), keep(s_.stream) { s.stream = st; }
-      ~StreamSwap() { s.stream = keep; }
-    };
-    if (rc == QTR_OK) {
-      StreamSwap on_stream3(s, s.stream3);
-      rc = wait_mail(h, s, MAIL_SEQ_SOLVE, ce.seq);
-      if (rc == QTR_OK) rc = solve_followup(h, s, ce.cs, ce.ct, n_corr, prm, s.stream3, h->stage_events != 0);
-    }
+    // the third stream's work is waited for and watched there
+    if (rc == QTR_OK) rc = wait_mail(h, s, s.stream3, MAIL_SEQ_SOLVE, ce.seq);
+    if (rc == QTR_OK) rc = solve_followup(h, s, ce.cs, ce.ct, n_corr, prm, s.stream3, h->stage_events != 0);
     if (rc != QTR_OK) {
       // The front end failed behind the back end's enqueue (capacity, a look-back timeout, the long-list arena), or a wait
       // did: today's record — counts and status — and nothing of the solver.  The abandoned chain drains before the
@@ -2037,12 +2029,10 @@ static int register_pair_impl(qtr_handle* h, Slot& s, const float* src_raw4, int
     // the next call on the slot, qtr_refine_pair and device outputs are ordered on s.stream: it sees the finished back end
     QTR_HIP_TRY(h, hipEventRecord(s.ev_join, s.stream3));
     QTR_HIP_TRY(h, hipStreamWaitEvent(s.stream, s.ev_join, 0));
-    if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev_end, s.stream));
-    if (rc != QTR_OK && rc != QTR_ERR_CLIQUE_TOO_SMALL) return rc;
-    s.times_pending = h->stage_events ? 6 : 4;
-    const int rc2 = copy_out_lists(h, s, res, clique, nullptr, final_inliers, cap, mem_out);
-    if (rc2 != QTR_OK) return res->status = rc2;
-    drain.armed = false;  // (copy_out_lists synchronised s.stream, which waited for the join)
+    if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_END], s.stream));
+    rc = finish_registration(h, s, rc, TIMES_PAIR_OVERLAP, res, clique, nullptr, final_inliers, cap, mem_out, s.stream);
+    // (a record whose lists are out has synchronised s.stream, which waited for the join)
+    drain.armed = rc != QTR_OK && rc != QTR_ERR_CLIQUE_TOO_SMALL;
     return rc;
   }
   int rc = front_device(h, s, src_raw4, Ps, tgt_raw4, Pt, fp, mem_in, true, &res->n_src, &res->n_tgt, &L, given);
@@ -2052,11 +2042,7 @@ static int register_pair_impl(qtr_handle* h, Slot& s, const float* src_raw4, int
   const float4 *cs = s.m_src, *ct = s.m_tgt;
   if (given) QTR_TRY(corr_stage(h, s, corr_src, corr_tgt, n_corr, mem_out, s.stream, &cs, &ct));
   rc = solve_device(h, s, cs, ct, res->n_corr, prm, res, true);
-  if (rc != QTR_OK && rc != QTR_ERR_CLIQUE_TOO_SMALL) return rc;
-  s.times_pending = h->stage_events ? 2 : 4;
-  const int rc2 = copy_out_lists(h, s, res, clique, nullptr, final_inliers, cap, mem_out);
-  if (rc2 != QTR_OK) return res->status = rc2;
-  return rc;
+  return finish_registration(h, s, rc, TIMES_PAIR, res, clique, nullptr, final_inliers, cap, mem_out, s.stream);
 }
 
 int qtr_register_pair(qtr_handle* h, int slot, const float* src_raw4, int Ps, const float* tgt_raw4, int Pt,
@@ -2111,7 +2097,7 @@ int qtr_feature_pair(qtr_handle* h, int slot, const float* src_raw4, int Ps, con
   if (n_tgt) *n_tgt = nt;
   *L_out = L;
   if (rc != QTR_OK) return rc;
-  s.times_pending = h->stage_events ? 3 : 4;
+  s.times_pending = h->stage_events ? TIMES_FRONT : TIMES_EVENTS_OFF;
   if ((src_kps4 || tgt_kps4 || corr2) && L > cap) {
     snprintf(h->err, sizeof(h->err), "L=%d exceeds output capacity %d", L, cap);
     return QTR_ERR_CAPACITY;
@@ -2154,36 +2140,10 @@ static int front_one_check(qtr_handle* h, bool have_cloud, int P, const qtr_fron
 // the gathered voxels of a merge): front_one_check passed and the device is set.
 static int front_one_chain(qtr_handle* h, Slot& s, const float4* d_raw, int P, const qtr_frontend_params* fp, int* n_out,
                            int* passed_out) {
-  int rc = QTR_OK;
-  auto fail_drained = [&](int code) {  // (the scan is not handed back while a kernel may still read it)
-    (void)hipStreamSynchronize(s.stream);
-    return code;
-  };
-  for (int attempt = 0;; ++attempt) {  // (the voxel sort's radix passes are speculated: vox_passes_next)
-    const int launched = s.fb.vox_passes;
-    s.fb.mail_seq = ++s.seq;
-    QTR_HIP_TRY(h, voxelize_enqueue(s.fb, 1, &d_raw, &P, fp->voxel_size, s.stream, launched, fp->fpfh_radius * 1.001f));
-    if ((rc = wait_mail(h, s, MAIL_SEQ_VOX0, s.seq)) != QTR_OK) return fail_drained(rc);
-    if (!vox_passes_next(s.fb.vox_passes, s.fb.vox_fewer, s.mail[MAIL_VOX0 + CNT_SORT_BITS], launched, attempt)) break;
-  }
+  QTR_TRY(voxel_stage(h, s, 1, &d_raw, &P, fp, [] { return (int)QTR_OK; }));
   const VoxVerdict v = vox_verdict(s.mail + MAIL_VOX0, P, h->lim.max_voxels);
+  QTR_TRY(vox_refusal(h, s, 1, &v, &P, true));
   const int n = v.n;
-  switch (v.reason) {
-    case VOX_TIMEOUT:
-      snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out");
-      return fail_drained(QTR_ERR_HIP);
-    case VOX_PASS_TOO_LARGE:
-      snprintf(h->err, sizeof(h->err), "voxel grid would overflow int32 (leaf too small): the cloud passes through as it "
-               "is (pcl::VoxelGrid), and its %d points exceed max_voxels=%d", P, h->lim.max_voxels);
-      return fail_drained(QTR_ERR_CAPACITY);
-    case VOX_TOO_MANY:
-      snprintf(h->err, sizeof(h->err), "voxel count %d exceeds max_voxels=%d", n, h->lim.max_voxels);
-      return fail_drained(QTR_ERR_CAPACITY);
-    case VOX_EMPTY:
-      snprintf(h->err, sizeof(h->err), "Invalid or empty point cloud dataset given!");
-      return fail_drained(QTR_ERR_BAD_ARG);
-    case VOX_OK: break;
-  }
   if (v.passed) QTR_HIP_TRY(h, hipMemcpyAsync(s.fb.cloud[0].vox, d_raw, (size_t)P * 16, hipMemcpyDeviceToDevice, s.stream));
   s.last_ns = s.last_n = n;
   s.last_nt = 0;
@@ -2194,19 +2154,9 @@ static int front_one_chain(qtr_handle* h, Slot& s, const float4* d_raw, int P, c
                               cell_table_cells(ncell, ncell)));
   QTR_HIP_TRY(h, hipMemcpyAsync(s.pinned_i32, s.fb.cloud[0].counts, 16 * sizeof(int), hipMemcpyDeviceToHost, s.stream));
   QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
-  switch (lists_verdict(s.pinned_i32, nullptr, h->long_lists)) {
-    case LISTS_TILE_ERROR:
-      snprintf(h->err, sizeof(h->err), "voxel grid: look-back timed out in a tile (centroids incomplete)");
-      return QTR_ERR_HIP;
-    case LISTS_CAPACITY:
-      snprintf(h->err, sizeof(h->err), "radius-neighbour lists longer than %d entries (longest %d) exceed the long-list "
-               "arena: qtr_limits.max_long_neighbors is %d", QTR_KMAX, s.pinned_i32[CNT_KMAX], h->lim.max_long_neighbors);
-      return QTR_ERR_CAPACITY;
-    case LISTS_NEED_LONG:  // (the input is where it was: nothing of the chain writes it)
-      h->long_lists = true;
-      return front_one_chain(h, s, d_raw, P, fp, n_out, passed_out);
-    case LISTS_OK: break;
-  }
+  bool again = false;
+  QTR_TRY(lists_refusal(h, 1, s.pinned_i32, nullptr, &again));
+  if (again) return front_one_chain(h, s, d_raw, P, fp, n_out, passed_out);
   *n_out = n;
   *passed_out = v.passed ? 1 : 0;
   return QTR_OK;
@@ -2265,7 +2215,7 @@ int qtr_keyframe_create(qtr_handle* h, int slot, const float* raw4, int P, const
   Slot* sp = get_slot(h, slot);
   if (!sp || !fp || !out) return QTR_ERR_BAD_ARG;
   Slot& s = *sp;
-  s.times_pending = 0;
+  s.times_pending = TIMES_NONE;
   int n = 0, passed = 0;
   QTR_TRY(front_one_device(h, s, raw4, P, fp, mem, &n, &passed));
   return keyframe_pack(h, s, fp, P, n, passed, out);
@@ -2279,7 +2229,7 @@ int qtr_keyframe_merge(qtr_handle* h, int slot, const qtr_keyframe* const* kfs, 
   Slot* sp = get_slot(h, slot);
   if (!sp || !fp || !out) return QTR_ERR_BAD_ARG;
   Slot& s = *sp;
-  s.times_pending = 0;
+  s.times_pending = TIMES_NONE;
   if (K < 1 || K > QTR_SUBMAP_MAX_KEYFRAMES || !kfs) {
     snprintf(h->err, sizeof(h->err), "keyframe merge: %d members (1 .. %d)", K, QTR_SUBMAP_MAX_KEYFRAMES);
     return QTR_ERR_BAD_ARG;
@@ -2670,7 +2620,7 @@ int qtr_register_keyframes(qtr_handle* h, int slot, const qtr_keyframe* kf_src, 
   const int ns = kf_src->info.n_voxels, nt = kf_tgt->info.n_voxels;
   res->n_src = s.last_ns = ns;
   res->n_tgt = s.last_nt = nt;
-  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[0], s.stream));
+  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_BEGIN], s.stream));
   // the matcher's clean slate first — it clears the duplicate tables the load fills, and the solver's state rides in it —
   // then ONE launch for both clouds; the matcher starts at its operand tables (init_done, prep_done)
   QTR_HIP_TRY(h, match_init_enqueue(s.fb, ns, nt, *fp, s.stream, true, (int*)s.sb.st, (int)(sizeof(SolverState) / 4)));
@@ -2682,12 +2632,9 @@ int qtr_register_keyframes(qtr_handle* h, int slot, const qtr_keyframe* kf_src, 
   s.last_L = L;
   if ((rc = check_max_corr(h, L)) != QTR_OK) return res->status = rc;
   QTR_HIP_TRY(h, gather_matched_enqueue(s.fb, L, s.m_src, s.m_tgt, s.stream));
-  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[7], s.stream));
+  if (h->stage_events) QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_MATCH], s.stream));
   rc = solve_device(h, s, s.m_src, s.m_tgt, L, prm, res, true);
-  if (rc != QTR_OK && rc != QTR_ERR_CLIQUE_TOO_SMALL) return rc;
-  s.times_pending = h->stage_events ? 5 : 4;
-  const int rc2 = copy_out_lists(h, s, res, clique, nullptr, final_inliers, cap, QTR_MEM_HOST);
-  if (rc2 != QTR_OK) return res->status = rc2;
+  rc = finish_registration(h, s, rc, TIMES_KEYFRAMES, res, clique, nullptr, final_inliers, cap, QTR_MEM_HOST, s.stream);
   mark_registration(s, rc, res);
   return rc;
 }
@@ -2825,7 +2772,7 @@ static int lane_preprocess(qtr_handle* h, Lane& ln, std::vector<PreScan>& pre) {
         q.stage = 1;
         moved = true;
       } else {
-        const hipError_t e = hipEventQuery(s.ev[1]);
+        const hipError_t e = hipEventQuery(s.ev[EV_STAGE_END]);
         if (e == hipErrorNotReady) continue;
         if (e != hipSuccess) {
           snprintf(h->err, sizeof(h->err), "batch pre-processing: %s", hipGetErrorString(e));
@@ -2850,8 +2797,8 @@ static int lane_preprocess(qtr_handle* h, Lane& ln, std::vector<PreScan>& pre) {
             q.stage = 0;
           } else {
             if (rc == QTR_OK) {  // the group's chain (lane stream) reads the staging buffers: it waits for this slot
-              QTR_HIP_TRY(h, hipEventRecord(s.ev[1], s.stream));
-              QTR_HIP_TRY(h, hipStreamWaitEvent(lead.stream, s.ev[1], 0));
+              QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_STAGE_END], s.stream));
+              QTR_HIP_TRY(h, hipStreamWaitEvent(lead.stream, s.ev[EV_STAGE_END], 0));
             }
             q.stage = 3;
             --open;
@@ -2925,7 +2872,7 @@ static int lane_start_chunk(qtr_handle* h, Lane& ln) {
       batch_fail_pair(h, ln.first_pair + g, QTR_ERR_CAPACITY);
       continue;
     }
-    s.times_pending = 0;
+    s.times_pending = TIMES_NONE;
     if (J.kf) {  // a keyframe pair (validated at submission): no voxel chain — the load and the matcher follow the loop
       const qtr_keyframe *ks = (const qtr_keyframe*)pd.src_raw4, *kt = (const qtr_keyframe*)pd.tgt_raw4;
       r.n_src = ln.ns[g] = s.last_ns = ks->info.n_voxels;
@@ -3199,7 +3146,7 @@ static int lane_after_voxels(qtr_handle* h, Lane& ln) {
   if (passed_through) QTR_HIP_TRY(h, hipEventRecord(lead.ev_vox, lead.stream));
   QTR_HIP_TRY(h, hipStreamWaitEvent(lead.stream2, lead.ev_vox, 0));
   QTR_HIP_TRY(h, mean_enqueue_group(F.data(), G, n2.data(), &ln.stage, lead.stream2));  // beside the FPFH chain
-  QTR_HIP_TRY(h, hipEventRecord(lead.ev[5], lead.stream2));
+  QTR_HIP_TRY(h, hipEventRecord(lead.ev[EV_JOIN2], lead.stream2));
   ln.long_lists = h->long_lists;
   if (ln.long_lists)
     for (int g : ln.active) QTR_TRY(ensure_long_arenas(h, h->slots[ln.first_slot + g]));
@@ -3211,7 +3158,7 @@ static int lane_after_voxels(qtr_handle* h, Lane& ln) {
   }
   QTR_HIP_TRY(h, fpfh_enqueue_group(F.data(), G, n2.data(), J.fp.normal_radius, J.fp.fpfh_radius, &ln.stage, lead.stream,
                                     ln.long_lists, true, max_ncell));
-  QTR_HIP_TRY(h, hipStreamWaitEvent(lead.stream, lead.ev[5], 0));
+  QTR_HIP_TRY(h, hipStreamWaitEvent(lead.stream, lead.ev[EV_JOIN2], 0));
   for (int g : ln.active) {
     Slot& s = h->slots[ln.first_slot + g];
     s.fb.mail_seq = ++s.seq;
@@ -3296,39 +3243,21 @@ static int lane_after_match(qtr_handle* h, Lane& ln) {
 static int lane_after_solve(qtr_handle* h, Lane& ln) {
   BatchJob& J = h->job;
   Slot& lead = h->slots[ln.first_slot];
-  bool copies = false;
+  int copies = 0;
   for (int g : ln.active) {
     Slot& s = h->slots[ln.first_slot + g];
     const int pair = ln.first_pair + g;
     qtr_result& r = J.results[pair];
     const qtr_pair_desc& pd = J.pairs[pair];
-    // Follow-up work of ONE pair of the group runs on the lane's stream (the lane's chain owns the slot's arenas), and
-    // everything that waits for it — wait_mail's liveness check, exact_phase's enqueues — must look at THAT stream:
-    // the slot's own stream is idle, so a wait that queries it gives up before the kernels have run.
-    struct StreamSwap {
-      Slot& s;
-      hipStream_t keep;
-      StreamSwap(Slot& s_, hipStream_t st) : s(s_), keep(s_.stream) { s.stream = st; }
-      ~StreamSwap() { s.stream = keep; }
-    } on_lane_stream(s, lead.stream);
+    // Follow-up work of ONE pair of the group runs on the lane's stream (the lane's chain owns the slot's arenas) and is
+    // waited for there: the slot's own stream is idle.
     QTR_TRY(solve_followup(h, s, ln.csrc[g], ln.ctgt[g], ln.L[g], &J.prm, lead.stream, false));
     result_from_mail(s, &r);
-    // (not copy_out_lists: an overflow marks the pair and the lane goes on, and the lane synchronises once)
-    const hipMemcpyKind kind = (J.mem == QTR_MEM_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (pd.clique && r.n_clique > 0) {
-      if (r.n_clique > pd.cap) r.status = QTR_ERR_CAPACITY;
-      else {
-        QTR_HIP_TRY(h, hipMemcpyAsync(pd.clique, s.sb.clique, sizeof(int) * (size_t)r.n_clique, kind, lead.stream));
-        copies = true;
-      }
-    }
-    if (pd.final_inliers && r.n_final > 0) {
-      if (r.n_final > pd.cap) r.status = QTR_ERR_CAPACITY;
-      else {
-        QTR_HIP_TRY(h, hipMemcpyAsync(pd.final_inliers, s.sb.final_inl, sizeof(int) * (size_t)r.n_final, kind, lead.stream));
-        copies = true;
-      }
-    }
+    // (not finish_registration's way: a list that does not fit marks the pair, the lane goes on and synchronises once)
+    const int rc_c = list_out_enqueue(h, pd.clique, s.sb.clique, r.n_clique, pd.cap, J.mem, lead.stream, &copies);
+    const int rc_f = list_out_enqueue(h, pd.final_inliers, s.sb.final_inl, r.n_final, pd.cap, J.mem, lead.stream, &copies);
+    if (rc_c == QTR_ERR_HIP || rc_f == QTR_ERR_HIP) return QTR_ERR_HIP;
+    if (rc_c != QTR_OK || rc_f != QTR_OK) r.status = QTR_ERR_CAPACITY;
     J.finished[pair] = 1;
     ++J.done;
   }
@@ -3580,8 +3509,8 @@ static int check_icp_params(qtr_handle* h, const qtr_icp_params* p) {
 // The single-call loop on the slot's ICP arena, which icp_device and the voxel map's registration (voxelmap.hip) share: the
 // empty result, the slot's debug / timing fields, then - unless `empty`: there is nothing to refine - bind() (the caller's
 // checks, reservations and view), before(&go) (what precedes the loop and ends with the initial state on the device, between
-// ev[0] and ev[1]; go = false: nothing to refine after all), launch(v) per iteration with no host read-back inside a block
-// of QTR_ICP_BLOCK launches (0: all max_iterations of them in one go), the final read-back, the result and the times.
+// EV_ICP_BEGIN and EV_ICP_GRID; go = false: nothing to refine after all), launch(v) per iteration with no host read-back inside
+// a block of QTR_ICP_BLOCK launches (0: all max_iterations of them in one go), the final read-back, the result and the times.
 extern "C++" {  // (a template, inside this file's extern "C")
 template <class Bind, class Before, class Launch>
 static int icp_loop(qtr_handle* h, Slot& s, int ns, bool empty, const double* guess, const qtr_icp_params* prm,
@@ -3596,11 +3525,11 @@ static int icp_loop(qtr_handle* h, Slot& s, int ns, bool empty, const double* gu
   IcpBufs& B = s.icp;
   const IcpView& v = B.v;
   const hipStream_t st = s.stream;
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[0], st));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_ICP_BEGIN], st));
   bool go = true;
   QTR_TRY(before(&go));
   if (!go) return QTR_OK;
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[1], st));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_ICP_GRID], st));
   const int block = h->icp_block > 0 ? h->icp_block : prm->max_iterations;
   for (int it = 0; it < prm->max_iterations;) {
     const int m = std::min(block, prm->max_iterations - it);
@@ -3612,16 +3541,16 @@ static int icp_loop(qtr_handle* h, Slot& s, int ns, bool empty, const double* gu
     QTR_HIP_TRY(h, hipStreamSynchronize(st));
     if (B.h_state->stop) break;
   }
-  QTR_HIP_TRY(h, hipEventRecord(s.ev[2], st));
+  QTR_HIP_TRY(h, hipEventRecord(s.ev[EV_ICP_END], st));
   QTR_HIP_TRY(h, hipMemcpyAsync(B.h_state, v.st, sizeof(QtrIcpState), hipMemcpyDeviceToHost, st));
   QTR_HIP_TRY(h, hipStreamSynchronize(st));
   icp_result_from(res, *B.h_state);
   s.icp_ns = ns;
   s.icp_iters = B.h_state->iterations;
   float ms = 0;
-  if (hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) s.icp_ms[0] = ms;
-  if (hipEventElapsedTime(&ms, s.ev[1], s.ev[2]) == hipSuccess) s.icp_ms[1] = ms;
-  s.times_pending = 0;
+  if (hipEventElapsedTime(&ms, s.ev[EV_ICP_BEGIN], s.ev[EV_ICP_GRID]) == hipSuccess) s.icp_ms[0] = ms;
+  if (hipEventElapsedTime(&ms, s.ev[EV_ICP_GRID], s.ev[EV_ICP_END]) == hipSuccess) s.icp_ms[1] = ms;
+  s.times_pending = TIMES_NONE;
   s.times = qtr_stage_times{};
   s.times.total = s.icp_ms[0] + s.icp_ms[1];
   return QTR_OK;

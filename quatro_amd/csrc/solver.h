@@ -82,8 +82,8 @@ void solver_carve(SolverBufs& B, void* base, int Lcap);
 // shares_device: another launch chain of the same call runs beside this one (qtr_register_pair_corr's front end):
 // k_hcore_async leaves compute units and LDS for it (solver.hip, clique_stage_launch)
 hipError_t solver_enqueue(const SolverBufs& B, const float4* src, const float4* tgt, int L, const qtr_params& prm,
-                          hipStream_t stream, int* pinned_state, hipEvent_t ev_graph, hipEvent_t ev_clique,
-                          bool reset_done = false, bool shares_device = false);
+                          hipStream_t stream, hipEvent_t ev_graph, hipEvent_t ev_clique, bool reset_done = false,
+                          bool shares_device = false);
 hipError_t solver_reset_enqueue(const SolverBufs& B, hipStream_t stream);
 // how many back-end launch chains may run side by side on the device with the calling thread's next enqueue (1: it has
 // the device to itself): bounds k_hcore_async's resident workgroups per pair (thread-local, see solver.hip)

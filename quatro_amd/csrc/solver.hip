@@ -4333,9 +4333,8 @@ static hipError_t solver_launch(const SolverView* views, int G, const qtr_params
 }
 
 hipError_t solver_enqueue(const SolverBufs& B, const float4* src, const float4* tgt, int L, const qtr_params& prm,
-                          hipStream_t stream, int* pinned_state /* unused */, hipEvent_t ev_graph, hipEvent_t ev_clique,
-                          bool reset_done, bool shares_device) {
-  (void)pinned_state;
+                          hipStream_t stream, hipEvent_t ev_graph, hipEvent_t ev_clique, bool reset_done,
+                          bool shares_device) {
   const hipError_t e = ensure_range_table(B, prm);
   if (e != hipSuccess) return e;
   const SolverView V = make_solver_view(B, src, tgt, L);

@@ -99,6 +99,17 @@ def _dev_items(pairs, fp, corr=None):
     return items
 
 
+def _refusal(h, call):
+    """(status code, the whole qtr_last_error text) of a call that must be refused"""
+    with pytest.raises(ql.QuatroHipError) as e:
+        call()
+    return e.value.code, h.last_error()
+
+
+def _corr300():
+    return synth.correspondences(300, 0.1, seed=7, noise=0.1)[:2]
+
+
 def test_keyframes_of_a_pass_through_pair_equal_register_pair(data, seq):
     s, t = data["passing"]
     fp = _fp("passing")
@@ -134,7 +145,7 @@ def test_batch_with_a_pass_through_pair_between_normal_pairs_equals_three_calls(
         _same(g, w, lists=host_mem)
 
 
-def test_keyframe_of_a_long_list_cloud_on_a_fresh_handle(data, seq):
+def test_keyframe_of_a_long_list_cloud_on_a_fresh_handle(data, seq, qo):
     c, d = data["long"]
     fp = _fp("long")
     fresh, warm = ql.Handle(0, **LIMITS), ql.Handle(0, **LIMITS)
@@ -154,6 +165,16 @@ def test_keyframe_of_a_long_list_cloud_on_a_fresh_handle(data, seq):
         with pytest.raises(ql.QuatroHipError, match="max_long_neighbors") as e:
             h.keyframe(c, fp)
         assert e.value.code == ql.QTR_ERR_CAPACITY
+        # the whole text, on every path: the longest list of a cloud is its point with the most voxels inside the FPFH radius
+        # (the point itself included)
+        longest = [int(_neighbours(qo.voxelize(p, LONG_LEAF), fp.fpfh_radius).max()) + 1 for p in (c, d)]
+        text = "radius-neighbour lists longer than %d entries (longest %s) exceed the long-list arena: " \
+               "qtr_limits.max_long_neighbors is 4096"
+        assert _refusal(h, lambda: h.keyframe(c, fp)) == (ql.QTR_ERR_CAPACITY, text % (KMAX, "%d" % longest[0]))
+        assert _refusal(h, lambda: h.keyframe(d, fp)) == (ql.QTR_ERR_CAPACITY, text % (KMAX, "%d" % longest[1]))
+        both = (ql.QTR_ERR_CAPACITY, text % (KMAX, "%d / %d" % tuple(longest)))
+        assert _refusal(h, lambda: h.register_pair(c, d, fp)) == both
+        assert _refusal(h, lambda: h.register_pair_corr(c, d, *_corr300(), fp)) == both
         _same(h.register_pair(*data["small"], _fp("small")), seq["small"])
     finally:
         h.close()
@@ -180,6 +201,19 @@ def test_capacity_refusals_on_every_path(data, seq, kind):
         with pytest.raises(ql.QuatroHipError) as e:
             h.keyframe(s, fp)
         assert e.value.code == ql.QTR_ERR_CAPACITY and "max_voxels" in str(e.value)
+        # the whole text on every path: the counts of both clouds for a pair, of the one cloud for a keyframe
+        if kind == "passing":
+            text = "voxel grid would overflow int32 (leaf too small): the cloud passes through as it is (pcl::VoxelGrid), " \
+                   "and its %s points exceed max_voxels=1024"
+            pair, one = "%d / %d" % (s.shape[0], t.shape[0]), ["%d" % p.shape[0] for p in (s, t)]
+        else:
+            text = "voxel count %s exceeds max_voxels=1024"
+            n = (seq[kind]["n_src"], seq[kind]["n_tgt"])
+            pair, one = "(%d,%d)" % n, ["%d" % k for k in n]
+        assert _refusal(h, lambda: h.register_pair(s, t, fp)) == (ql.QTR_ERR_CAPACITY, text % pair)
+        assert _refusal(h, lambda: h.register_pair_corr(s, t, *_corr300(), fp)) == (ql.QTR_ERR_CAPACITY, text % pair)
+        assert _refusal(h, lambda: h.keyframe(s, fp)) == (ql.QTR_ERR_CAPACITY, text % one[0])
+        assert _refusal(h, lambda: h.keyframe(t, fp)) == (ql.QTR_ERR_CAPACITY, text % one[1])
         with h.keyframe(fits[0], fp) as ks, h.keyframe(fits[1], fp) as kt:
             _same(h.register_keyframes(ks, kt, fp), ok)
         got = h.register_batch([(*fits, 2), (s, t, 2), (*fits, 2)], fp)
@@ -187,6 +221,46 @@ def test_capacity_refusals_on_every_path(data, seq, kind):
         _same(got[0], ok)
         _same(got[2], ok)
         _same(h.register_batch([(*fits, 2)], fp)[0], ok)  # the lane and its slots after the refusal
+    finally:
+        h.close()
+
+
+def test_refusals_in_front_of_the_first_launch_on_every_path(data):
+    """max_points, an empty cloud, normal_radius > fpfh_radius: the same status and the same text from qtr_register_pair,
+    qtr_register_pair_corr and qtr_keyframe_create — in that order when a pair has more than one reason — and the slot
+    goes on as before."""
+    s, t = data["normal"]
+    small = data["tiny"]
+    fp = _fp("normal")
+    hw = ql.Handle(0, **LIMITS)
+    try:
+        ok = hw.register_pair(*small, fp)
+    finally:
+        hw.close()
+    bad = ql.default_frontend_params(seed=2, normal_radius=2.0, fpfh_radius=1.0)
+    empty = np.zeros((0, 4), dtype=np.float32)
+    corr = _corr300()
+    lim = dict(max_points=4096, max_voxels=1024, max_corr=8192)
+    assert min(s.shape[0], t.shape[0]) > lim["max_points"] >= max(p.shape[0] for p in small)
+    h = ql.Handle(0, **lim)
+    try:
+        points = (ql.QTR_ERR_CAPACITY, "cloud exceeds max_points=4096")
+        nothing = (ql.QTR_ERR_BAD_ARG, "Invalid or empty point cloud dataset given!")
+        radius = (ql.QTR_ERR_BAD_ARG, "[FPFHManager]: Normal should be lower than fpfh_radius!!!!")
+        for a, b in ((s, t), (small[0], t), (s, small[1])):  # either cloud of a pair
+            assert _refusal(h, lambda: h.register_pair(a, b, fp)) == points
+            assert _refusal(h, lambda: h.register_pair_corr(a, b, *corr, fp)) == points
+        assert _refusal(h, lambda: h.keyframe(s, fp)) == points
+        for a, b in ((empty, empty), (empty, small[1]), (small[0], empty), (empty, t), (s, empty)):  # empty before max_points
+            assert _refusal(h, lambda: h.register_pair(a, b, fp)) == nothing
+            assert _refusal(h, lambda: h.register_pair_corr(a, b, *corr, fp)) == nothing
+        assert _refusal(h, lambda: h.keyframe(empty, fp)) == nothing
+        for a, b in ((small[0], small[1]), (empty, small[1]), (s, t)):  # the radii before everything else
+            assert _refusal(h, lambda: h.register_pair(a, b, bad)) == radius
+            assert _refusal(h, lambda: h.register_pair_corr(a, b, *corr, bad)) == radius
+        for a in (small[0], empty, s):
+            assert _refusal(h, lambda: h.keyframe(a, bad)) == radius
+        _same(h.register_pair(*small, fp), ok)
     finally:
         h.close()
 
