@@ -796,7 +796,12 @@ QTR_API int qtr_pgo_optimize(qtr_handle* h, int slot, int n_nodes, const double*
 QTR_API long long qtr_debug_fetch(qtr_handle* h, int slot, int what, void* dst, size_t bytes);
 
 /* Evaluates the shared deterministic math (include/qtr_math.h) ON THE DEVICE, for the test that pins
- * host/device bit-equality: fn 0 atan2f(a,b), 1 acosf(a), 2 sinf(a) (theta in [0,1.2]), 3 cosf(a). */
+ * host/device bit-equality: fn 0 atan2f(a,b), 1 acosf(a), 2 sinf(a) (theta in [0,1.2]), 3 cosf(a) — and the SPFH
+ * kernel's decisions, as floats: fn 4 the bin 0 .. 10 of the first block that k2_spfh stores for the arc tangent's arguments
+ * (y, x) = (a, b), floor(11 (atan2f(a,b) + pi) / 2 pi): the shortcut below, then the arc tangent where it is not sure;
+ * fn 5 the role swap acosf(|a|) > acosf(|b|) as 1 / 0; fn 6 the bin shortcut alone (five cross products, no arc tangent):
+ * the bin, or -1 where it is not sure (y = +-0, a non-finite argument, |a| + |b| outside (1e-30, 1e30), a direction
+ * within 1e-6 of a bin boundary). */
 QTR_API int qtr_debug_math(qtr_handle* h, int fn, const float* a, const float* b, float* out, int n);
 
 #ifdef __cplusplus

@@ -4205,8 +4205,10 @@ __global__ void k_debug_math(int fn, const float* a, const float* b, float* out,
     case 1: r = qm_acosf(a[i]); break;
     case 2: qm_sincosf(a[i], &s, &c); r = s; break;
     case 3: qm_sincosf(a[i], &s, &c); r = c; break;
+    case 4: r = (float)spfh_angle_bin(a[i], b[i]); break;        // the first block's bin as k2_spfh stores it
     case 5: r = spfh_swap_roles(a[i], b[i]) ? 1.f : 0.f; break;  // the SPFH kernel's shortcut (tests compare it with the
                                                                  // plain arithmetic)
+    case 6: r = (float)spfh_bin_of_angle(a[i], b[i]); break;     // the bin shortcut alone: -1 where it is not sure
     default: break;
   }
   out[i] = r;

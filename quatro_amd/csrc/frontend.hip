@@ -1206,6 +1206,13 @@ __device__ __forceinline__ int spfh_bin_of_angle(float y, float x) {
   const int m = (int)(c0 > 0.f) + (int)(c1 > 0.f) + (int)(c2 > 0.f) + (int)(c3 > 0.f) + (int)(c4 > 0.f);
   return (y > 0.f) ? 5 + m : 5 - m;
 }
+// the bin k2_spfh stores: the shortcut, and the arc tangent where it is not sure
+__device__ __forceinline__ int spfh_angle_bin(float y, float x) {
+  const float d_pi = 1.0f / (2.0f * (float)M_PI);
+  int b1 = spfh_bin_of_angle(y, x);
+  if (b1 < 0) b1 = bin11(11 * (((double)qm_atan2f(y, x) + M_PI) * (double)d_pi));
+  return b1;
+}
 // (f[0] is left to the caller: yx = the arc tangent's two arguments, see spfh_bin_of_angle)
 __device__ bool dev_pair_features(const float4& p1, const float4& nn1, const float4& p2, const float4& nn2, float* f, float* yx) {
   float dp[3] = {p2.x - p1.x, p2.y - p1.y, p2.z - p1.z};
@@ -1282,7 +1289,6 @@ __device__ __forceinline__ void d_spfh(const float4* __restrict__ pts, const flo
   }
   __syncthreads();
   const int total = s_off[SPFH_PB];
-  const float d_pi = 1.0f / (2.0f * (float)M_PI);
   for (int t = tid; t < total; t += 256) {  // (four pairs per thread and round trip were measured: 20 -> 24 us)
     int pi = 0;  // the point this pair belongs to: largest pi with s_off[pi] <= t (5 halvings of 32)
 #pragma unroll
@@ -1295,9 +1301,7 @@ __device__ __forceinline__ void d_spfh(const float4* __restrict__ pts, const flo
     // (the first block's bin from five cross products instead of the arc tangent: round 2 measured "same kernel time" with
     // the role swap's two arc cosines still in the loop; with those gone — spfh_swap_roles — the arc tangent was a third
     // of the kernel's vector instructions, and the batched path is bound by their count: profiles/r6_pmc_fpfh.json)
-    int b1 = spfh_bin_of_angle(yx[0], yx[1]);
-    if (b1 < 0) b1 = bin11(11 * (((double)qm_atan2f(yx[0], yx[1]) + M_PI) * (double)d_pi));
-    atomicAdd(&cnt[pi][b1], 1);
+    atomicAdd(&cnt[pi][spfh_angle_bin(yx[0], yx[1])], 1);
     atomicAdd(&cnt[pi][11 + bin11(11 * (((double)f[1] + 1.0) * 0.5))], 1);
     atomicAdd(&cnt[pi][22 + bin11(11 * (((double)f[2] + 1.0) * 0.5))], 1);
   }

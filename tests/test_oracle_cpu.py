@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from backend_restate import ref_cote_python as _ref_cote_python  # noqa: E402
 from backend_restate import ref_gnc_rotation2d_numpy as _ref_gnc_rotation2d_numpy  # noqa: E402
 from backend_restate import ref_gnc_rotation3d_numpy as _ref_gnc_rotation3d_numpy  # noqa: E402
+from front_cases import angle_bin_inputs, angle_bin_mirror, angle_bin_want, brute_neighbors, voxelize_numpy  # noqa: E402
 
 
 def _cloud(n, seed, extent=6.0):
@@ -36,25 +37,7 @@ def test_voxelize_matches_independent_numpy(qo):
     pts[:, :3] = rng.normal(0, 3, (3000, 3)).astype(np.float32)
     leaf = np.float32(0.3)
     out = qo.voxelize(pts, float(leaf))
-    inv = np.float32(1.0) / leaf
-    mn, mx = pts[:, :3].min(0), pts[:, :3].max(0)
-    minb = np.floor(mn * inv).astype(np.int64)
-    maxb = np.floor(mx * inv).astype(np.int64)
-    div = maxb - minb + 1
-    ijk = (np.floor(pts[:, :3] * inv) - minb.astype(np.float32)).astype(np.int64)
-    idx = ijk[:, 0] + ijk[:, 1] * div[0] + ijk[:, 2] * div[0] * div[1]
-    order = np.lexsort((np.arange(len(idx)), idx))
-    exp = []
-    i = 0
-    while i < len(order):
-        j = i
-        acc = np.zeros(3, dtype=np.float32)
-        while j < len(order) and idx[order[j]] == idx[order[i]]:
-            acc = acc + pts[order[j], :3]
-            j += 1
-        exp.append(acc / np.float32(j - i))
-        i = j
-    exp = np.array(exp, dtype=np.float32)
+    exp = voxelize_numpy(pts, leaf)
     assert out.shape[0] == exp.shape[0]
     assert np.array_equal(out[:, :3].view(np.uint32), exp.view(np.uint32))
     # output order = ascending voxel index; every centroid lies in its voxel
@@ -75,19 +58,11 @@ def test_voxelize_edge_cases(qo):
 def test_radius_neighbors_vs_bruteforce(qo):
     c = _cloud(1200, 1)
     off, idx, d2 = qo.radius_neighbors(c, 0.75)
-    r2 = np.float32(0.75 * 0.75)
-    p = c[:, :3]
-    for i in range(0, 1200, 37):
-        dx = p[i, 0] - p[:, 0]
-        dy = p[i, 1] - p[:, 1]
-        dz = p[i, 2] - p[:, 2]
-        dd = ((dx * dx) + dy * dy) + dz * dz  # float32, L2_Simple order
-        sel = np.nonzero(dd < r2)[0]
-        order = sel[np.lexsort((sel, dd[sel]))]
-        got = idx[off[i]:off[i + 1]]
-        assert np.array_equal(got, order)
-        assert np.array_equal(d2[off[i]:off[i + 1]].view(np.uint32), dd[order].view(np.uint32))
-        assert got[0] == i  # the query itself, distance 0
+    boff, bidx, bd2 = brute_neighbors(c, 0.75)  # float32, L2_Simple order, sorted by (d2, index): every point, not a sample
+    assert np.array_equal(off, boff)
+    assert np.array_equal(idx, bidx)
+    assert np.array_equal(d2.view(np.uint32), bd2.view(np.uint32))
+    assert np.array_equal(idx[off[:-1]], np.arange(1200))  # the query itself, distance 0
 
 
 # ------------------------------------------------------------------------------------------- K2-K4
@@ -1100,32 +1075,21 @@ def test_spfh_angle_bin_shortcut_logic_against_the_oracle_arithmetic(qo):
     spfh_bin_of_angle: five cross products against the boundary directions instead of atan2f) against the oracle's plain
     arithmetic — qm_atan2f (qo_math 0), then floor(11 (f1 + pi) d_pi) in binary64 as pcl::computePointSPFHSignature does:
     wherever the shortcut claims to be sure it must give that bin.  Inputs: uniform directions, directions within 4e-6 rad of
-    every boundary (both sides, also of the cut at +-pi and of 0), y = +-0, tiny and huge magnitudes."""
-    f32 = np.float32
-    rng = np.random.default_rng(6)
-    d_pi = float(f32(1.0) / (f32(2.0) * f32(np.pi)))
-    T = np.array([k / (11 * d_pi) - np.pi for k in range(0, 12)])
-    n = 400000
-    phi = np.concatenate([rng.uniform(-np.pi, np.pi, n),
-                          (T[rng.integers(0, 12, n)] + rng.uniform(-4e-6, 4e-6, n)),
-                          rng.uniform(-4e-6, 4e-6, n // 4), np.pi - rng.uniform(0, 4e-6, n // 4), -np.pi + rng.uniform(0, 4e-6, n // 4)])
-    r = np.exp(rng.uniform(np.log(1e-12), np.log(1e6), phi.size))
-    y, x = (r * np.sin(phi)).astype(f32), (r * np.cos(phi)).astype(f32)
-    y[:2000:4], y[1:2000:4] = f32(0.0), f32(-0.0)                      # atan2f(-0, x < 0) = -pi rounds below -pi: bin 0
-    f1 = qo.math_fn(0, y, x).astype(np.float64)
-    g = 11.0 * ((f1 + np.pi) * d_pi)
-    want = np.where(g != g, 0, np.clip(np.floor(g), 0, 10)).astype(np.int64)
-    ya, s = np.abs(y), np.abs(y) + np.abs(x)
-    C = [(0.95949297361449748, 0.2817325568414295), (0.6548607339452851, 0.75574957435425827),
-         (0.14231483827328512, 0.98982144188093268), (-0.41541501300188632, 0.90963199535451844),
-         (-0.84125353283118109, 0.54064081745559778)]
-    c = [f32(ca) * ya - f32(sa) * x for ca, sa in C]                   # (float32 products, float32 difference)
-    low = np.minimum.reduce([np.abs(v) for v in c])
-    sure = (low > f32(1e-6) * s) & (s > f32(1e-30)) & (s < f32(1e30)) & (ya != 0)
-    m = sum((v > 0).astype(np.int64) for v in c)
-    got = np.where(y > 0, 5 + m, 5 - m)
-    assert sure[2000:n].mean() > 0.9999 and sure.mean() > 0.4         # (uniform directions: practically always sure)
-    assert not sure[:2000:4].any() and not sure[1:2000:4].any()
+    every boundary (both sides, also of the cut at +-pi and of 0), y = +-0, tiny and huge magnitudes, both guards of the
+    shortcut, denormals, infinities and NaN (tests/front_cases.py: angle_bin_inputs, with the mirror itself)."""
+    inp = angle_bin_inputs()
+    y, x = inp.y, inp.x
+    want = angle_bin_want(qo, y, x)
+    assert np.array_equal(want, qo.math_fn(4, y, x).astype(np.int64))  # (the oracle's own bin is that arithmetic)
+    sure, got = angle_bin_mirror(y, x)
+    assert sure[inp.uniform].mean() > 0.9999 and sure.mean() > 0.4     # (uniform directions: practically always sure)
+    assert inp.zero_y.sum() >= 1000 + 28 and not sure[inp.zero_y].any()
+    assert inp.nonfinite.sum() >= 57 and not sure[inp.nonfinite].any()
+    assert inp.out_of_guard.sum() > 20000 and not sure[inp.out_of_guard].any()
+    inside = ~inp.out_of_guard & ~inp.uniform & ~inp.zero_y                # next to both guards, on the inner side
+    with np.errstate(all="ignore"):
+        s = np.abs(y) + np.abs(x)
+    assert (sure & inside & (s < 1e-29)).sum() > 1000 and (sure & inside & (s > 1e29)).sum() > 1000
     assert np.array_equal(got[sure], want[sure])
     assert set(np.unique(want[sure])) == set(range(11))
 
