@@ -615,12 +615,17 @@ def constant_velocity_guess(T_prev2, T_prev1):
     return np.array(G, dtype=np.float64)
 
 
-def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capacity=None):
+def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capacity=None, window_radius=None):
     """Scan-to-map odometry: a keyframe of every scan (fp; a scan that already is a Keyframe is used as it is), the first
     inserted at the identity, every later one registered against the map from the constant-velocity guess
     T_{k-1} (T_{k-2}^-1 T_{k-1}) (the identity motion for the second scan) and inserted under the result.  A registration
     that is not valid keeps its guess as the pose.  Returns (poses [K, 4, 4], vmap); the caller destroys the map.  The
-    keyframes made here are closed before the call returns.  capacity None: 1 << 20 voxels."""
+    keyframes made here are closed before the call returns.  capacity None: 1 << 20 voxels.
+
+    window_radius = r (metres): a local map.  After each insert the map is evicted around the translation of the pose just
+    inserted (VoxelMap.evict: voxels farther than floor(r / voxel_size) voxels from the pose's voxel leave), so `capacity`
+    can be sized for the window, not for the trajectory, and scans are no longer registered against voxels folded from
+    poses far behind.  None: nothing is evicted, the map of the whole trajectory."""
     fp = fp or _ql.default_frontend_params()
     vmap = handle.voxel_map(voxel_size, (1 << 20) if capacity is None else capacity)
     poses = []
@@ -636,6 +641,8 @@ def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capac
                     r = localize(handle, vmap, kf, guess, icp)
                     T = np.array(r["T"], dtype=np.float64) if r["valid"] else np.array(guess, dtype=np.float64)
                 vmap.insert_keyframe(kf, T)
+                if window_radius is not None:
+                    vmap.evict(T[:3, 3], window_radius)
             finally:
                 if own:
                     kf.close()

@@ -21,11 +21,14 @@ TEST_LIB = os.path.join(HERE, "libquatro_hip_testengines.so")
 # the voxel map's entry points (include/quatro_voxelmap.h) are a library of their own over the same sources: libquatro_hip.so's
 # dynamic symbol table stays the C ABI of include/quatro_hip.h
 VOXELMAP_LIB = os.path.join(HERE, "libquatro_voxelmap.so")
+# ... and so are the map's upkeep entry points (include/quatro_voxelmap_keep.h): the other two tables stay what they were
+VOXELMAP_KEEP_LIB = os.path.join(HERE, "libquatro_voxelmap_keep.so")
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))) + [
     os.path.join("..", "..", "include", "qtr_math.h"), os.path.join("..", "..", "include", "qtr_icp_math.h"),
     os.path.join("..", "..", "include", "qtr_place_math.h"),
     os.path.join("..", "..", "include", "qtr_submap_math.h"), os.path.join("..", "..", "include", "qtr_eval_math.h"),
     os.path.join("..", "..", "include", "qtr_pgo_math.h"), os.path.join("..", "..", "include", "qtr_vmap_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap.h"),
+    os.path.join("..", "..", "include", "qtr_vmap_keep_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap_keep.h"),
     os.path.join("..", "..", "include", "quatro_hip.h")]
 
 
@@ -45,6 +48,12 @@ def build_voxelmap(force: bool = False, verbose: bool = True) -> str:
     return build(force, verbose, lib=VOXELMAP_LIB, defines=("-DQTR_VOXELMAP_LIB",), exports="exports_voxelmap.map")
 
 
+def build_voxelmap_keep(force: bool = False, verbose: bool = True) -> str:
+    build_voxelmap(False, verbose)  # (the three libraries come from the same sources: the other two, where they are stale)
+    return build(force, verbose, lib=VOXELMAP_KEEP_LIB, defines=("-DQTR_VOXELMAP_KEEP_LIB",),
+                 exports="exports_voxelmap_keep.map")
+
+
 def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=(), exports: str = "exports.map") -> str:
     if not force and not is_stale(lib):
         return lib
@@ -62,4 +71,5 @@ def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=(),
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     build_voxelmap(force="--force" in sys.argv)
+    build_voxelmap_keep(force="--force" in sys.argv)
     build_test_engines(force="--force" in sys.argv)

@@ -244,6 +244,8 @@ struct qtr_voxel_map {
   void* table = nullptr;    // keys, cnt, acc, rec, tcnt, did
   void* scratch = nullptr;  // the insert's per-point arrays (max_points points), allocated on the first insert
   int* pin = nullptr;       // pinned: the counters' read-back
+  void* stage = nullptr;    // evict / restore staging for stage_cap voxels (voxelmap_keep.hip), allocated on first need
+  size_t stage_cap = 0;
   VmapView v{};
   VmapIns ins{};
   hipStream_t stream = nullptr;  // clear and fetch, which take no slot
@@ -291,6 +293,7 @@ static void vmap_release(qtr_voxel_map* m) {
   }
   if (m->table) (void)hipFree(m->table);
   if (m->scratch) (void)hipFree(m->scratch);
+  if (m->stage) (void)hipFree(m->stage);
   if (m->pin) (void)hipHostFree(m->pin);
   delete m;
 }

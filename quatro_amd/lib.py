@@ -159,6 +159,10 @@ class VoxelMapInsertInfo(C.Structure):
     _fields_ = [("n_points", C.c_int), ("n_members", C.c_int), ("n_new_voxels", C.c_int), ("n_touched_voxels", C.c_int)]
 
 
+class VoxelMapEvictInfo(C.Structure):
+    _fields_ = [("n_kept", C.c_int), ("n_evicted", C.c_int), ("n_members_evicted", C.c_longlong)]
+
+
 KF_VOX, KF_NORMALS, KF_FPFH, KF_MEAN = 1, 2, 3, 4
 VMAP_COORDS, VMAP_COUNT, VMAP_SUMS, VMAP_RECORDS, VMAP_CLOUD = 1, 2, 3, 4, 5
 VMAP_MAX_CAPACITY = 1 << 24
@@ -192,6 +196,8 @@ VOXELMAP_EXPORTS = [
     "qtr_voxel_map_get_info", "qtr_voxel_map_insert", "qtr_voxel_map_insert_keyframe", "qtr_voxel_map_register",
     "qtr_voxel_map_register_keyframe", "qtr_voxel_map_fetch",
 ]
+# the C ABI of include/quatro_voxelmap_keep.h: libquatro_voxelmap_keep.so, the map's upkeep, a third library likewise
+VOXELMAP_KEEP_EXPORTS = ["qtr_voxel_map_evict", "qtr_voxel_map_restore"]
 
 _lib = None
 
@@ -433,6 +439,30 @@ def load_voxelmap():
     lib.qtr_voxel_map_fetch.restype = C.c_longlong
     lib.qtr_voxel_map_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
     _vmap_lib = lib
+    return lib
+
+
+VOXELMAP_KEEP_LIB_PATH = os.environ.get("QTR_VOXELMAP_KEEP_LIB") or os.path.join(_HERE, "libquatro_voxelmap_keep.so")
+_vmap_keep_lib = None
+
+
+def load_voxelmap_keep():
+    """libquatro_voxelmap_keep.so (include/quatro_voxelmap_keep.h): the map's upkeep, evict and restore.  They take the
+    handles and maps of the other two libraries; all three come from the same build
+    (quatro_amd.build.build_voxelmap_keep)."""
+    global _vmap_keep_lib
+    if _vmap_keep_lib is not None:
+        return _vmap_keep_lib
+    load_voxelmap()
+    if not os.path.exists(VOXELMAP_KEEP_LIB_PATH):
+        raise FileNotFoundError(
+            f"{VOXELMAP_KEEP_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
+            "(or __graft_entry__.build()) first.")
+    lib = C.CDLL(VOXELMAP_KEEP_LIB_PATH)
+    lib.qtr_voxel_map_evict.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double * 3), C.c_double,
+                                        C.POINTER(VoxelMapEvictInfo)]
+    lib.qtr_voxel_map_restore.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    _vmap_keep_lib = lib
     return lib
 
 
@@ -692,6 +722,41 @@ class VoxelMap:
     def clear(self, slot: int = 0) -> None:
         """Empties the map; its voxel size and capacity stay (qtr_voxel_map_clear)."""
         self._handle._check(self._vlib.qtr_voxel_map_clear(self._handle._h, slot, self._m))
+
+    def evict(self, centre, radius: float, slot: int = 0) -> dict:
+        """Sliding-window eviction (qtr_voxel_map_evict): with C = floor(centre / voxel_size) and R = floor(radius /
+        voxel_size), the voxels with |coordinates - C|^2 > R^2 (in integers) leave the map; the others stay bit for bit.
+        Returns n_kept, n_evicted, n_members_evicted."""
+        h, klib = self._handle, load_voxelmap_keep()
+        c = (C.c_double * 3)(*[float(x) for x in np.asarray(centre, dtype=np.float64).reshape(3)])
+        info = VoxelMapEvictInfo()
+        h._check(klib.qtr_voxel_map_evict(h._h, slot, self._m, C.byref(c), float(radius), C.byref(info)))
+        return {n: getattr(info, n) for n, _ in VoxelMapEvictInfo._fields_}
+
+    def restore(self, coords, count, sums, slot: int = 0) -> None:
+        """Puts voxels given as the fetch sections VMAP_COORDS (int32 [n, 3]), VMAP_COUNT (int32 [n]) and VMAP_SUMS (float64
+        [n, 9]) into this map, which must hold no voxel (qtr_voxel_map_restore): numpy arrays (host) or contiguous torch
+        tensors, all three on the device."""
+        h, klib = self._handle, load_voxelmap_keep()
+        if isinstance(coords, np.ndarray) or not hasattr(coords, "data_ptr"):
+            coords = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 3)
+            count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+            sums = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1, 9)
+        else:
+            import torch
+            assert (coords.dtype, count.dtype, sums.dtype) == (torch.int32, torch.int32, torch.float64)
+        n = int(coords.shape[0])
+        assert tuple(coords.shape) == (n, 3) and tuple(count.shape) == (n,) and tuple(sums.shape) == (n, 9)
+        (pc, m1), (pn, m2), (ps, m3) = _ptr(coords), _ptr(count), _ptr(sums)
+        assert m1 == m2 == m3, "coords, count and sums must all be host arrays or all be device tensors"
+        h._check(klib.qtr_voxel_map_restore(h._h, slot, self._m, pc, pn, ps, n, m1))
+
+    def save(self, path) -> None:
+        """The whole state of the map as one .npz file (np.savez, which appends ".npz" to a name without it): voxel_size,
+        capacity and the sections coords, count and sums.  Handle.load_voxel_map reads it back."""
+        info = self.info()
+        np.savez(path, voxel_size=np.float64(info["voxel_size"]), capacity=np.int64(info["capacity"]),
+                 coords=self.fetch(VMAP_COORDS), count=self.fetch(VMAP_COUNT), sums=self.fetch(VMAP_SUMS))
 
     def destroy(self):
         if self._m and getattr(self._handle, "_h", None):
@@ -1223,6 +1288,20 @@ class Handle:
         prm.voxel_size, prm.capacity = float(voxel_size), int(capacity)
         self._check(vlib.qtr_voxel_map_create(self._h, C.byref(prm), C.byref(out)))
         return VoxelMap(self, out.value)
+
+    def load_voxel_map(self, path, capacity: int | None = None) -> VoxelMap:
+        """A new voxel map of this handle with the voxels of a file written by VoxelMap.save (qtr_voxel_map_restore);
+        capacity None: the saved map's."""
+        with np.load(path) as f:
+            side, cap = float(f["voxel_size"]), int(f["capacity"])
+            coords, count, sums = f["coords"], f["count"], f["sums"]
+        vm = self.voxel_map(side, cap if capacity is None else int(capacity))
+        try:
+            vm.restore(coords, count, sums)
+        except Exception:
+            vm.destroy()
+            raise
+        return vm
 
     def place_describe(self, xyz4, params: PlaceParams | None = None, slot: int = 0):
         """qtr_place_describe: the [num_rings, num_sectors] descriptor of a host cloud ([n, 4] float32 -> numpy) or of a
