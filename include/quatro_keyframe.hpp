@@ -14,6 +14,8 @@
 
 #include "quatro_hip_cxx.hpp"
 
+struct qtr_deskew_info;  // (include/quatro_deskew.h)
+
 namespace quatro_hip {
 
 // RAII owner of one qtr_keyframe of default_handle(); move-only, read-only once made.
@@ -69,6 +71,12 @@ class Keyframe {
     }
     return out;
   }
+  // A keyframe of a RAW sweep of a moving sensor, deskewed on the device on its way (qtr_keyframe_create_deskewed): times = n
+  // floats, the time of every point; K = knot_times.size() knots, knot_poses 16 doubles each; info (optional) receives the
+  // deskew's counts.  DEFINED in quatro_deskew.hpp: a program that calls it includes that header and adds -lquatro_deskew.
+  static Keyframe create_deskewed(const float* raw4, const float* times, int n, const std::vector<double>& knot_times,
+                                  const std::vector<double>& knot_poses, double t_ref, const qtr_frontend_params& fp,
+                                  qtr_deskew_info* info = nullptr);
   // QTR_KF_VOX / _NORMALS / _FPFH / _MEAN as floats
   std::vector<float> fetch(int what) const {
     const long long bytes = qtr_keyframe_fetch(default_handle(), kf_, what, nullptr, 0);

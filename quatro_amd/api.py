@@ -615,7 +615,23 @@ def constant_velocity_guess(T_prev2, T_prev1):
     return np.array(G, dtype=np.float64)
 
 
-def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capacity=None, window_radius=None):
+def constant_velocity_knots(T_prev2, T_prev1, period):
+    """The knots of a sweep under the constant-velocity guess: ([0, period], [I, T_{k-2}^-1 T_{k-1}]) — the sensor moves during
+    sweep k as it moved from pose k - 2 to pose k - 1, expressed in its own frame at the sweep's start — for Handle.deskew and
+    Handle.keyframe(times=...).  The motion is computed in the fixed-order float64 arithmetic of constant_velocity_guess
+    (the inverse is [R^T | -R^T t]), so every caller gets the same bits from the same poses."""
+    A = [[float(x) for x in row] for row in np.asarray(T_prev2, dtype=np.float64).reshape(4, 4)]
+    B = [[float(x) for x in row] for row in np.asarray(T_prev1, dtype=np.float64).reshape(4, 4)]
+    inv = [[A[c][r] for c in range(3)] + [-((A[0][r] * A[0][3] + A[1][r] * A[1][3]) + A[2][r] * A[2][3])] for r in range(3)]
+    inv.append([0.0, 0.0, 0.0, 1.0])
+    M = [[((inv[r][0] * B[0][c] + inv[r][1] * B[1][c]) + inv[r][2] * B[2][c]) + inv[r][3] * B[3][c] for c in range(4)]
+         for r in range(4)]
+    M[3] = [0.0, 0.0, 0.0, 1.0]
+    return np.array([0.0, float(period)], dtype=np.float64), np.stack([np.eye(4), np.array(M, dtype=np.float64)])
+
+
+def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capacity=None, window_radius=None, times=None,
+                         sweep_period=None):
     """Scan-to-map odometry: a keyframe of every scan (fp; a scan that already is a Keyframe is used as it is), the first
     inserted at the identity, every later one registered against the map from the constant-velocity guess
     T_{k-1} (T_{k-2}^-1 T_{k-1}) (the identity motion for the second scan) and inserted under the result.  A registration
@@ -625,14 +641,30 @@ def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capac
     window_radius = r (metres): a local map.  After each insert the map is evicted around the translation of the pose just
     inserted (VoxelMap.evict: voxels farther than floor(r / voxel_size) voxels from the pose's voxel leave), so `capacity`
     can be sized for the window, not for the trajectory, and scans are no longer registered against voxels folded from
-    poses far behind.  None: nothing is evicted, the map of the whole trajectory."""
+    poses far behind.  None: nothing is evicted, the map of the whole trajectory.
+
+    times = a list of per-scan float32 arrays (the time of every point since its sweep's start, seconds) with sweep_period
+    (seconds per sweep): the scans are RAW sweeps of a moving sensor and every one is deskewed on the device on its way to
+    its keyframe (Handle.keyframe(times=...), t_ref = 0): scan k >= 2 under constant_velocity_knots(T_{k-2}, T_{k-1},
+    sweep_period), scans 0 and 1 under identity knots (no motion is known yet).  The poses are then the sensor's at the start
+    of each sweep.  A scan that already is a Keyframe is used as it is.  None: the scans are taken as they are."""
     fp = fp or _ql.default_frontend_params()
+    if times is not None:
+        if sweep_period is None or not float(sweep_period) > 0.0:
+            raise ValueError("scan_to_map_odometry: times needs sweep_period > 0 (seconds per sweep)")
+        if len(times) != len(scans):
+            raise ValueError(f"scan_to_map_odometry: {len(scans)} scans, {len(times)} arrays of times")
     vmap = handle.voxel_map(voxel_size, (1 << 20) if capacity is None else capacity)
     poses = []
     try:
         for k, scan in enumerate(scans):
             own = not isinstance(scan, _ql.Keyframe)
-            kf = handle.keyframe(scan, fp) if own else scan
+            if own and times is not None:
+                kt, kp = (constant_velocity_knots(poses[-2], poses[-1], sweep_period) if k >= 2 else
+                          (np.array([0.0, float(sweep_period)]), np.stack([np.eye(4), np.eye(4)])))
+                kf = handle.keyframe(scan, fp, times=times[k], knot_times=kt, knot_poses=kp, t_ref=0.0)
+            else:
+                kf = handle.keyframe(scan, fp) if own else scan
             try:
                 if k == 0:
                     T = np.eye(4)

@@ -23,12 +23,15 @@ TEST_LIB = os.path.join(HERE, "libquatro_hip_testengines.so")
 VOXELMAP_LIB = os.path.join(HERE, "libquatro_voxelmap.so")
 # ... and so are the map's upkeep entry points (include/quatro_voxelmap_keep.h): the other two tables stay what they were
 VOXELMAP_KEEP_LIB = os.path.join(HERE, "libquatro_voxelmap_keep.so")
+# ... and sweep deskew (include/quatro_deskew.h), a fourth
+DESKEW_LIB = os.path.join(HERE, "libquatro_deskew.so")
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))) + [
     os.path.join("..", "..", "include", "qtr_math.h"), os.path.join("..", "..", "include", "qtr_icp_math.h"),
     os.path.join("..", "..", "include", "qtr_place_math.h"),
     os.path.join("..", "..", "include", "qtr_submap_math.h"), os.path.join("..", "..", "include", "qtr_eval_math.h"),
     os.path.join("..", "..", "include", "qtr_pgo_math.h"), os.path.join("..", "..", "include", "qtr_vmap_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap.h"),
     os.path.join("..", "..", "include", "qtr_vmap_keep_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap_keep.h"),
+    os.path.join("..", "..", "include", "qtr_deskew_math.h"), os.path.join("..", "..", "include", "quatro_deskew.h"),
     os.path.join("..", "..", "include", "quatro_hip.h")]
 
 
@@ -54,6 +57,11 @@ def build_voxelmap_keep(force: bool = False, verbose: bool = True) -> str:
                  exports="exports_voxelmap_keep.map")
 
 
+def build_deskew(force: bool = False, verbose: bool = True) -> str:
+    build_voxelmap_keep(False, verbose)  # (the four libraries come from the same sources: the other three, where they are stale)
+    return build(force, verbose, lib=DESKEW_LIB, defines=("-DQTR_DESKEW_LIB",), exports="exports_deskew.map")
+
+
 def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=(), exports: str = "exports.map") -> str:
     if not force and not is_stale(lib):
         return lib
@@ -72,4 +80,5 @@ if __name__ == "__main__":
     build(force="--force" in sys.argv)
     build_voxelmap(force="--force" in sys.argv)
     build_voxelmap_keep(force="--force" in sys.argv)
+    build_deskew(force="--force" in sys.argv)
     build_test_engines(force="--force" in sys.argv)

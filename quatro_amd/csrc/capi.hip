@@ -73,6 +73,8 @@ struct Slot {
   PlaceScratch place;            // place-index scratch (allocated / grown on the first query or add: place.hip)
   KfGatherMember* merge_pin = nullptr;  // qtr_keyframe_merge: the member table in pinned host memory and its device copy
   KfGatherMember* merge_dev = nullptr;  // (QTR_SUBMAP_MAX_KEYFRAMES records each, allocated on the slot's first merge)
+  void* deskew_pin = nullptr;  // deskew.hip: the knot table and the counters' read-back in pinned host memory, and the device
+  void* deskew_dev = nullptr;  // copy of the table with the counters behind it (allocated on the slot's first deskew)
 };
 
 // What a batch lane is waiting for: the mail of the chain it enqueued last (lane_poll).
@@ -474,6 +476,8 @@ void qtr_destroy(qtr_handle* h) {
     if (s.place.pin) (void)hipHostFree(s.place.pin);
     if (s.merge_pin) (void)hipHostFree(s.merge_pin);
     if (s.merge_dev) (void)hipFree(s.merge_dev);
+    if (s.deskew_pin) (void)hipHostFree(s.deskew_pin);
+    if (s.deskew_dev) (void)hipFree(s.deskew_dev);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.stream2) (void)hipStreamDestroy(s.stream2);
     if (s.stream3) (void)hipStreamDestroy(s.stream3);

@@ -163,7 +163,12 @@ class VoxelMapEvictInfo(C.Structure):
     _fields_ = [("n_kept", C.c_int), ("n_evicted", C.c_int), ("n_members_evicted", C.c_longlong)]
 
 
+class DeskewInfo(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("n_skipped", C.c_int), ("n_extrapolated", C.c_int)]
+
+
 KF_VOX, KF_NORMALS, KF_FPFH, KF_MEAN = 1, 2, 3, 4
+DESKEW_MAX_KNOTS = 256
 VMAP_COORDS, VMAP_COUNT, VMAP_SUMS, VMAP_RECORDS, VMAP_CLOUD = 1, 2, 3, 4, 5
 VMAP_MAX_CAPACITY = 1 << 24
 PLACE_DESC, PLACE_COLNORM2 = 1, 2
@@ -198,6 +203,8 @@ VOXELMAP_EXPORTS = [
 ]
 # the C ABI of include/quatro_voxelmap_keep.h: libquatro_voxelmap_keep.so, the map's upkeep, a third library likewise
 VOXELMAP_KEEP_EXPORTS = ["qtr_voxel_map_evict", "qtr_voxel_map_restore"]
+# the C ABI of include/quatro_deskew.h: libquatro_deskew.so, sweep deskew, a fourth library likewise
+DESKEW_EXPORTS = ["qtr_deskew", "qtr_keyframe_create_deskewed", "qtr_deskew_pose_at"]
 
 _lib = None
 
@@ -466,6 +473,53 @@ def load_voxelmap_keep():
     return lib
 
 
+DESKEW_LIB_PATH = os.environ.get("QTR_DESKEW_LIB") or os.path.join(_HERE, "libquatro_deskew.so")
+_deskew_lib = None
+
+
+def load_deskew():
+    """libquatro_deskew.so (include/quatro_deskew.h): motion compensation of a raw sweep.  Its calls take the handles of
+    libquatro_hip.so; both come from the same build (quatro_amd.build.build_deskew)."""
+    global _deskew_lib
+    if _deskew_lib is not None:
+        return _deskew_lib
+    load()
+    if not os.path.exists(DESKEW_LIB_PATH):
+        raise FileNotFoundError(
+            f"{DESKEW_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
+            "(or __graft_entry__.build()) first.")
+    lib = C.CDLL(DESKEW_LIB_PATH)
+    lib.qtr_deskew.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                               C.c_double, C.c_void_p, C.c_int, C.POINTER(DeskewInfo)]
+    lib.qtr_keyframe_create_deskewed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_int, C.c_double, C.POINTER(FrontendParams), C.c_int,
+                                                 C.POINTER(C.c_void_p), C.POINTER(DeskewInfo)]
+    lib.qtr_deskew_pose_at.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
+    _deskew_lib = lib
+    return lib
+
+
+def _knots(knot_times, knot_poses):
+    """(times [K] float64, poses [K, 16] float64), contiguous host arrays."""
+    kt = np.ascontiguousarray(np.asarray(knot_times, dtype=np.float64).reshape(-1))
+    kp = np.ascontiguousarray(np.asarray(knot_poses, dtype=np.float64).reshape(-1, 16))
+    if kt.shape[0] != kp.shape[0]:
+        raise ValueError(f"{kt.shape[0]} knot times, {kp.shape[0]} knot poses")
+    return kt, kp
+
+
+def deskew_pose_at(knot_times, knot_poses, t: float) -> np.ndarray:
+    """qtr_deskew_pose_at (host only): the 4 x 4 pose the knots give at time t by the deskew's rule — rotation along the
+    geodesic of the knot interval, translation linearly, the first / last interval extrapolated outside the knots."""
+    kt, kp = _knots(knot_times, knot_poses)
+    T = np.zeros(16, dtype=np.float64)
+    rc = load_deskew().qtr_deskew_pose_at(kt.ctypes.data, kp.ctypes.data, int(kt.shape[0]), float(t), T.ctypes.data)
+    if rc != QTR_OK:
+        raise QuatroHipError(rc, "qtr_deskew_pose_at: the knots are refused (2 .. 256 of them, finite and strictly increasing "
+                                 "times, finite poses, at most pi / 2 of rotation between two)")
+    return T.reshape(4, 4)
+
+
 def comm_unique_id() -> bytes:
     """The rendezvous id rank 0 creates for qtr_comm_init (128 bytes)."""
     buf = C.create_string_buffer(128)
@@ -602,6 +656,8 @@ def _f4(a):
 class Keyframe:
     """One scan's front end kept on the device (qtr_keyframe): made by Handle.keyframe, read-only, freed by close() / the
     context manager — or by the handle's close() at the latest (it is then dead: do not use it afterwards)."""
+
+    deskew = None  # n_points, n_skipped, n_extrapolated of the deskew, for a keyframe made of a raw sweep with its times
 
     def __init__(self, handle: "Handle", ptr: int):
         self._handle, self._kf = handle, C.c_void_p(ptr)
@@ -1197,15 +1253,69 @@ class Handle:
         return out, [_icp_dict(refined[i]) for i in range(B)]
 
     # ---- keyframes: a scan's front end once, registrations against it many times
-    def keyframe(self, raw4, fp: FrontendParams | None = None, slot: int = 0) -> Keyframe:
-        """qtr_keyframe_create on a host scan ([P, 4] float32) or a contiguous torch device tensor."""
+    def keyframe(self, raw4, fp: FrontendParams | None = None, slot: int = 0, times=None, knot_times=None, knot_poses=None,
+                 t_ref: float = 0.0) -> Keyframe:
+        """qtr_keyframe_create on a host scan ([P, 4] float32) or a contiguous torch device tensor.
+
+        times, knot_times and knot_poses given (all three): the scan is a raw sweep that is deskewed on the device first
+        (qtr_keyframe_create_deskewed: per-point times [P] float32 where the scan lives, knots as for Handle.deskew); the
+        counts of that pass are left in the keyframe's `deskew` attribute."""
         fp = fp or default_frontend_params()
         if isinstance(raw4, np.ndarray):
             raw4 = _f4(raw4)
         ptr, mem = _ptr(raw4)
         kf = C.c_void_p()
+        if times is not None or knot_times is not None or knot_poses is not None:
+            if times is None or knot_times is None or knot_poses is None:
+                raise ValueError("a deskewed keyframe needs times, knot_times and knot_poses")
+            times, pt, kt, kp = self._deskew_args(raw4, times, mem, knot_times, knot_poses)
+            info = DeskewInfo()
+            self._check(load_deskew().qtr_keyframe_create_deskewed(
+                self._h, slot, ptr, pt, int(raw4.shape[0]), kt.ctypes.data, kp.ctypes.data, int(kt.shape[0]), float(t_ref),
+                C.byref(fp), mem, C.byref(kf), C.byref(info)))
+            out = Keyframe(self, kf.value)
+            out.deskew = {n: getattr(info, n) for n, _ in DeskewInfo._fields_}
+            return out
         self._check(self._lib.qtr_keyframe_create(self._h, slot, ptr, int(raw4.shape[0]), C.byref(fp), mem, C.byref(kf)))
         return Keyframe(self, kf.value)
+
+    def _deskew_args(self, cloud, times, mem, knot_times, knot_poses):
+        """(times, their pointer, knot times, knot poses) for a cloud that lives in `mem`: the caller holds the returned
+        arrays while the pointers are in use."""
+        if isinstance(times, np.ndarray) or not hasattr(times, "data_ptr"):
+            times = np.ascontiguousarray(times, dtype=np.float32).reshape(-1)
+        else:
+            import torch
+            assert times.dtype == torch.float32
+        pt, mt = _ptr(times)
+        if mt != mem:
+            raise ValueError("cloud and times must both be host arrays or both be device tensors")
+        if int(times.shape[0]) != int(cloud.shape[0]) or len(times.shape) != 1:
+            raise ValueError(f"{int(cloud.shape[0])} points, times of shape {tuple(times.shape)}")
+        kt, kp = _knots(knot_times, knot_poses)
+        return times, pt, kt, kp
+
+    def deskew(self, cloud, times, knot_times, knot_poses, t_ref: float = 0.0, slot: int = 0, out=None):
+        """qtr_deskew: the sweep `cloud` ([P, 4] float32, host array or contiguous torch device tensor) with the time of
+        every point (`times`, [P] float32, where the cloud lives) carried into the sensor frame at t_ref, given K knots:
+        knot_times [K] (finite, strictly increasing) and knot_poses [K, 4, 4] (sensor frame at that time -> a fixed frame),
+        host arrays.  Returns (deskewed cloud, info): a new numpy array for a host cloud; for a device tensor a new tensor,
+        or `out` (which may be the cloud itself: in place).  info: n_points, n_skipped (points with a non-finite
+        coordinate or time, copied unchanged), n_extrapolated (times outside the knots)."""
+        if isinstance(cloud, np.ndarray) or not hasattr(cloud, "data_ptr"):
+            cloud = _f4(cloud)
+            assert out is None, "out= is for device tensors"
+            out = np.empty_like(cloud)
+        elif out is None:
+            import torch
+            out = torch.empty_like(cloud)
+        (pc, mem), (po, mo) = _ptr(cloud), _ptr(out)
+        assert mem == mo and tuple(out.shape) == tuple(cloud.shape)
+        times, pt, kt, kp = self._deskew_args(cloud, times, mem, knot_times, knot_poses)
+        info = DeskewInfo()
+        self._check(load_deskew().qtr_deskew(self._h, slot, pc, pt, int(cloud.shape[0]), kt.ctypes.data, kp.ctypes.data,
+                                             int(kt.shape[0]), float(t_ref), po, mem, C.byref(info)))
+        return out, {n: getattr(info, n) for n, _ in DeskewInfo._fields_}
 
     def merge_keyframes(self, kfs, poses=None, fp: FrontendParams | None = None, slot: int = 0) -> Keyframe:
         """qtr_keyframe_merge: the keyframes' stored voxels, member k moved by poses[k] ([K, 4, 4] float64; None: identities),
