@@ -573,18 +573,31 @@ def make_submap(handle, keyframes, poses, center, half_width, fp=None, id_lo=0, 
     return handle.merge_keyframes([keyframes[i] for i in range(lo, hi)], rel, fp, slot)
 
 
-def build_map(handle, keyframes, poses, voxel_size=1.0, capacity=None):
+def build_map(handle, keyframes, poses, voxel_size=1.0, capacity=None, carve=None):
     """The global map: every keyframe inserted under its pose (4 x 4, keyframe frame -> map frame — what
     Handle.optimize_pose_graph returns) into a new VoxelMap of side voxel_size, in list order.  capacity None: the sum of
     the keyframes' voxel counts, which no map of them can exceed (at least 1).  The caller destroys the returned map; its
-    fetch() is the map cloud."""
+    fetch() is the map cloud.
+
+    carve = CarveParams (lib.default_carve_params): after all inserts the map is carved with all keyframes under their poses
+    (VoxelMap.carve_keyframes), in groups of 64 in list order, each group a vote of its own: what moved through the scene
+    while it was mapped leaves the map.  Every group must hold at least carve.min_votes keyframes (ValueError before
+    anything is built).  The keyframes should be made of raw sweeps (see VoxelMap.carve).  None: nothing is carved."""
     assert len(keyframes) == len(poses)
+    if carve is not None:
+        groups = [(a, min(a + _ql.CARVE_MAX_KEYFRAMES, len(keyframes))) for a in range(0, len(keyframes), _ql.CARVE_MAX_KEYFRAMES)]
+        if any(b - a < carve.min_votes for a, b in groups):
+            raise ValueError(f"build_map: carve.min_votes={carve.min_votes} exceeds a group of the {len(keyframes)} keyframes "
+                             f"(groups of {_ql.CARVE_MAX_KEYFRAMES})")
     if capacity is None:
         capacity = max(1, sum(int(kf.info["n_voxels"]) for kf in keyframes))
     vmap = handle.voxel_map(voxel_size, capacity)
     try:
         for kf, pose in zip(keyframes, poses):
             vmap.insert_keyframe(kf, pose)
+        if carve is not None:
+            for a, b in groups:
+                vmap.carve_keyframes(keyframes[a:b], np.asarray(poses, dtype=np.float64)[a:b], carve)
     except Exception:
         vmap.destroy()
         raise
@@ -631,7 +644,7 @@ def constant_velocity_knots(T_prev2, T_prev1, period):
 
 
 def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capacity=None, window_radius=None, times=None,
-                         sweep_period=None):
+                         sweep_period=None, carve=None):
     """Scan-to-map odometry: a keyframe of every scan (fp; a scan that already is a Keyframe is used as it is), the first
     inserted at the identity, every later one registered against the map from the constant-velocity guess
     T_{k-1} (T_{k-2}^-1 T_{k-1}) (the identity motion for the second scan) and inserted under the result.  A registration
@@ -647,8 +660,15 @@ def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capac
     (seconds per sweep): the scans are RAW sweeps of a moving sensor and every one is deskewed on the device on its way to
     its keyframe (Handle.keyframe(times=...), t_ref = 0): scan k >= 2 under constant_velocity_knots(T_{k-2}, T_{k-1},
     sweep_period), scans 0 and 1 under identity knots (no motion is known yet).  The poses are then the sensor's at the start
-    of each sweep.  A scan that already is a Keyframe is used as it is.  None: the scans are taken as they are."""
+    of each sweep.  A scan that already is a Keyframe is used as it is.  None: the scans are taken as they are.
+
+    carve = CarveParams (lib.default_carve_params): after each insert — and after its eviction where a window is set — the
+    map is carved with that scan's keyframe under its pose (VoxelMap.carve_keyframes, one vote, so carve.min_votes must be
+    1; ValueError before anything is built): voxels the scan saw through leave the map before the next registration.  The scans should be raw sweeps (see
+    VoxelMap.carve).  None: nothing is carved."""
     fp = fp or _ql.default_frontend_params()
+    if carve is not None and carve.min_votes != 1:
+        raise ValueError(f"scan_to_map_odometry: carve.min_votes={carve.min_votes} (one scan votes per carve: it must be 1)")
     if times is not None:
         if sweep_period is None or not float(sweep_period) > 0.0:
             raise ValueError("scan_to_map_odometry: times needs sweep_period > 0 (seconds per sweep)")
@@ -675,6 +695,8 @@ def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capac
                 vmap.insert_keyframe(kf, T)
                 if window_radius is not None:
                     vmap.evict(T[:3, 3], window_radius)
+                if carve is not None:
+                    vmap.carve_keyframes([kf], T[None], carve)
             finally:
                 if own:
                     kf.close()

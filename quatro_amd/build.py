@@ -25,6 +25,8 @@ VOXELMAP_LIB = os.path.join(HERE, "libquatro_voxelmap.so")
 VOXELMAP_KEEP_LIB = os.path.join(HERE, "libquatro_voxelmap_keep.so")
 # ... and sweep deskew (include/quatro_deskew.h), a fourth
 DESKEW_LIB = os.path.join(HERE, "libquatro_deskew.so")
+# ... and the map's visibility carving (include/quatro_voxelmap_carve.h), a fifth
+VOXELMAP_CARVE_LIB = os.path.join(HERE, "libquatro_voxelmap_carve.so")
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))) + [
     os.path.join("..", "..", "include", "qtr_math.h"), os.path.join("..", "..", "include", "qtr_icp_math.h"),
     os.path.join("..", "..", "include", "qtr_place_math.h"),
@@ -32,6 +34,7 @@ SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc"
     os.path.join("..", "..", "include", "qtr_pgo_math.h"), os.path.join("..", "..", "include", "qtr_vmap_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap.h"),
     os.path.join("..", "..", "include", "qtr_vmap_keep_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap_keep.h"),
     os.path.join("..", "..", "include", "qtr_deskew_math.h"), os.path.join("..", "..", "include", "quatro_deskew.h"),
+    os.path.join("..", "..", "include", "qtr_vmap_carve_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap_carve.h"),
     os.path.join("..", "..", "include", "quatro_hip.h")]
 
 
@@ -62,6 +65,12 @@ def build_deskew(force: bool = False, verbose: bool = True) -> str:
     return build(force, verbose, lib=DESKEW_LIB, defines=("-DQTR_DESKEW_LIB",), exports="exports_deskew.map")
 
 
+def build_voxelmap_carve(force: bool = False, verbose: bool = True) -> str:
+    build_deskew(False, verbose)  # (the five libraries come from the same sources: the other four, where they are stale)
+    return build(force, verbose, lib=VOXELMAP_CARVE_LIB, defines=("-DQTR_VOXELMAP_CARVE_LIB",),
+                 exports="exports_voxelmap_carve.map")
+
+
 def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=(), exports: str = "exports.map") -> str:
     if not force and not is_stale(lib):
         return lib
@@ -81,4 +90,5 @@ if __name__ == "__main__":
     build_voxelmap(force="--force" in sys.argv)
     build_voxelmap_keep(force="--force" in sys.argv)
     build_deskew(force="--force" in sys.argv)
+    build_voxelmap_carve(force="--force" in sys.argv)
     build_test_engines(force="--force" in sys.argv)

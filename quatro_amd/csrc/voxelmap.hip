@@ -246,6 +246,9 @@ struct qtr_voxel_map {
   int* pin = nullptr;       // pinned: the counters' read-back
   void* stage = nullptr;    // evict / restore staging for stage_cap voxels (voxelmap_keep.hip), allocated on first need
   size_t stage_cap = 0;
+  void* carve_img = nullptr;  // visibility carving (voxelmap_carve.hip): the call's poses and range images, allocated on first need
+  size_t carve_img_bytes = 0;
+  unsigned char* carve_mark = nullptr;  // ... and its verdict, one byte per table slot
   VmapView v{};
   VmapIns ins{};
   hipStream_t stream = nullptr;  // clear and fetch, which take no slot
@@ -294,6 +297,8 @@ static void vmap_release(qtr_voxel_map* m) {
   if (m->table) (void)hipFree(m->table);
   if (m->scratch) (void)hipFree(m->scratch);
   if (m->stage) (void)hipFree(m->stage);
+  if (m->carve_img) (void)hipFree(m->carve_img);
+  if (m->carve_mark) (void)hipFree(m->carve_mark);
   if (m->pin) (void)hipHostFree(m->pin);
   delete m;
 }

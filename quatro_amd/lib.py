@@ -167,8 +167,20 @@ class DeskewInfo(C.Structure):
     _fields_ = [("n_points", C.c_int), ("n_skipped", C.c_int), ("n_extrapolated", C.c_int)]
 
 
+class CarveParams(C.Structure):
+    _fields_ = [("rows", C.c_int), ("cols", C.c_int), ("window", C.c_int), ("min_votes", C.c_int),
+                ("fov_up_deg", C.c_double), ("fov_down_deg", C.c_double), ("margin_abs", C.c_double),
+                ("margin_rel", C.c_double), ("min_range", C.c_double), ("max_range", C.c_double), ("reserved", C.c_int * 8)]
+
+
+class VoxelMapCarveInfo(C.Structure):
+    _fields_ = [("n_kept", C.c_int), ("n_carved", C.c_int), ("n_tested", C.c_int), ("reserved", C.c_int),
+                ("n_members_carved", C.c_longlong)]
+
+
 KF_VOX, KF_NORMALS, KF_FPFH, KF_MEAN = 1, 2, 3, 4
 DESKEW_MAX_KNOTS = 256
+CARVE_MAX_KEYFRAMES = 64
 VMAP_COORDS, VMAP_COUNT, VMAP_SUMS, VMAP_RECORDS, VMAP_CLOUD = 1, 2, 3, 4, 5
 VMAP_MAX_CAPACITY = 1 << 24
 PLACE_DESC, PLACE_COLNORM2 = 1, 2
@@ -205,6 +217,8 @@ VOXELMAP_EXPORTS = [
 VOXELMAP_KEEP_EXPORTS = ["qtr_voxel_map_evict", "qtr_voxel_map_restore"]
 # the C ABI of include/quatro_deskew.h: libquatro_deskew.so, sweep deskew, a fourth library likewise
 DESKEW_EXPORTS = ["qtr_deskew", "qtr_keyframe_create_deskewed", "qtr_deskew_pose_at"]
+# the C ABI of include/quatro_voxelmap_carve.h: libquatro_voxelmap_carve.so, the map's visibility carving, a fifth likewise
+VOXELMAP_CARVE_EXPORTS = ["qtr_default_carve_params", "qtr_voxel_map_carve", "qtr_voxel_map_carve_keyframes"]
 
 _lib = None
 
@@ -499,6 +513,45 @@ def load_deskew():
     return lib
 
 
+VOXELMAP_CARVE_LIB_PATH = os.environ.get("QTR_VOXELMAP_CARVE_LIB") or os.path.join(_HERE, "libquatro_voxelmap_carve.so")
+_vmap_carve_lib = None
+
+
+def load_voxelmap_carve():
+    """libquatro_voxelmap_carve.so (include/quatro_voxelmap_carve.h): the map's visibility carving.  Its calls take the
+    handles, keyframes and maps of the other libraries; all come from the same build
+    (quatro_amd.build.build_voxelmap_carve)."""
+    global _vmap_carve_lib
+    if _vmap_carve_lib is not None:
+        return _vmap_carve_lib
+    load_voxelmap()
+    if not os.path.exists(VOXELMAP_CARVE_LIB_PATH):
+        raise FileNotFoundError(
+            f"{VOXELMAP_CARVE_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
+            "(or __graft_entry__.build()) first.")
+    lib = C.CDLL(VOXELMAP_CARVE_LIB_PATH)
+    lib.qtr_default_carve_params.argtypes = [C.POINTER(CarveParams)]
+    lib.qtr_default_carve_params.restype = None
+    lib.qtr_voxel_map_carve.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.POINTER(CarveParams), C.c_int, C.POINTER(VoxelMapCarveInfo)]
+    lib.qtr_voxel_map_carve_keyframes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int,
+                                                  C.POINTER(CarveParams), C.POINTER(VoxelMapCarveInfo)]
+    _vmap_carve_lib = lib
+    return lib
+
+
+def default_carve_params(**kw) -> CarveParams:
+    """qtr_default_carve_params (64 x 1024 pixels over [-25.5, 2.5] degrees, window 2, min_votes 1, margin_abs 0 = the map's
+    voxel_size, ranges 1 .. 80 m), with the given fields replaced."""
+    p = CarveParams()
+    load_voxelmap_carve().qtr_default_carve_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(CarveParams._fields_) or k == "reserved":
+            raise TypeError(f"default_carve_params: no parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
 def _knots(knot_times, knot_poses):
     """(times [K] float64, poses [K, 16] float64), contiguous host arrays."""
     kt = np.ascontiguousarray(np.asarray(knot_times, dtype=np.float64).reshape(-1))
@@ -788,6 +841,42 @@ class VoxelMap:
         info = VoxelMapEvictInfo()
         h._check(klib.qtr_voxel_map_evict(h._h, slot, self._m, C.byref(c), float(radius), C.byref(info)))
         return {n: getattr(info, n) for n, _ in VoxelMapEvictInfo._fields_}
+
+    def carve(self, xyz4, pose=None, params: "CarveParams | None" = None, slot: int = 0) -> dict:
+        """Visibility carving with one scan (qtr_voxel_map_carve): xyz4 [n, 4] float32 (numpy, or a contiguous torch device
+        tensor) taken at pose (4 x 4, scan frame -> map frame; None = identity).  A voxel whose mean the scan saw through
+        — the centre pixel of its range image is filled and no filled pixel of the window around it holds a range
+        <= r_v + margin — leaves the map; the others stay bit for bit.  Carve with the raw sweep, not a ground-removed
+        cloud.  Returns n_kept, n_carved, n_tested, n_members_carved."""
+        h, clib = self._handle, load_voxelmap_carve()
+        if isinstance(xyz4, np.ndarray) or not hasattr(xyz4, "data_ptr"):
+            xyz4 = _f4(xyz4)
+        else:
+            assert xyz4.shape[-1] == 4
+        pp, mem = _ptr(xyz4)
+        g, info = _guess16(pose), VoxelMapCarveInfo()
+        h._check(clib.qtr_voxel_map_carve(h._h, slot, self._m, pp, int(xyz4.shape[0]), None if g is None else g.ctypes.data,
+                                          None if params is None else C.byref(params), mem, C.byref(info)))
+        return self._carve_dict(info)
+
+    def carve_keyframes(self, kfs, poses, params: "CarveParams | None" = None, slot: int = 0) -> dict:
+        """Visibility carving with 0 .. 64 keyframes of this handle, each under its pose ([K, 4, 4]), their stored voxels read
+        in place (qtr_voxel_map_carve_keyframes); a voxel leaves when at least params.min_votes of them saw through it.
+        Not for merged (submap) keyframes: they have no single viewpoint."""
+        h, clib = self._handle, load_voxelmap_carve()
+        kfs = list(kfs)
+        P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 16))
+        if P.shape[0] != len(kfs):
+            raise ValueError(f"{len(kfs)} keyframes, {P.shape[0]} poses")
+        arr = (C.c_void_p * max(len(kfs), 1))(*[k._kf.value for k in kfs])
+        info = VoxelMapCarveInfo()
+        h._check(clib.qtr_voxel_map_carve_keyframes(h._h, slot, self._m, arr, P.ctypes.data, len(kfs),
+                                                    None if params is None else C.byref(params), C.byref(info)))
+        return self._carve_dict(info)
+
+    @staticmethod
+    def _carve_dict(info: "VoxelMapCarveInfo") -> dict:
+        return {n: getattr(info, n) for n in ("n_kept", "n_carved", "n_tested", "n_members_carved")}
 
     def restore(self, coords, count, sums, slot: int = 0) -> None:
         """Puts voxels given as the fetch sections VMAP_COORDS (int32 [n, 3]), VMAP_COUNT (int32 [n]) and VMAP_SUMS (float64
