@@ -15,6 +15,7 @@ in libquatro_hip.so; this module holds state and argument checks only.
 from __future__ import annotations
 
 import enum
+import math
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -609,6 +610,74 @@ def localize(handle, vmap, keyframe, guess, icp=None):
     against vmap from `guess` (4 x 4, keyframe frame -> map frame).  The map is only read.  Returns the ICP result dict; its T
     is the pose."""
     return vmap.register_keyframe(keyframe, guess, icp)
+
+
+def pose_hypothesis(base, yaw, dx=0.0, dy=0.0):
+    """qtr_vmap_hypothesis (include/qtr_vmap_batch_math.h) restated in Python floats: base . [Rz(yaw) | (dx, dy, 0)], cos
+    and sin from libm, everything else in the header's order, so C, C++ and Python give the same bits.  Pure host code: no
+    library is loaded."""
+    b = [[float(x) for x in row] for row in np.asarray(base, dtype=np.float64).reshape(4, 4)]
+    yaw, dx, dy = float(yaw), float(dx), float(dy)
+    c, s = math.cos(yaw), math.sin(yaw)
+    out = [[r[0] * c + r[1] * s, r[1] * c - r[0] * s, r[2], (r[0] * dx + r[1] * dy) + r[3]] for r in b[:3]]
+    out.append([0.0, 0.0, 0.0, 1.0])
+    return np.array(out, dtype=np.float64)
+
+
+def pose_hypotheses(base, yaws, offsets):
+    """The guesses around `base` (4 x 4, a frame -> the map frame): pose_hypothesis(base, yaw, dx, dy) for every yaw of
+    `yaws` (radians, about base's z) and every (dx, dy) of `offsets` (metres, in base's xy plane), the yaws outermost.
+    Returns [len(yaws) * len(offsets), 4, 4] float64."""
+    out = [pose_hypothesis(base, yaw, dx, dy) for yaw in yaws for dx, dy in offsets]
+    return np.stack(out) if out else np.zeros((0, 4, 4))
+
+
+def best_hypothesis(results) -> int:
+    """qtr_vmap_batch_best restated: among the ICP dicts with status 0 and valid, the largest n_corr; ties go to the smaller
+    rmse, then to the smaller index; -1 when none qualifies."""
+    best = -1
+    for i, r in enumerate(results):
+        if r.get("status", 0) != 0 or not r.get("valid"):
+            continue
+        if best < 0 or r["n_corr"] > results[best]["n_corr"] or (
+                r["n_corr"] == results[best]["n_corr"] and float(r["rmse"]) < float(results[best]["rmse"])):
+            best = i
+    return best
+
+
+def relocalize(handle, vmap, keyframe, guesses, icp=None, slot=0):
+    """Localisation of a scan in a finished map without one good guess: the scan — a Keyframe, or a pair (xyz4, normals4) of
+    a voxelised cloud with its normals — is registered against vmap from every guess of `guesses` ([G, 4, 4], scan frame ->
+    map frame) by VoxelMap.register_batch — one chain of launches per 64 guesses — and best_hypothesis picks the winner.
+    Returns {"best": its index (-1: no registration is valid), "T": its pose (None then), "results": the G ICP dicts}.
+    The map is only read."""
+    guesses = np.asarray(guesses, dtype=np.float64).reshape(-1, 4, 4)
+    scan = tuple(keyframe) if isinstance(keyframe, (tuple, list)) else (keyframe,)
+    results = vmap.register_batch([scan + (g,) for g in guesses], icp, slot)
+    best = best_hypothesis(results)
+    return {"best": best, "T": results[best]["T"] if best >= 0 else None, "results": results}
+
+
+def relocalize_in_map(handle, index, poses, vmap, query_kf, k, yaws=(0.0,), offsets=((0.0, 0.0),), icp=None, id_lo=0,
+                      id_hi=None, slot=0):
+    """Relocalisation from nothing: index.query(query_kf, k, id_lo, id_hi) names the k most similar entries with a yaw each
+    (query -> entry); poses[id] (4 x 4, entry frame -> map frame) turned by that yaw is a guess for the query's pose in the
+    map, and pose_hypotheses spreads `yaws` and `offsets` around it: len(matches) * len(yaws) * len(offsets) guesses,
+    candidates outermost, registered by relocalize.  Returns relocalize's dict plus "matches", "guesses" ([G, 4, 4]),
+    "candidate" (per guess: its position in matches) and "best_id" (the index entry the winner came from, -1 without
+    one)."""
+    matches = index.query(query_kf, k, id_lo, id_hi)
+    guesses, cand = [], []
+    for c, m in enumerate(matches):
+        base = np.asarray(poses[m["id"]], dtype=np.float64).reshape(4, 4)
+        hyp = pose_hypotheses(base, [float(m["yaw"]) + float(y) for y in yaws], offsets)
+        guesses += list(hyp)
+        cand += [c] * len(hyp)
+    guesses = np.stack(guesses) if guesses else np.zeros((0, 4, 4))
+    out = relocalize(handle, vmap, query_kf, guesses, icp, slot)
+    out.update(matches=matches, guesses=guesses, candidate=cand,
+               best_id=matches[cand[out["best"]]]["id"] if out["best"] >= 0 else -1)
+    return out
 
 
 def constant_velocity_guess(T_prev2, T_prev1):

@@ -27,6 +27,8 @@ VOXELMAP_KEEP_LIB = os.path.join(HERE, "libquatro_voxelmap_keep.so")
 DESKEW_LIB = os.path.join(HERE, "libquatro_deskew.so")
 # ... and the map's visibility carving (include/quatro_voxelmap_carve.h), a fifth
 VOXELMAP_CARVE_LIB = os.path.join(HERE, "libquatro_voxelmap_carve.so")
+# ... and the grouped map registration (include/quatro_voxelmap_batch.h), a sixth
+VOXELMAP_BATCH_LIB = os.path.join(HERE, "libquatro_voxelmap_batch.so")
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))) + [
     os.path.join("..", "..", "include", "qtr_math.h"), os.path.join("..", "..", "include", "qtr_icp_math.h"),
     os.path.join("..", "..", "include", "qtr_place_math.h"),
@@ -35,6 +37,7 @@ SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc"
     os.path.join("..", "..", "include", "qtr_vmap_keep_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap_keep.h"),
     os.path.join("..", "..", "include", "qtr_deskew_math.h"), os.path.join("..", "..", "include", "quatro_deskew.h"),
     os.path.join("..", "..", "include", "qtr_vmap_carve_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap_carve.h"),
+    os.path.join("..", "..", "include", "qtr_vmap_batch_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap_batch.h"),
     os.path.join("..", "..", "include", "quatro_hip.h")]
 
 
@@ -71,6 +74,12 @@ def build_voxelmap_carve(force: bool = False, verbose: bool = True) -> str:
                  exports="exports_voxelmap_carve.map")
 
 
+def build_voxelmap_batch(force: bool = False, verbose: bool = True) -> str:
+    build_voxelmap_carve(False, verbose)  # (the six libraries come from the same sources: the other five, where they are stale)
+    return build(force, verbose, lib=VOXELMAP_BATCH_LIB, defines=("-DQTR_VOXELMAP_BATCH_LIB",),
+                 exports="exports_voxelmap_batch.map")
+
+
 def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=(), exports: str = "exports.map") -> str:
     if not force and not is_stale(lib):
         return lib
@@ -91,4 +100,5 @@ if __name__ == "__main__":
     build_voxelmap_keep(force="--force" in sys.argv)
     build_deskew(force="--force" in sys.argv)
     build_voxelmap_carve(force="--force" in sys.argv)
+    build_voxelmap_batch(force="--force" in sys.argv)
     build_test_engines(force="--force" in sys.argv)

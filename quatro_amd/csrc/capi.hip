@@ -75,6 +75,7 @@ struct Slot {
   KfGatherMember* merge_dev = nullptr;  // (QTR_SUBMAP_MAX_KEYFRAMES records each, allocated on the slot's first merge)
   void* deskew_pin = nullptr;  // deskew.hip: the knot table and the counters' read-back in pinned host memory, and the device
   void* deskew_dev = nullptr;  // copy of the table with the counters behind it (allocated on the slot's first deskew)
+  struct VmapBatch* vbatch = nullptr;  // voxelmap_batch.hip: the slot's batch arena (allocated on the slot's first batch)
 };
 
 // What a batch lane is waiting for: the mail of the chain it enqueued last (lane_poll).
@@ -177,6 +178,7 @@ struct qtr_handle {
 
 static std::atomic<unsigned long long> g_handle_uid{0};
 static void vmap_free_all(qtr_handle* h);  // (voxelmap.hip)
+static void vmap_batch_free(Slot& s);      // (voxelmap_batch.hip)
 
 #define QTR_TRY(expr)                  \
   do {                                 \
@@ -478,6 +480,7 @@ void qtr_destroy(qtr_handle* h) {
     if (s.merge_dev) (void)hipFree(s.merge_dev);
     if (s.deskew_pin) (void)hipHostFree(s.deskew_pin);
     if (s.deskew_dev) (void)hipFree(s.deskew_dev);
+    vmap_batch_free(s);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.stream2) (void)hipStreamDestroy(s.stream2);
     if (s.stream3) (void)hipStreamDestroy(s.stream3);

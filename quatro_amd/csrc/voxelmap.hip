@@ -186,9 +186,9 @@ __device__ __forceinline__ long long d_vmap_find(const VmapView& m, u64 key) {
   return -1;
 }
 
-// one iteration of a registration against the map: d_icp_iter<3>'s frame around the hash lookup
-__global__ __launch_bounds__(256) void k_vmap_iter(IcpView v, VmapView m) {
-  const int blk = (int)blockIdx.x, nblk = (int)gridDim.x;
+// One workgroup (chunk `blk` of `nblk`) of one iteration of a registration against the map: d_icp_iter<3>'s frame around the
+// hash lookup.  Shared by k_vmap_iter and the grouped k_vmap_iter_group (voxelmap_batch.hip).
+__device__ __forceinline__ void d_vmap_iter(const IcpView& v, const VmapView& m, int blk, int nblk) {
   double T[16], o[QTR_ICP_NT];
   if (!icp_iter_begin(v, T, o)) return;
   const int i = blk * QTR_ICP_CHUNK + threadIdx.x;
@@ -212,6 +212,8 @@ __global__ __launch_bounds__(256) void k_vmap_iter(IcpView v, VmapView m) {
   }
   icp_iter_finish<QTR_ICP_T_W + 1>(v, o, blk, nblk);
 }
+
+__global__ __launch_bounds__(256) void k_vmap_iter(IcpView v, VmapView m) { d_vmap_iter(v, m, (int)blockIdx.x, (int)gridDim.x); }
 
 // a fetch section of the voxels at slots[0 .. n), in that order
 __global__ __launch_bounds__(256) void k_vmap_gather(VmapView m, const int* __restrict__ slots, int n, int what, void* out) {

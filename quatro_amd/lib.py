@@ -178,6 +178,13 @@ class VoxelMapCarveInfo(C.Structure):
                 ("n_members_carved", C.c_longlong)]
 
 
+class VmapRegItem(C.Structure):
+    _fields_ = [("kf", C.c_void_p), ("src4", C.c_void_p), ("src_normals4", C.c_void_p), ("n", C.c_int), ("mem", C.c_int),
+                ("guess", C.c_double * 16)]
+
+
+VMAP_BATCH_MAX = 64
+VMAP_BATCH_TRACE, VMAP_BATCH_CORR, VMAP_BATCH_TIMES = 1, 2, 3
 KF_VOX, KF_NORMALS, KF_FPFH, KF_MEAN = 1, 2, 3, 4
 DESKEW_MAX_KNOTS = 256
 CARVE_MAX_KEYFRAMES = 64
@@ -219,6 +226,8 @@ VOXELMAP_KEEP_EXPORTS = ["qtr_voxel_map_evict", "qtr_voxel_map_restore"]
 DESKEW_EXPORTS = ["qtr_deskew", "qtr_keyframe_create_deskewed", "qtr_deskew_pose_at"]
 # the C ABI of include/quatro_voxelmap_carve.h: libquatro_voxelmap_carve.so, the map's visibility carving, a fifth likewise
 VOXELMAP_CARVE_EXPORTS = ["qtr_default_carve_params", "qtr_voxel_map_carve", "qtr_voxel_map_carve_keyframes"]
+# the C ABI of include/quatro_voxelmap_batch.h: libquatro_voxelmap_batch.so, the grouped map registration, a sixth likewise
+VOXELMAP_BATCH_EXPORTS = ["qtr_voxel_map_register_batch", "qtr_voxel_map_batch_fetch"]
 
 _lib = None
 
@@ -540,6 +549,31 @@ def load_voxelmap_carve():
     return lib
 
 
+VOXELMAP_BATCH_LIB_PATH = os.environ.get("QTR_VOXELMAP_BATCH_LIB") or os.path.join(_HERE, "libquatro_voxelmap_batch.so")
+_vmap_batch_lib = None
+
+
+def load_voxelmap_batch():
+    """libquatro_voxelmap_batch.so (include/quatro_voxelmap_batch.h): the grouped map registration.  Its calls take the
+    handles, keyframes and maps of the other libraries; all come from the same build
+    (quatro_amd.build.build_voxelmap_batch)."""
+    global _vmap_batch_lib
+    if _vmap_batch_lib is not None:
+        return _vmap_batch_lib
+    load_voxelmap()
+    if not os.path.exists(VOXELMAP_BATCH_LIB_PATH):
+        raise FileNotFoundError(
+            f"{VOXELMAP_BATCH_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
+            "(or __graft_entry__.build()) first.")
+    lib = C.CDLL(VOXELMAP_BATCH_LIB_PATH)
+    lib.qtr_voxel_map_register_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(VmapRegItem), C.c_int,
+                                                 C.POINTER(IcpParams), C.POINTER(IcpResult)]
+    lib.qtr_voxel_map_batch_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    lib.qtr_voxel_map_batch_fetch.restype = C.c_longlong
+    _vmap_batch_lib = lib
+    return lib
+
+
 def default_carve_params(**kw) -> CarveParams:
     """qtr_default_carve_params (64 x 1024 pixels over [-25.5, 2.5] degrees, window 2, min_votes 1, margin_abs 0 = the map's
     voxel_size, ranges 1 .. 80 m), with the given fields replaced."""
@@ -813,6 +847,59 @@ class VoxelMap:
                                                     C.byref(prm), C.byref(res))
         h._check(rc)
         return _icp_dict(res)
+
+    def _batch_items(self, items):
+        """The C items of [(Keyframe, guess) | (xyz4, normals4, guess)] and the arrays that must outlive the call."""
+        arr, keep = (VmapRegItem * max(len(items), 1))(), []
+        for a, item in zip(arr, items):
+            if len(item) == 2:
+                a.kf, guess = item[0]._kf.value, item[1]
+            else:
+                keep_p, keep_n, pp, pn, mem = self._cloud(item[0], item[1])
+                keep += [keep_p, keep_n]
+                a.kf, a.src4, a.src_normals4, a.n, a.mem, guess = None, pp, pn, int(keep_p.shape[0]), mem, item[2]
+            g = np.eye(4).reshape(16) if guess is None else _guess16(guess)
+            a.guess[:] = [float(v) for v in g]
+        return arr, keep
+
+    def register_batch_raw(self, items, params: IcpParams | None = None, slot: int = 0):
+        """qtr_voxel_map_register_batch on at most VMAP_BATCH_MAX items as it stands: (return code, the IcpResult array)."""
+        h, blib = self._handle, load_voxelmap_batch()
+        prm = params or default_icp_params(method=ICP_VOXEL_PLANE_TO_PLANE)
+        items = list(items)
+        arr, keep = self._batch_items(items)
+        res = (IcpResult * max(len(items), 1))()
+        rc = blib.qtr_voxel_map_register_batch(h._h, slot, self._m, arr, len(items), C.byref(prm), res)
+        del keep
+        return rc, res
+
+    def register_batch(self, items, params: IcpParams | None = None, slot: int = 0) -> list:
+        """A batch of registrations against the map in one chain of launches (qtr_voxel_map_register_batch).  items: a list of
+        (Keyframe, guess) or (xyz4, normals4, guess), the clouds numpy arrays (host) or contiguous torch device tensors,
+        guess 4 x 4 (None = identity).  Returns one ICP dict per item, each what register / register_keyframe returns for
+        that item alone, bit for bit.  More than VMAP_BATCH_MAX items run in chunks of VMAP_BATCH_MAX in list order (then
+        batch_fetch serves the last chunk).  params None = the defaults with method = ICP_VOXEL_PLANE_TO_PLANE."""
+        items, out = list(items), []
+        for a in range(0, len(items), VMAP_BATCH_MAX):
+            chunk = items[a:a + VMAP_BATCH_MAX]
+            rc, res = self.register_batch_raw(chunk, params, slot)
+            self._handle._check(rc)
+            out += [_icp_dict(res[i]) for i in range(len(chunk))]
+        return out
+
+    def batch_fetch(self, item: int, what: int = VMAP_BATCH_TRACE, slot: int = 0) -> np.ndarray:
+        """Of item `item` of the slot's last batch (qtr_voxel_map_batch_fetch): VMAP_BATCH_TRACE -> float64 [iterations, 18],
+        VMAP_BATCH_CORR -> int32 [n] (0 matched, -1 none, at the last evaluation), VMAP_BATCH_TIMES -> float32 [2] (device ms
+        before the loop and of the loop; the whole batch's)."""
+        h, blib = self._handle, load_voxelmap_batch()
+        dtype, cols = {VMAP_BATCH_TRACE: (np.float64, 18), VMAP_BATCH_CORR: (np.int32, 0), VMAP_BATCH_TIMES: (np.float32, 0)}[what]
+        nbytes = blib.qtr_voxel_map_batch_fetch(h._h, slot, item, what, None, 0)
+        if nbytes < 0:
+            raise QuatroHipError(-1, "qtr_voxel_map_batch_fetch failed")
+        out = np.zeros(nbytes // np.dtype(dtype).itemsize, dtype=dtype)
+        if nbytes and blib.qtr_voxel_map_batch_fetch(h._h, slot, item, what, out.ctypes.data, nbytes) < 0:
+            raise QuatroHipError(-1, "qtr_voxel_map_batch_fetch failed")
+        return out.reshape(-1, cols) if cols else out
 
     def fetch(self, what: int = VMAP_CLOUD) -> np.ndarray:
         """In ascending key order: VMAP_COORDS -> int32 [n, 3], VMAP_COUNT -> int32 [n], VMAP_SUMS / VMAP_RECORDS ->
