@@ -645,27 +645,76 @@ def best_hypothesis(results) -> int:
     return best
 
 
-def relocalize(handle, vmap, keyframe, guesses, icp=None, slot=0):
+def best_evaluation(evals) -> int:
+    """qtr_vmap_eval_best (include/qtr_vmap_eval_math.h) restated: among the valid map evaluations the largest n_corr; ties
+    go to the smaller rmse, then to the smaller index; -1 when none is valid."""
+    best = -1
+    for i, e in enumerate(evals):
+        if not e.get("valid"):
+            continue
+        if best < 0 or e["n_corr"] > evals[best]["n_corr"] or (
+                e["n_corr"] == evals[best]["n_corr"] and float(e["rmse"]) < float(evals[best]["rmse"])):
+            best = i
+    return best
+
+
+def evaluation_order(evals) -> list:
+    """The indices of the map evaluations sorted by best_evaluation's rule (more n_corr, then the smaller rmse, then the
+    smaller index), the invalid ones last in index order: order[0] is best_evaluation(evals) when one is valid."""
+    good = sorted((i for i, e in enumerate(evals) if e.get("valid")),
+                  key=lambda i: (-int(evals[i]["n_corr"]), float(evals[i]["rmse"]), i))
+    return good + [i for i, e in enumerate(evals) if not e.get("valid")]
+
+
+def _scan_items(scan, guesses):
+    scan = tuple(scan) if isinstance(scan, (tuple, list)) else (scan,)
+    return [scan + (g,) for g in np.asarray(guesses, dtype=np.float64).reshape(-1, 4, 4)]
+
+
+def score_hypotheses(handle, vmap, scan, guesses, slot=0):
+    """One scan — a Keyframe, or a pair (xyz4, normals4) — evaluated against vmap under every pose of `guesses` ([G, 4, 4],
+    scan frame -> map frame) by VoxelMap.evaluate_batch: one launch per 1024 poses, nothing is iterated.  Returns
+    {"evaluations": the G evaluation dicts, "order": evaluation_order of them, "best": order[0] or -1 when none is valid}.
+    The map is only read."""
+    evals = vmap.evaluate_batch(_scan_items(scan, guesses), False, slot)
+    order = evaluation_order(evals)
+    return {"evaluations": evals, "order": order, "best": best_evaluation(evals)}
+
+
+def relocalize(handle, vmap, keyframe, guesses, icp=None, slot=0, keep=None):
     """Localisation of a scan in a finished map without one good guess: the scan — a Keyframe, or a pair (xyz4, normals4) of
     a voxelised cloud with its normals — is registered against vmap from every guess of `guesses` ([G, 4, 4], scan frame ->
     map frame) by VoxelMap.register_batch — one chain of launches per 64 guesses — and best_hypothesis picks the winner.
     Returns {"best": its index (-1: no registration is valid), "T": its pose (None then), "results": the G ICP dicts}.
+    keep = m: score_hypotheses first, then only the first m guesses of its order are registered (in index order; each is
+    bit for bit what the full batch gives it); "results" holds None for the others and the output gains "scores".  Whether
+    the eventual winner scores among the first m depends on the scene and on the grid's spacing.
     The map is only read."""
     guesses = np.asarray(guesses, dtype=np.float64).reshape(-1, 4, 4)
-    scan = tuple(keyframe) if isinstance(keyframe, (tuple, list)) else (keyframe,)
-    results = vmap.register_batch([scan + (g,) for g in guesses], icp, slot)
-    best = best_hypothesis(results)
-    return {"best": best, "T": results[best]["T"] if best >= 0 else None, "results": results}
+    items = _scan_items(keyframe, guesses)
+    if keep is None:
+        results = vmap.register_batch(items, icp, slot)
+        best = best_hypothesis(results)
+        return {"best": best, "T": results[best]["T"] if best >= 0 else None, "results": results}
+    scores = score_hypotheses(handle, vmap, keyframe, guesses, slot)
+    chosen = sorted(scores["order"][:max(int(keep), 0)])
+    sub = vmap.register_batch([items[i] for i in chosen], icp, slot)
+    results = [None] * len(items)
+    for i, r in zip(chosen, sub):
+        results[i] = r
+    b = best_hypothesis(sub)
+    best = chosen[b] if b >= 0 else -1
+    return {"best": best, "T": results[best]["T"] if best >= 0 else None, "results": results, "scores": scores}
 
 
 def relocalize_in_map(handle, index, poses, vmap, query_kf, k, yaws=(0.0,), offsets=((0.0, 0.0),), icp=None, id_lo=0,
-                      id_hi=None, slot=0):
+                      id_hi=None, slot=0, keep=None):
     """Relocalisation from nothing: index.query(query_kf, k, id_lo, id_hi) names the k most similar entries with a yaw each
     (query -> entry); poses[id] (4 x 4, entry frame -> map frame) turned by that yaw is a guess for the query's pose in the
     map, and pose_hypotheses spreads `yaws` and `offsets` around it: len(matches) * len(yaws) * len(offsets) guesses,
-    candidates outermost, registered by relocalize.  Returns relocalize's dict plus "matches", "guesses" ([G, 4, 4]),
-    "candidate" (per guess: its position in matches) and "best_id" (the index entry the winner came from, -1 without
-    one)."""
+    candidates outermost, registered by relocalize (keep: relocalize's).  Returns relocalize's dict plus "matches", "guesses"
+    ([G, 4, 4]), "candidate" (per guess: its position in matches) and "best_id" (the index entry the winner came from, -1
+    without one)."""
     matches = index.query(query_kf, k, id_lo, id_hi)
     guesses, cand = [], []
     for c, m in enumerate(matches):
@@ -674,10 +723,27 @@ def relocalize_in_map(handle, index, poses, vmap, query_kf, k, yaws=(0.0,), offs
         guesses += list(hyp)
         cand += [c] * len(hyp)
     guesses = np.stack(guesses) if guesses else np.zeros((0, 4, 4))
-    out = relocalize(handle, vmap, query_kf, guesses, icp, slot)
+    out = relocalize(handle, vmap, query_kf, guesses, icp, slot, keep)
     out.update(matches=matches, guesses=guesses, candidate=cand,
                best_id=matches[cand[out["best"]]]["id"] if out["best"] >= 0 else -1)
     return out
+
+
+def degeneracy(evaluation):
+    """How well a map evaluation's hessian (the registration's normal matrix at T: rotation first, then translation, in
+    the map's frame) constrains the pose.  Host code only.  Returns {"eigenvalues": numpy.linalg.eigvalsh of the 6 x 6,
+    ascending, "condition": largest / smallest (inf when the smallest is not positive), "translation_eigenvalues":
+    eigvalsh of the translation block after the rotation is marginalised out (H_tt - H_tr H_rr^+ H_rt), ascending,
+    "weakest_translation": the unit eigenvector of the smallest of them — along a corridor, in the plane of an open
+    field}."""
+    H = np.asarray(evaluation["hessian"], dtype=np.float64).reshape(6, 6)
+    ev = np.linalg.eigvalsh(H)
+    St = H[3:, 3:] - H[3:, :3] @ np.linalg.pinv(H[:3, :3]) @ H[:3, 3:]
+    St = 0.5 * (St + St.T)
+    tv, tvec = np.linalg.eigh(St)
+    w = tvec[:, 0] / np.linalg.norm(tvec[:, 0])
+    return {"eigenvalues": ev, "condition": float(ev[-1] / ev[0]) if ev[0] > 0.0 else float("inf"),
+            "weakest_translation": w, "translation_eigenvalues": tv}
 
 
 def constant_velocity_guess(T_prev2, T_prev1):
@@ -876,6 +942,25 @@ class PoseGraph:
         if not record.get("valid", True) or evaluation is None:
             raise ValueError("PoseGraph.add_odometry: the registration is not valid or was not evaluated")
         return self.add_edge(s, t, record["T"], evaluation["information"], False)
+
+    def add_map_node(self) -> int:
+        """A fixed node at the identity: a finished voxel map's frame.  Returns its id."""
+        return self.add_node(np.eye(4), fixed=True)
+
+    def add_localization(self, node, map_node, result, evaluation, which="information", uncertain=False) -> int:
+        """The edge of a localisation in a map: s = node, t = map_node, T = result["T"] (a VoxelMap registration's pose, node
+        frame -> map frame) and the 6 x 6 evaluation[which] of a map evaluation at that T; which: "information" (Open3D's
+        form on the matched voxel means) or "hessian" (the registration's normal matrix).  The map node sits at the
+        identity, X_t = I, so the optimiser's residual vee(X_t^-1 X_s Z^-1) vanishes at X_s = T; the matrix is formed on
+        world points, and the world is the edge's target frame, which is the frame an edge's information is expressed in.
+        Raises on an invalid result or evaluation."""
+        if which not in ("information", "hessian"):
+            raise ValueError(f"PoseGraph.add_localization: which={which!r} (\"information\" or \"hessian\")")
+        if result is None or not result.get("valid") or result.get("status", 0) != 0:
+            raise ValueError("PoseGraph.add_localization: the localisation is not valid")
+        if evaluation is None or not evaluation.get("valid") or evaluation.get("status", 0) != 0:
+            raise ValueError("PoseGraph.add_localization: the evaluation is not valid")
+        return self.add_edge(node, map_node, result["T"], evaluation[which], uncertain)
 
     def add_loop(self, query_id, loop, use="best", uncertain=True) -> int:
         """The loop edge of a close_loop(..., evaluate=...) output: query_id -> the chosen candidate's index entry.  use:

@@ -29,6 +29,8 @@ DESKEW_LIB = os.path.join(HERE, "libquatro_deskew.so")
 VOXELMAP_CARVE_LIB = os.path.join(HERE, "libquatro_voxelmap_carve.so")
 # ... and the grouped map registration (include/quatro_voxelmap_batch.h), a sixth
 VOXELMAP_BATCH_LIB = os.path.join(HERE, "libquatro_voxelmap_batch.so")
+# ... and the evaluation of poses against the map (include/quatro_voxelmap_eval.h), a seventh
+VOXELMAP_EVAL_LIB = os.path.join(HERE, "libquatro_voxelmap_eval.so")
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))) + [
     os.path.join("..", "..", "include", "qtr_math.h"), os.path.join("..", "..", "include", "qtr_icp_math.h"),
     os.path.join("..", "..", "include", "qtr_place_math.h"),
@@ -38,6 +40,7 @@ SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc"
     os.path.join("..", "..", "include", "qtr_deskew_math.h"), os.path.join("..", "..", "include", "quatro_deskew.h"),
     os.path.join("..", "..", "include", "qtr_vmap_carve_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap_carve.h"),
     os.path.join("..", "..", "include", "qtr_vmap_batch_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap_batch.h"),
+    os.path.join("..", "..", "include", "qtr_vmap_eval_math.h"), os.path.join("..", "..", "include", "quatro_voxelmap_eval.h"),
     os.path.join("..", "..", "include", "quatro_hip.h")]
 
 
@@ -80,6 +83,12 @@ def build_voxelmap_batch(force: bool = False, verbose: bool = True) -> str:
                  exports="exports_voxelmap_batch.map")
 
 
+def build_voxelmap_eval(force: bool = False, verbose: bool = True) -> str:
+    build_voxelmap_batch(False, verbose)  # (the seven libraries come from the same sources: the other six, where they are stale)
+    return build(force, verbose, lib=VOXELMAP_EVAL_LIB, defines=("-DQTR_VOXELMAP_EVAL_LIB",),
+                 exports="exports_voxelmap_eval.map")
+
+
 def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=(), exports: str = "exports.map") -> str:
     if not force and not is_stale(lib):
         return lib
@@ -101,4 +110,5 @@ if __name__ == "__main__":
     build_deskew(force="--force" in sys.argv)
     build_voxelmap_carve(force="--force" in sys.argv)
     build_voxelmap_batch(force="--force" in sys.argv)
+    build_voxelmap_eval(force="--force" in sys.argv)
     build_test_engines(force="--force" in sys.argv)

@@ -183,7 +183,20 @@ class VmapRegItem(C.Structure):
                 ("guess", C.c_double * 16)]
 
 
+class VmapEvalParams(C.Structure):
+    _fields_ = [("per_point", C.c_int), ("reserved", C.c_int * 3)]
+
+
+class VmapEvalResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("valid", C.c_int), ("n_source", C.c_int), ("n_corr", C.c_int),
+                ("overlap", C.c_double), ("sum_d2", C.c_double), ("inlier_rmse", C.c_double), ("sum_w", C.c_double),
+                ("chi2", C.c_double), ("rmse", C.c_double), ("information", C.c_double * 36), ("hessian", C.c_double * 36),
+                ("gradient", C.c_double * 6)]
+
+
 VMAP_BATCH_MAX = 64
+VMAP_EVAL_MAX = 1024
+VMAP_EVAL_CORR, VMAP_EVAL_POINT, VMAP_EVAL_TIMES = 1, 2, 3
 VMAP_BATCH_TRACE, VMAP_BATCH_CORR, VMAP_BATCH_TIMES = 1, 2, 3
 KF_VOX, KF_NORMALS, KF_FPFH, KF_MEAN = 1, 2, 3, 4
 DESKEW_MAX_KNOTS = 256
@@ -228,6 +241,9 @@ DESKEW_EXPORTS = ["qtr_deskew", "qtr_keyframe_create_deskewed", "qtr_deskew_pose
 VOXELMAP_CARVE_EXPORTS = ["qtr_default_carve_params", "qtr_voxel_map_carve", "qtr_voxel_map_carve_keyframes"]
 # the C ABI of include/quatro_voxelmap_batch.h: libquatro_voxelmap_batch.so, the grouped map registration, a sixth likewise
 VOXELMAP_BATCH_EXPORTS = ["qtr_voxel_map_register_batch", "qtr_voxel_map_batch_fetch"]
+# the C ABI of include/quatro_voxelmap_eval.h: libquatro_voxelmap_eval.so, poses evaluated against the map, a seventh likewise
+VOXELMAP_EVAL_EXPORTS = ["qtr_default_vmap_eval_params", "qtr_voxel_map_evaluate", "qtr_voxel_map_evaluate_keyframe",
+                         "qtr_voxel_map_evaluate_batch", "qtr_voxel_map_eval_fetch"]
 
 _lib = None
 
@@ -574,6 +590,51 @@ def load_voxelmap_batch():
     return lib
 
 
+VOXELMAP_EVAL_LIB_PATH = os.environ.get("QTR_VOXELMAP_EVAL_LIB") or os.path.join(_HERE, "libquatro_voxelmap_eval.so")
+_vmap_eval_lib = None
+
+
+def load_voxelmap_eval():
+    """libquatro_voxelmap_eval.so (include/quatro_voxelmap_eval.h): poses evaluated against the map.  Its calls take the
+    handles, keyframes and maps of the other libraries; all come from the same build
+    (quatro_amd.build.build_voxelmap_eval)."""
+    global _vmap_eval_lib
+    if _vmap_eval_lib is not None:
+        return _vmap_eval_lib
+    load_voxelmap()
+    if not os.path.exists(VOXELMAP_EVAL_LIB_PATH):
+        raise FileNotFoundError(
+            f"{VOXELMAP_EVAL_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
+            "(or __graft_entry__.build()) first.")
+    lib = C.CDLL(VOXELMAP_EVAL_LIB_PATH)
+    lib.qtr_default_vmap_eval_params.argtypes = [C.POINTER(VmapEvalParams)]
+    lib.qtr_default_vmap_eval_params.restype = None
+    lib.qtr_voxel_map_evaluate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                           C.c_void_p, C.POINTER(VmapEvalParams), C.POINTER(VmapEvalResult)]
+    lib.qtr_voxel_map_evaluate_keyframe.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.POINTER(VmapEvalParams), C.POINTER(VmapEvalResult)]
+    lib.qtr_voxel_map_evaluate_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(VmapRegItem), C.c_int,
+                                                 C.POINTER(VmapEvalParams), C.POINTER(VmapEvalResult)]
+    lib.qtr_voxel_map_eval_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    lib.qtr_voxel_map_eval_fetch.restype = C.c_longlong
+    _vmap_eval_lib = lib
+    return lib
+
+
+def default_vmap_eval_params(per_point: bool = False) -> VmapEvalParams:
+    p = VmapEvalParams()
+    load_voxelmap_eval().qtr_default_vmap_eval_params(C.byref(p))
+    p.per_point = 1 if per_point else 0
+    return p
+
+
+def _vmap_eval_dict(res: VmapEvalResult) -> dict:
+    return {"status": res.status, "valid": bool(res.valid), "n_source": res.n_source, "n_corr": res.n_corr,
+            "overlap": res.overlap, "sum_d2": res.sum_d2, "inlier_rmse": res.inlier_rmse, "sum_w": res.sum_w,
+            "chi2": res.chi2, "rmse": res.rmse, "information": np.array(res.information[:]).reshape(6, 6),
+            "hessian": np.array(res.hessian[:]).reshape(6, 6), "gradient": np.array(res.gradient[:])}
+
+
 def default_carve_params(**kw) -> CarveParams:
     """qtr_default_carve_params (64 x 1024 pixels over [-25.5, 2.5] degrees, window 2, min_votes 1, margin_abs 0 = the map's
     voxel_size, ranges 1 .. 80 m), with the given fields replaced."""
@@ -899,6 +960,66 @@ class VoxelMap:
         out = np.zeros(nbytes // np.dtype(dtype).itemsize, dtype=dtype)
         if nbytes and blib.qtr_voxel_map_batch_fetch(h._h, slot, item, what, out.ctypes.data, nbytes) < 0:
             raise QuatroHipError(-1, "qtr_voxel_map_batch_fetch failed")
+        return out.reshape(-1, cols) if cols else out
+
+    def evaluate(self, xyz4, normals4, T, per_point: bool = False, slot: int = 0) -> dict:
+        """The scan evaluated against the map under the pose T (4 x 4, scan frame -> map frame), without stepping it
+        (qtr_voxel_map_evaluate): valid, n_source, n_corr, overlap, sum_d2, inlier_rmse (distance to the voxel means), sum_w,
+        chi2, rmse (the registration's at T), information (6 x 6, Open3D's form, rotation first, on the voxel means), hessian
+        (the registration's normal matrix at T) and gradient.  per_point keeps the labels eval_fetch serves."""
+        h, elib = self._handle, load_voxelmap_eval()
+        keep_p, keep_n, pp, pn, mem = self._cloud(xyz4, normals4)
+        g, prm, res = _guess16(T), default_vmap_eval_params(per_point), VmapEvalResult()
+        rc = elib.qtr_voxel_map_evaluate(h._h, slot, self._m, pp, pn, int(keep_p.shape[0]), mem,
+                                         None if g is None else g.ctypes.data, C.byref(prm), C.byref(res))
+        h._check(rc)
+        return _vmap_eval_dict(res)
+
+    def evaluate_keyframe(self, kf: Keyframe, T, per_point: bool = False, slot: int = 0) -> dict:
+        """evaluate of the keyframe's stored voxels and normals, read in place (qtr_voxel_map_evaluate_keyframe)."""
+        h, elib = self._handle, load_voxelmap_eval()
+        g, prm, res = _guess16(T), default_vmap_eval_params(per_point), VmapEvalResult()
+        rc = elib.qtr_voxel_map_evaluate_keyframe(h._h, slot, self._m, kf._kf, None if g is None else g.ctypes.data,
+                                                  C.byref(prm), C.byref(res))
+        h._check(rc)
+        return _vmap_eval_dict(res)
+
+    def evaluate_batch_raw(self, items, per_point: bool = False, slot: int = 0):
+        """qtr_voxel_map_evaluate_batch on the items as they stand: (return code, the VmapEvalResult array)."""
+        h, elib = self._handle, load_voxelmap_eval()
+        items = list(items)
+        arr, keep = self._batch_items(items)
+        prm, res = default_vmap_eval_params(per_point), (VmapEvalResult * max(len(items), 1))()
+        rc = elib.qtr_voxel_map_evaluate_batch(h._h, slot, self._m, arr, len(items), C.byref(prm), res)
+        del keep
+        return rc, res
+
+    def evaluate_batch(self, items, per_point: bool = False, slot: int = 0) -> list:
+        """A batch of evaluations in one launch (qtr_voxel_map_evaluate_batch).  items: register_batch's forms, (Keyframe, T)
+        or (xyz4, normals4, T).  Returns one evaluation dict per item, each what evaluate / evaluate_keyframe returns for
+        that item alone, bit for bit.  More than the limit (VMAP_EVAL_MAX, with per_point VMAP_BATCH_MAX) run in chunks in
+        list order (then eval_fetch serves the last chunk)."""
+        items, out = list(items), []
+        lim = VMAP_BATCH_MAX if per_point else VMAP_EVAL_MAX
+        for a in range(0, len(items), lim):
+            chunk = items[a:a + lim]
+            rc, res = self.evaluate_batch_raw(chunk, per_point, slot)
+            self._handle._check(rc)
+            out += [_vmap_eval_dict(res[i]) for i in range(len(chunk))]
+        return out
+
+    def eval_fetch(self, item: int, what: int = VMAP_EVAL_CORR, slot: int = 0) -> np.ndarray:
+        """Of item `item` of the slot's last evaluation (qtr_voxel_map_eval_fetch): VMAP_EVAL_CORR -> int32 [n] (0 matched, -1
+        none), VMAP_EVAL_POINT -> float64 [n, 2] ((w d^T M d, w) of a matched point, (0, 0) otherwise; both only after a
+        per_point call), VMAP_EVAL_TIMES -> float32 [1] (device ms of the upload and the launch)."""
+        h, elib = self._handle, load_voxelmap_eval()
+        dtype, cols = {VMAP_EVAL_CORR: (np.int32, 0), VMAP_EVAL_POINT: (np.float64, 2), VMAP_EVAL_TIMES: (np.float32, 0)}[what]
+        nbytes = elib.qtr_voxel_map_eval_fetch(h._h, slot, item, what, None, 0)
+        if nbytes < 0:
+            raise QuatroHipError(-1, "qtr_voxel_map_eval_fetch failed")
+        out = np.zeros(nbytes // np.dtype(dtype).itemsize, dtype=dtype)
+        if nbytes and elib.qtr_voxel_map_eval_fetch(h._h, slot, item, what, out.ctypes.data, nbytes) < 0:
+            raise QuatroHipError(-1, "qtr_voxel_map_eval_fetch failed")
         return out.reshape(-1, cols) if cols else out
 
     def fetch(self, what: int = VMAP_CLOUD) -> np.ndarray:
