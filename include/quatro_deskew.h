@@ -1,8 +1,8 @@
-/* quatro_deskew.h - C ABI of quatro_amd/libquatro_deskew.so: motion compensation ("deskew") of a raw LiDAR sweep.
+/* quatro_deskew.h - C ABI of motion compensation ("deskew") of a raw LiDAR sweep, exported by quatro_amd/libquatro_ext.so.
  *
- * A fourth library beside libquatro_hip.so (include/quatro_hip.h), libquatro_voxelmap.so and libquatro_voxelmap_keep.so,
- * whose entry points stay exactly what they were: it is built from the same sources, works on the handles the first one
- * made, and exports the three entry points below and nothing else.  All of them must come from the same build.
+ * libquatro_ext.so is the extension library beside libquatro_hip.so (include/quatro_hip.h, whose entry points stay exactly
+ * what they were): it is built from the same sources and works on the handles libquatro_hip.so made; the three entry
+ * points below are among its exports.  Both libraries must come from the same build.
  * The contract, bit-exact in binary64, is include/qtr_deskew_math.h.
  *
  * A spinning LiDAR takes the points of one sweep at different times while the sensor moves.  Given the time of every point
@@ -40,8 +40,8 @@
 extern "C" {
 #endif
 
-#ifndef QTR_DESKEW_API /* (the other three libraries' builds hide these: they are libquatro_deskew.so's exports) */
-#define QTR_DESKEW_API QTR_API
+#ifndef QTR_EXT_API /* (the build of libquatro_hip.so itself hides these: they are libquatro_ext.so's exports) */
+#define QTR_EXT_API QTR_API
 #endif
 
 #define QTR_DESKEW_KNOTS_MAX 256
@@ -50,16 +50,16 @@ typedef struct qtr_deskew_info {
   int n_points, n_skipped, n_extrapolated;
 } qtr_deskew_info;
 
-QTR_DESKEW_API int qtr_deskew(qtr_handle* h, int slot, const float* xyz4, const float* times, int P,
-                              const double* knot_times, const double* knot_poses /* K x 16 */, int K, double t_ref,
-                              float* out_xyz4, int mem, qtr_deskew_info* info /* may be NULL */);
+QTR_EXT_API int qtr_deskew(qtr_handle* h, int slot, const float* xyz4, const float* times, int P,
+                           const double* knot_times, const double* knot_poses /* K x 16 */, int K, double t_ref,
+                           float* out_xyz4, int mem, qtr_deskew_info* info /* may be NULL */);
 
-QTR_DESKEW_API int qtr_keyframe_create_deskewed(qtr_handle* h, int slot, const float* raw4, const float* times, int P,
-                                                const double* knot_times, const double* knot_poses, int K, double t_ref,
-                                                const qtr_frontend_params* fp, int mem, qtr_keyframe** out,
-                                                qtr_deskew_info* info /* may be NULL */);
+QTR_EXT_API int qtr_keyframe_create_deskewed(qtr_handle* h, int slot, const float* raw4, const float* times, int P,
+                                             const double* knot_times, const double* knot_poses, int K, double t_ref,
+                                             const qtr_frontend_params* fp, int mem, qtr_keyframe** out,
+                                             qtr_deskew_info* info /* may be NULL */);
 
-QTR_DESKEW_API int qtr_deskew_pose_at(const double* knot_times, const double* knot_poses, int K, double t, double* T16);
+QTR_EXT_API int qtr_deskew_pose_at(const double* knot_times, const double* knot_poses, int K, double t, double* T16);
 
 #ifdef __cplusplus
 }

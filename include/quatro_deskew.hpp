@@ -1,7 +1,7 @@
 // quatro_deskew.hpp — motion compensation of a raw sweep over the process-wide handle of quatro_hip_cxx.hpp: free functions
 // over qtr_deskew / qtr_deskew_pose_at and the definition of Keyframe::create_deskewed (declared in quatro_keyframe.hpp).  A
-// header of its own because the calls are a library of their own (include/quatro_deskew.h): a program that includes only
-// quatro_keyframe.hpp still links with -lquatro_hip; one that includes this header adds -lquatro_deskew.  Host code only.
+// header of its own because the calls are the extension library's (include/quatro_deskew.h): a program that includes only
+// quatro_keyframe.hpp still links with -lquatro_hip; one that includes this header adds -lquatro_ext.  Host code only.
 #ifndef QUATRO_DESKEW_H
 #define QUATRO_DESKEW_H
 

@@ -73,7 +73,7 @@ class Keyframe {
   }
   // A keyframe of a RAW sweep of a moving sensor, deskewed on the device on its way (qtr_keyframe_create_deskewed): times = n
   // floats, the time of every point; K = knot_times.size() knots, knot_poses 16 doubles each; info (optional) receives the
-  // deskew's counts.  DEFINED in quatro_deskew.hpp: a program that calls it includes that header and adds -lquatro_deskew.
+  // deskew's counts.  DEFINED in quatro_deskew.hpp: a program that calls it includes that header and adds -lquatro_ext.
   static Keyframe create_deskewed(const float* raw4, const float* times, int n, const std::vector<double>& knot_times,
                                   const std::vector<double>& knot_poses, double t_ref, const qtr_frontend_params& fp,
                                   qtr_deskew_info* info = nullptr);

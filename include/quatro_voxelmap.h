@@ -1,10 +1,11 @@
-/* quatro_voxelmap.h - C ABI of quatro_amd/libquatro_voxelmap.so: the persistent Gaussian voxel map.
+/* quatro_voxelmap.h - C ABI of the persistent Gaussian voxel map, exported by quatro_amd/libquatro_ext.so.
  *
- * A library of its own beside libquatro_hip.so (include/quatro_hip.h, whose entry points stay exactly what they were): it
- * is built from the same sources, shares the handle, the slots, the keyframes and the slot's ICP state with it, and
- * exports the ten entry points below and nothing else.  A program creates its handle with qtr_create, links both
- * libraries and passes the handle to the calls here; qtr_last_error returns their messages and qtr_debug_fetch their
- * traces like any other call's.  Both libraries must come from the same build. */
+ * libquatro_ext.so is the extension library beside libquatro_hip.so (include/quatro_hip.h, whose entry points stay exactly
+ * what they were): it is built from the same sources, shares the handle, the slots, the keyframes and the slot's ICP state
+ * with it, and exports the entry points of this header and of the other extension headers (quatro_voxelmap_keep.h,
+ * quatro_voxelmap_carve.h, quatro_voxelmap_batch.h, quatro_voxelmap_eval.h, quatro_deskew.h) and nothing else.  A program
+ * creates its handle with qtr_create, links both libraries and passes the handle to the calls here; qtr_last_error returns
+ * their messages and qtr_debug_fetch their traces like any other call's.  Both libraries must come from the same build. */
 #ifndef QUATRO_VOXELMAP_C_H
 #define QUATRO_VOXELMAP_C_H
 
@@ -14,8 +15,8 @@
 extern "C" {
 #endif
 
-#ifndef QTR_VMAP_API /* (the build of libquatro_hip.so itself hides these: they are libquatro_voxelmap.so's exports) */
-#define QTR_VMAP_API QTR_API
+#ifndef QTR_EXT_API /* (the build of libquatro_hip.so itself hides these: they are libquatro_ext.so's exports) */
+#define QTR_EXT_API QTR_API
 #endif
 
 /* Persistent Gaussian voxel map: the world-frame map the optimised poses are for, and a refinement target that spans any
@@ -65,22 +66,22 @@ typedef struct qtr_voxel_map_insert_info {
 #define QTR_VMAP_SUMS 3    /* double[n][9] the raw sums: X (3), m m^T (00 01 02 11 12 22) */
 #define QTR_VMAP_RECORDS 4 /* double[n][9] mu (3) and C_b (6) of the finished record */
 #define QTR_VMAP_CLOUD 5   /* float4[n] mu rounded once to float, w = (float)members: the map as a point cloud */
-QTR_VMAP_API void qtr_default_voxel_map_params(qtr_voxel_map_params* p);
-QTR_VMAP_API int qtr_voxel_map_create(qtr_handle* h, const qtr_voxel_map_params* params /* NULL = defaults */, qtr_voxel_map** out);
-QTR_VMAP_API void qtr_voxel_map_destroy(qtr_handle* h, qtr_voxel_map* map);
-QTR_VMAP_API int qtr_voxel_map_clear(qtr_handle* h, int slot, qtr_voxel_map* map);
-QTR_VMAP_API int qtr_voxel_map_get_info(const qtr_voxel_map* map, qtr_voxel_map_info* info);
-QTR_VMAP_API int qtr_voxel_map_insert(qtr_handle* h, int slot, qtr_voxel_map* map, const float* xyz4, const float* normals4, int n,
-                                 const double pose[16] /* NULL = identity */, int mem,
-                                 qtr_voxel_map_insert_info* info /* may be NULL */);
-QTR_VMAP_API int qtr_voxel_map_insert_keyframe(qtr_handle* h, int slot, qtr_voxel_map* map, const qtr_keyframe* kf,
-                                          const double pose[16], qtr_voxel_map_insert_info* info);
-QTR_VMAP_API int qtr_voxel_map_register(qtr_handle* h, int slot, const qtr_voxel_map* map, const float* src4, int n,
-                                   const float* src_normals4, const double guess[16], const qtr_icp_params* prm,
-                                   qtr_icp_result* res, int mem);
-QTR_VMAP_API int qtr_voxel_map_register_keyframe(qtr_handle* h, int slot, const qtr_voxel_map* map, const qtr_keyframe* kf,
-                                            const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res);
-QTR_VMAP_API long long qtr_voxel_map_fetch(qtr_handle* h, const qtr_voxel_map* map, int what, void* dst, size_t bytes);
+QTR_EXT_API void qtr_default_voxel_map_params(qtr_voxel_map_params* p);
+QTR_EXT_API int qtr_voxel_map_create(qtr_handle* h, const qtr_voxel_map_params* params /* NULL = defaults */, qtr_voxel_map** out);
+QTR_EXT_API void qtr_voxel_map_destroy(qtr_handle* h, qtr_voxel_map* map);
+QTR_EXT_API int qtr_voxel_map_clear(qtr_handle* h, int slot, qtr_voxel_map* map);
+QTR_EXT_API int qtr_voxel_map_get_info(const qtr_voxel_map* map, qtr_voxel_map_info* info);
+QTR_EXT_API int qtr_voxel_map_insert(qtr_handle* h, int slot, qtr_voxel_map* map, const float* xyz4, const float* normals4, int n,
+                                const double pose[16] /* NULL = identity */, int mem,
+                                qtr_voxel_map_insert_info* info /* may be NULL */);
+QTR_EXT_API int qtr_voxel_map_insert_keyframe(qtr_handle* h, int slot, qtr_voxel_map* map, const qtr_keyframe* kf,
+                                         const double pose[16], qtr_voxel_map_insert_info* info);
+QTR_EXT_API int qtr_voxel_map_register(qtr_handle* h, int slot, const qtr_voxel_map* map, const float* src4, int n,
+                                  const float* src_normals4, const double guess[16], const qtr_icp_params* prm,
+                                  qtr_icp_result* res, int mem);
+QTR_EXT_API int qtr_voxel_map_register_keyframe(qtr_handle* h, int slot, const qtr_voxel_map* map, const qtr_keyframe* kf,
+                                           const double guess[16], const qtr_icp_params* prm, qtr_icp_result* res);
+QTR_EXT_API long long qtr_voxel_map_fetch(qtr_handle* h, const qtr_voxel_map* map, int what, void* dst, size_t bytes);
 
 #ifdef __cplusplus
 }

@@ -2,8 +2,8 @@
 // clouds are inserted under poses (any number of them), scans are registered against the map with the voxelised
 // plane-to-plane iteration, and the voxel means come back as the map cloud (qtr_voxel_map_*).  It is the global map after
 // optimize_pose_graph (quatro_pgo.hpp), the target of scan-to-map odometry and of localisation in a finished map.  Poses
-// are 16 row-major doubles (a quatro_hip::Pose of quatro_pgo.hpp passes as pose.data()).  Host code only; link with -lquatro_hip -lquatro_voxelmap
-// (the map's entry points are a library of their own, include/quatro_voxelmap.h).
+// are 16 row-major doubles (a quatro_hip::Pose of quatro_pgo.hpp passes as pose.data()).  Host code only; link with
+// -lquatro_hip -lquatro_ext (the map's entry points are the extension library's, include/quatro_voxelmap.h).
 #ifndef QUATRO_VOXELMAP_H
 #define QUATRO_VOXELMAP_H
 

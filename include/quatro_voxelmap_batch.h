@@ -1,10 +1,9 @@
-/* quatro_voxelmap_batch.h - C ABI of quatro_amd/libquatro_voxelmap_batch.so: a batch of scans and guesses registered
- * against one voxel map in one chain of launches.
+/* quatro_voxelmap_batch.h - C ABI of a batch of scans and guesses registered against one voxel map in one chain of
+ * launches, exported by quatro_amd/libquatro_ext.so.
  *
- * A sixth library beside libquatro_hip.so, libquatro_voxelmap.so, libquatro_voxelmap_keep.so, libquatro_deskew.so and
- * libquatro_voxelmap_carve.so, whose entry points stay exactly what they were: it is built from the same sources, works on
- * the handles, keyframes and maps the others made, and exports the two entry points below and nothing else.  All must come
- * from the same build.  The contract is include/qtr_vmap_batch_math.h.
+ * The two entry points below work on the handles and keyframes of libquatro_hip.so (include/quatro_hip.h) and the maps of
+ * include/quatro_voxelmap.h, which says what the extension library is.  Both libraries must come from the same build.  The
+ * contract is include/qtr_vmap_batch_math.h.
  *
  * Plane-to-plane against voxels of side c captures about one voxel, so finding a scan's pose in a finished map without a
  * good guess means trying many guesses: the k candidates of a place query, each with a small grid of yaw and xy offsets
@@ -40,8 +39,8 @@
 extern "C" {
 #endif
 
-#ifndef QTR_VMAP_BATCH_API /* (the other libraries' builds hide these: they are libquatro_voxelmap_batch.so's exports) */
-#define QTR_VMAP_BATCH_API QTR_API
+#ifndef QTR_EXT_API /* (the build of libquatro_hip.so itself hides these: they are libquatro_ext.so's exports) */
+#define QTR_EXT_API QTR_API
 #endif
 
 #define QTR_VMAP_BATCH_MAX 64
@@ -60,12 +59,12 @@ typedef struct qtr_vmap_reg_item {
   double guess[16];          /* rows 0 - 2 read, finite; row 3 taken as (0 0 0 1) */
 } qtr_vmap_reg_item;
 
-QTR_VMAP_BATCH_API int qtr_voxel_map_register_batch(qtr_handle* h, int slot, const qtr_voxel_map* map,
-                                                    const qtr_vmap_reg_item* items, int B, const qtr_icp_params* prm,
-                                                    qtr_icp_result* results /* [B] */);
+QTR_EXT_API int qtr_voxel_map_register_batch(qtr_handle* h, int slot, const qtr_voxel_map* map,
+                                             const qtr_vmap_reg_item* items, int B, const qtr_icp_params* prm,
+                                             qtr_icp_result* results /* [B] */);
 /* copies min(bytes, what there is) bytes to dst (may be NULL) and returns what there is; -1: a bad slot, item or `what`, or
  * no batch has run on the slot */
-QTR_VMAP_BATCH_API long long qtr_voxel_map_batch_fetch(qtr_handle* h, int slot, int item, int what, void* dst, size_t bytes);
+QTR_EXT_API long long qtr_voxel_map_batch_fetch(qtr_handle* h, int slot, int item, int what, void* dst, size_t bytes);
 
 #ifdef __cplusplus
 }

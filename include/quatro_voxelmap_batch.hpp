@@ -1,8 +1,7 @@
 // quatro_voxelmap_batch.hpp — a batch of scans and guesses registered against a quatro_hip::VoxelMap (quatro_voxelmap.hpp) in
 // one chain of launches, and the two helpers of a relocalisation, as free functions over qtr_voxel_map_register_batch,
-// qtr_vmap_hypothesis and qtr_vmap_batch_best.  A header of its own because the calls are a library of their own
-// (include/quatro_voxelmap_batch.h): a program that includes this header adds -lquatro_voxelmap_batch to -lquatro_hip
-// -lquatro_voxelmap.  Host code only.
+// qtr_vmap_hypothesis and qtr_vmap_batch_best.  The calls are the extension library's
+// (include/quatro_voxelmap_batch.h): link with -lquatro_hip -lquatro_ext.  Host code only.
 #ifndef QUATRO_VOXELMAP_BATCH_H
 #define QUATRO_VOXELMAP_BATCH_H
 

@@ -1,8 +1,7 @@
-/* quatro_voxelmap_carve.h - C ABI of quatro_amd/libquatro_voxelmap_carve.so: visibility carving of the voxel map.
+/* quatro_voxelmap_carve.h - C ABI of visibility carving of the voxel map, exported by quatro_amd/libquatro_ext.so.
  *
- * A fifth library beside libquatro_hip.so, libquatro_voxelmap.so, libquatro_voxelmap_keep.so and libquatro_deskew.so, whose
- * entry points stay exactly what they were: it is built from the same sources, works on the handles, keyframes and maps the
- * others made, and exports the three entry points below and nothing else.  All must come from the same build.
+ * The three entry points below work on the handles and keyframes of libquatro_hip.so (include/quatro_hip.h) and the maps of
+ * include/quatro_voxelmap.h, which says what the extension library is.  Both libraries must come from the same build.
  * The contract, exact in binary64, is include/qtr_vmap_carve_math.h.
  *
  * The map forgets by EVIDENCE: a voxel leaves when enough scans, taken from known poses, measured returns clearly behind it
@@ -44,8 +43,8 @@
 extern "C" {
 #endif
 
-#ifndef QTR_VMAP_CARVE_API /* (the other libraries' builds hide these: they are libquatro_voxelmap_carve.so's exports) */
-#define QTR_VMAP_CARVE_API QTR_API
+#ifndef QTR_EXT_API /* (the build of libquatro_hip.so itself hides these: they are libquatro_ext.so's exports) */
+#define QTR_EXT_API QTR_API
 #endif
 
 #define QTR_CARVE_MAX_KEYFRAMES 64
@@ -71,16 +70,16 @@ typedef struct qtr_voxel_map_carve_info {
   long long n_members_carved;  /* the carved voxels' members */
 } qtr_voxel_map_carve_info;
 
-QTR_VMAP_CARVE_API void qtr_default_carve_params(qtr_carve_params* p);
+QTR_EXT_API void qtr_default_carve_params(qtr_carve_params* p);
 /* one cloud (n records of 16 bytes, x y z and a fourth float that is not read) in host or device memory (`mem` as in
  * qtr_voxel_map_insert), taken at `pose` (row-major 4x4, scan frame -> map frame, rows 0 - 2 read; NULL = identity) */
-QTR_VMAP_CARVE_API int qtr_voxel_map_carve(qtr_handle* h, int slot, qtr_voxel_map* map, const float* xyz4, int n,
-                                           const double pose[16], const qtr_carve_params* prm /* NULL = defaults */, int mem,
-                                           qtr_voxel_map_carve_info* info /* may be NULL */);
+QTR_EXT_API int qtr_voxel_map_carve(qtr_handle* h, int slot, qtr_voxel_map* map, const float* xyz4, int n,
+                                    const double pose[16], const qtr_carve_params* prm /* NULL = defaults */, int mem,
+                                    qtr_voxel_map_carve_info* info /* may be NULL */);
 /* n_kf keyframes of this handle, their stored voxels read in place, each under its pose (poses: n_kf x 16 doubles) */
-QTR_VMAP_CARVE_API int qtr_voxel_map_carve_keyframes(qtr_handle* h, int slot, qtr_voxel_map* map, const qtr_keyframe* const* kfs,
-                                                     const double* poses, int n_kf, const qtr_carve_params* prm,
-                                                     qtr_voxel_map_carve_info* info);
+QTR_EXT_API int qtr_voxel_map_carve_keyframes(qtr_handle* h, int slot, qtr_voxel_map* map, const qtr_keyframe* const* kfs,
+                                              const double* poses, int n_kf, const qtr_carve_params* prm,
+                                              qtr_voxel_map_carve_info* info);
 
 #ifdef __cplusplus
 }

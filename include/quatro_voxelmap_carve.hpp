@@ -1,7 +1,6 @@
 // quatro_voxelmap_carve.hpp — visibility carving of a quatro_hip::VoxelMap (quatro_voxelmap.hpp): voxels that later scans see
-// through leave the map, as free functions over qtr_voxel_map_carve / qtr_voxel_map_carve_keyframes.  A header of its own
-// because the calls are a library of their own (include/quatro_voxelmap_carve.h): a program that includes this header adds
-// -lquatro_voxelmap_carve to -lquatro_hip -lquatro_voxelmap.  Host code only.
+// through leave the map, as free functions over qtr_voxel_map_carve / qtr_voxel_map_carve_keyframes.  The calls are
+// the extension library's (include/quatro_voxelmap_carve.h): link with -lquatro_hip -lquatro_ext.  Host code only.
 #ifndef QUATRO_VOXELMAP_CARVE_H
 #define QUATRO_VOXELMAP_CARVE_H
 

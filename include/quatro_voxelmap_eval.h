@@ -1,10 +1,9 @@
-/* quatro_voxelmap_eval.h - C ABI of quatro_amd/libquatro_voxelmap_eval.so: a pose evaluated against the voxel map, without
- * stepping it.
+/* quatro_voxelmap_eval.h - C ABI of a pose evaluated against the voxel map, without stepping it, exported by
+ * quatro_amd/libquatro_ext.so.
  *
- * A seventh library beside libquatro_hip.so, libquatro_voxelmap.so, libquatro_voxelmap_keep.so, libquatro_deskew.so,
- * libquatro_voxelmap_carve.so and libquatro_voxelmap_batch.so, whose entry points stay exactly what they were: it is built
- * from the same sources, works on the handles, keyframes and maps the others made, and exports the entry points below and
- * nothing else.  All must come from the same build.  The contract is include/qtr_vmap_eval_math.h.
+ * The five entry points below work on the handles and keyframes of libquatro_hip.so (include/quatro_hip.h) and the maps of
+ * include/quatro_voxelmap.h, which says what the extension library is.  Both libraries must come from the same build.  The
+ * contract is include/qtr_vmap_eval_math.h.
  *
  * What qtr_evaluate* is to a pair of clouds, this is to a scan and a map: how much of the scan lies in voxels of the map
  * under T (overlap), how far from their means (inlier_rmse), the registration's own cost at T (chi2, rmse), the 6x6
@@ -42,8 +41,8 @@
 extern "C" {
 #endif
 
-#ifndef QTR_VMAP_EVAL_API /* (the other libraries' builds hide these: they are libquatro_voxelmap_eval.so's exports) */
-#define QTR_VMAP_EVAL_API QTR_API
+#ifndef QTR_EXT_API /* (the build of libquatro_hip.so itself hides these: they are libquatro_ext.so's exports) */
+#define QTR_EXT_API QTR_API
 #endif
 
 #define QTR_VMAP_EVAL_MAX 1024 /* items of one call without per-point output (with it: QTR_VMAP_BATCH_MAX) */
@@ -73,20 +72,20 @@ typedef struct qtr_vmap_eval_result {
   double gradient[6];     /* sum w J^T M d at T */
 } qtr_vmap_eval_result;
 
-QTR_VMAP_EVAL_API void qtr_default_vmap_eval_params(qtr_vmap_eval_params* prm);
-QTR_VMAP_EVAL_API int qtr_voxel_map_evaluate(qtr_handle* h, int slot, const qtr_voxel_map* map, const float* src4,
-                                             const float* src_normals4, int n, int mem, const double T[16],
-                                             const qtr_vmap_eval_params* prm, qtr_vmap_eval_result* result);
-QTR_VMAP_EVAL_API int qtr_voxel_map_evaluate_keyframe(qtr_handle* h, int slot, const qtr_voxel_map* map, const qtr_keyframe* kf,
-                                                      const double T[16], const qtr_vmap_eval_params* prm,
-                                                      qtr_vmap_eval_result* result);
+QTR_EXT_API void qtr_default_vmap_eval_params(qtr_vmap_eval_params* prm);
+QTR_EXT_API int qtr_voxel_map_evaluate(qtr_handle* h, int slot, const qtr_voxel_map* map, const float* src4,
+                                       const float* src_normals4, int n, int mem, const double T[16],
+                                       const qtr_vmap_eval_params* prm, qtr_vmap_eval_result* result);
+QTR_EXT_API int qtr_voxel_map_evaluate_keyframe(qtr_handle* h, int slot, const qtr_voxel_map* map, const qtr_keyframe* kf,
+                                                const double T[16], const qtr_vmap_eval_params* prm,
+                                                qtr_vmap_eval_result* result);
 /* items[i].guess is the pose of item i */
-QTR_VMAP_EVAL_API int qtr_voxel_map_evaluate_batch(qtr_handle* h, int slot, const qtr_voxel_map* map,
-                                                   const qtr_vmap_reg_item* items, int B, const qtr_vmap_eval_params* prm,
-                                                   qtr_vmap_eval_result* results /* [B] */);
+QTR_EXT_API int qtr_voxel_map_evaluate_batch(qtr_handle* h, int slot, const qtr_voxel_map* map,
+                                             const qtr_vmap_reg_item* items, int B, const qtr_vmap_eval_params* prm,
+                                             qtr_vmap_eval_result* results /* [B] */);
 /* copies min(bytes, what there is) bytes to dst (may be NULL) and returns what there is; -1: a bad slot, item or `what`, no
  * evaluation has run on the slot, or a per-point section after a call that did not ask for it */
-QTR_VMAP_EVAL_API long long qtr_voxel_map_eval_fetch(qtr_handle* h, int slot, int item, int what, void* dst, size_t bytes);
+QTR_EXT_API long long qtr_voxel_map_eval_fetch(qtr_handle* h, int slot, int item, int what, void* dst, size_t bytes);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,7 @@
 // quatro_voxelmap_eval.hpp — poses evaluated against a quatro_hip::VoxelMap (quatro_voxelmap.hpp) without stepping them, as
 // free functions over qtr_voxel_map_evaluate, qtr_voxel_map_evaluate_batch and qtr_vmap_eval_best.  The items are
-// quatro_voxelmap_batch.hpp's (batch_item; the guess is the pose).  A header of its own because the calls are a library of
-// their own (include/quatro_voxelmap_eval.h): a program that includes this header adds -lquatro_voxelmap_eval to -lquatro_hip
-// -lquatro_voxelmap.  Host code only.
+// quatro_voxelmap_batch.hpp's (batch_item; the guess is the pose).  The calls are the extension library's
+// (include/quatro_voxelmap_eval.h): link with -lquatro_hip -lquatro_ext.  Host code only.
 #ifndef QUATRO_VOXELMAP_EVAL_H
 #define QUATRO_VOXELMAP_EVAL_H
 

@@ -1,8 +1,7 @@
-/* quatro_voxelmap_keep.h - C ABI of quatro_amd/libquatro_voxelmap_keep.so: the voxel map's upkeep.
+/* quatro_voxelmap_keep.h - C ABI of the voxel map's upkeep, exported by quatro_amd/libquatro_ext.so.
  *
- * A third library beside libquatro_hip.so (include/quatro_hip.h) and libquatro_voxelmap.so (include/quatro_voxelmap.h),
- * whose entry points stay exactly what they were: it is built from the same sources, works on the handles and maps the
- * other two made, and exports the two entry points below and nothing else.  All three must come from the same build.
+ * The two entry points below work on the handles of libquatro_hip.so (include/quatro_hip.h) and the maps of
+ * include/quatro_voxelmap.h, which says what the extension library is.  Both libraries must come from the same build.
  * The contract, exact in integers, is include/qtr_vmap_keep_math.h.
  *   evict    sliding-window eviction: with C = floor(centre / voxel_size) per axis and R = floor(radius / voxel_size), a
  *            voxel with coordinates i stays iff |i - C|^2 <= R^2 (int64).  The map afterwards is the map before without the
@@ -32,8 +31,8 @@
 extern "C" {
 #endif
 
-#ifndef QTR_VMAP_KEEP_API /* (the other two libraries' builds hide these: they are libquatro_voxelmap_keep.so's exports) */
-#define QTR_VMAP_KEEP_API QTR_API
+#ifndef QTR_EXT_API /* (the build of libquatro_hip.so itself hides these: they are libquatro_ext.so's exports) */
+#define QTR_EXT_API QTR_API
 #endif
 
 typedef struct qtr_voxel_map_evict_info {
@@ -41,10 +40,10 @@ typedef struct qtr_voxel_map_evict_info {
   long long n_members_evicted; /* their members */
 } qtr_voxel_map_evict_info;
 
-QTR_VMAP_KEEP_API int qtr_voxel_map_evict(qtr_handle* h, int slot, qtr_voxel_map* map, const double centre[3], double radius,
-                                          qtr_voxel_map_evict_info* info /* may be NULL */);
-QTR_VMAP_KEEP_API int qtr_voxel_map_restore(qtr_handle* h, int slot, qtr_voxel_map* map, const int* coords, const int* count,
-                                            const double* sums, int n, int mem);
+QTR_EXT_API int qtr_voxel_map_evict(qtr_handle* h, int slot, qtr_voxel_map* map, const double centre[3], double radius,
+                                    qtr_voxel_map_evict_info* info /* may be NULL */);
+QTR_EXT_API int qtr_voxel_map_restore(qtr_handle* h, int slot, qtr_voxel_map* map, const int* coords, const int* count,
+                                      const double* sums, int n, int mem);
 
 #ifdef __cplusplus
 }

@@ -1,8 +1,6 @@
 // quatro_voxelmap_keep.hpp — upkeep of a quatro_hip::VoxelMap (quatro_voxelmap.hpp): sliding-window eviction and restore
-// from fetched sections, as free functions over qtr_voxel_map_evict / qtr_voxel_map_restore.  A header of its own because
-// the two calls are a library of their own (include/quatro_voxelmap_keep.h): a program that includes only
-// quatro_voxelmap.hpp still links with -lquatro_hip -lquatro_voxelmap; one that includes this header adds
-// -lquatro_voxelmap_keep.  Host code only.
+// from fetched sections, as free functions over qtr_voxel_map_evict / qtr_voxel_map_restore.  The two calls
+// are the extension library's (include/quatro_voxelmap_keep.h): link with -lquatro_hip -lquatro_ext.  Host code only.
 #ifndef QUATRO_VOXELMAP_KEEP_H
 #define QUATRO_VOXELMAP_KEEP_H
 

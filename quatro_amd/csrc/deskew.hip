@@ -1,8 +1,8 @@
 // deskew.hip — motion compensation of a raw sweep on the device (qtr_deskew / qtr_keyframe_create_deskewed /
 // qtr_deskew_pose_at, include/quatro_deskew.h).  The contract is include/qtr_deskew_math.h.
 //
-// The three entry points are the exports of a fourth library, libquatro_deskew.so: the same unity.hip built with
-// -DQTR_DESKEW_LIB and exports_deskew.map; the other three libraries carry this code hidden and export none of it.
+// The three entry points are exports of the extension library, libquatro_ext.so (voxelmap.hip says how it is built);
+// libquatro_hip.so carries this code hidden and exports none of it.
 //
 // The knot table — per interval tau_j, the divisor tau_{j+1} - tau_j, R_j, c_j, c_{j+1} - c_j and w_j = Log(R_j^T R_{j+1}),
 // in front of it the reference pose — is computed by the HOST with qtr_deskew_table, the header's own function, into the
@@ -18,9 +18,6 @@
 // already staged (front_one_chain), as qtr_keyframe_merge does; the counts travel to pinned memory on the same stream and
 // are read after the waits that chain has anyway.
 // No kernel waits for another workgroup, none is launched cooperatively, all stores are plain vector stores.
-#ifndef QTR_DESKEW_LIB
-#define QTR_DESKEW_API __attribute__((visibility("hidden")))
-#endif
 #include "../../include/quatro_deskew.h"
 #include "../../include/qtr_deskew_math.h"
 

@@ -1,4 +1,8 @@
-// unity.hip — single translation unit of libquatro_hip.so (all kernels + the C ABI).
+// unity.hip — single translation unit of libquatro_hip.so (all kernels + the C ABI) and, with -DQTR_EXT_LIB and
+// exports_ext.map, of libquatro_ext.so: the same code with the entry points of the extension headers visible.
+#ifndef QTR_EXT_LIB  // libquatro_hip.so carries the extension code (its handle frees the maps) but exports none of it
+#define QTR_EXT_API __attribute__((visibility("hidden")))
+#endif
 #include "solver.hip"
 #include "exact.hip"
 #include "stages.hip"

@@ -2,10 +2,11 @@
 // HBM between calls.  Clouds and keyframes are inserted under poses, scans are registered against it with the VGICP
 // iteration of icp.hip, and the voxel means come back as the map cloud.  The arithmetic is include/qtr_vmap_math.h.
 //
-// The entry points are the exports of a library of their own, libquatro_voxelmap.so: the same unity.hip built with
-// -DQTR_VOXELMAP_LIB and exports_voxelmap.map, so that it shares every structure of the handle with libquatro_hip.so, whose
-// own symbol table stays the C ABI of include/quatro_hip.h.  A handle made by one library is used by the other: both run the
-// same code on the same HIP runtime, and nothing here touches a file-scope variable of capi.hip.
+// The entry points are exports of the extension library, libquatro_ext.so: the same unity.hip built with -DQTR_EXT_LIB and
+// exports_ext.map, so that it shares every structure of the handle with libquatro_hip.so, whose own symbol table stays the
+// C ABI of include/quatro_hip.h.  A handle made by the product library is used by the extension library: both run the same
+// code on the same HIP runtime, and no extension entry point touches a file-scope variable of capi.hip or solver.hip (each
+// library has its own copy of g_handle_uid and t_hca_share; only the product library's are ever used).
 //
 // Table: open addressing with linear probing over S slots (a power of two >= 2 x capacity), 64-bit keys, QTR_VMAP_EMPTY for
 // a free slot.  Everything a voxel owns lives at its slot: member count, the raw sums acc[9] and the FINISHED record
@@ -32,9 +33,6 @@
 // between the iteration frame of icp.hip (icp_iter_begin / icp_iter_finish: the stop flag's early return, T, the reduction
 // tail, the step, the trace row, the ticket); the host side is capi.hip's icp_loop on the slot's IcpBufs with the empty grid
 // and this kernel as its launch.  Lookups are plain loads: the table was written by earlier launches.
-#ifndef QTR_VOXELMAP_LIB  // libquatro_hip.so carries this code (its handle frees the maps) but exports none of it
-#define QTR_VMAP_API __attribute__((visibility("hidden")))
-#endif
 #include "../../include/quatro_voxelmap.h"
 #include "../../include/qtr_vmap_math.h"
 

@@ -2,9 +2,8 @@
 // (qtr_voxel_map_register_batch / qtr_voxel_map_batch_fetch, include/quatro_voxelmap_batch.h).  The contract is
 // include/qtr_vmap_batch_math.h: item i IS qtr_voxel_map_register with its cloud and guess, bit for bit.
 //
-// The two entry points are the exports of a sixth library, libquatro_voxelmap_batch.so: the same unity.hip built with
-// -DQTR_VOXELMAP_BATCH_LIB and exports_voxelmap_batch.map; the other five libraries carry this code hidden and export none
-// of it.
+// The two entry points are exports of the extension library, libquatro_ext.so (voxelmap.hip says how it is built);
+// libquatro_hip.so carries this code hidden and exports none of it.
 //
 // A call with B items:
 //   (copies)            host-resident clouds into the slot's batch arena (one copy per distinct cloud), the B views and
@@ -27,9 +26,6 @@
 // call's need, freed with the handle.
 // The map is only read.  No kernel waits for another workgroup, none is launched cooperatively, all stores are plain vector
 // stores.
-#ifndef QTR_VOXELMAP_BATCH_LIB
-#define QTR_VMAP_BATCH_API __attribute__((visibility("hidden")))
-#endif
 #include "../../include/quatro_voxelmap_batch.h"
 #include "../../include/qtr_vmap_batch_math.h"
 

@@ -2,9 +2,8 @@
 // scans, taken from known poses, measured returns clearly behind it (qtr_voxel_map_carve / qtr_voxel_map_carve_keyframes,
 // include/quatro_voxelmap_carve.h).  The contract is include/qtr_vmap_carve_math.h.
 //
-// The three entry points are the exports of a fifth library, libquatro_voxelmap_carve.so: the same unity.hip built with
-// -DQTR_VOXELMAP_CARVE_LIB and exports_voxelmap_carve.map; the other four libraries carry this code hidden and export none
-// of it.
+// The three entry points are exports of the extension library, libquatro_ext.so (voxelmap.hip says how it is built);
+// libquatro_hip.so carries this code hidden and exports none of it.
 //
 // A call with B scans (one cloud, or 1 .. 64 keyframes read in place):
 //   (memset)        the B images to QTR_CARVE_EMPTY, one hipMemsetAsync
@@ -26,9 +25,6 @@
 // Memory: 64 poses (6 KiB) and B x rows x cols x 4 bytes of images in one allocation, one byte per table slot in
 // another; both made on the first call that needs them, grown only, freed with the map.
 // No kernel waits for another workgroup, none is launched cooperatively, all stores are plain vector stores.
-#ifndef QTR_VOXELMAP_CARVE_LIB
-#define QTR_VMAP_CARVE_API __attribute__((visibility("hidden")))
-#endif
 #include "../../include/quatro_voxelmap_carve.h"
 #include "../../include/qtr_vmap_carve_math.h"
 

@@ -3,8 +3,8 @@
 // registration's match rule and terms at a fixed T, the voxel means' sums beside them, the registration's sum shape, and
 // qtr_vmap_eval_finish.
 //
-// The entry points are the exports of a seventh library, libquatro_voxelmap_eval.so: the same unity.hip built with
-// -DQTR_VOXELMAP_EVAL_LIB and exports_voxelmap_eval.map; the other six libraries carry this code hidden and export none of it.
+// The entry points are exports of the extension library, libquatro_ext.so (voxelmap.hip says how it is built);
+// libquatro_hip.so carries this code hidden and exports none of it.
 //
 // A call with B items (the single entries are B = 1):
 //   (copies)            host-resident clouds into the slot's evaluation arena (one copy per distinct cloud); the B views, each
@@ -24,9 +24,6 @@
 // share one staged copy.  Allocated on the slot's first evaluation, grown to a call's need, freed with the handle.
 // The map is only read.  No kernel waits for another workgroup, none is launched cooperatively, all stores are plain vector
 // stores.
-#ifndef QTR_VOXELMAP_EVAL_LIB
-#define QTR_VMAP_EVAL_API __attribute__((visibility("hidden")))
-#endif
 #include "../../include/quatro_voxelmap_eval.h"
 #include "../../include/qtr_vmap_eval_math.h"
 

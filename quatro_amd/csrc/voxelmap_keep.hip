@@ -2,8 +2,8 @@
 // sections (qtr_voxel_map_evict / qtr_voxel_map_restore, include/quatro_voxelmap_keep.h).  The contract is
 // include/qtr_vmap_keep_math.h.
 //
-// The two entry points are the exports of a third library, libquatro_voxelmap_keep.so: the same unity.hip built with
-// -DQTR_VOXELMAP_KEEP_LIB and exports_voxelmap_keep.map; the other two libraries carry this code hidden and export none of it.
+// The two entry points are exports of the extension library, libquatro_ext.so (voxelmap.hip says how it is built);
+// libquatro_hip.so carries this code hidden and exports none of it.
 //
 // The table is open addressing with linear probing and d_vmap_find stops at the first empty slot, so a voxel is never
 // deleted in place: a hole would cut every probe chain that runs through it.  Both entries end in the same device path
@@ -30,9 +30,6 @@
 // Staging: 164 bytes per voxel (key 8, acc 72, record 80, count 4) + 64 bytes of counters, allocated on first need for the
 // map's n_voxels (evict) or n (restore), never for the table, and grown only.
 // No kernel waits for another workgroup, none is launched cooperatively, all stores are plain vector stores.
-#ifndef QTR_VOXELMAP_KEEP_LIB
-#define QTR_VMAP_KEEP_API __attribute__((visibility("hidden")))
-#endif
 #include "../../include/quatro_voxelmap_keep.h"
 #include "../../include/qtr_vmap_keep_math.h"
 

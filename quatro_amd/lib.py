@@ -227,23 +227,20 @@ EXPORTS = [
     "qtr_evaluate_keyframes_batch",
     "qtr_default_pgo_params", "qtr_pgo_optimize",
 ]
-# the C ABI of include/quatro_voxelmap.h: libquatro_voxelmap.so, a library of its own over the same handle
-VOXELMAP_EXPORTS = [
+# the C ABI of the six extension headers, per header; libquatro_ext.so exports their concatenation over the same handle
+VOXELMAP_EXPORTS = [  # include/quatro_voxelmap.h
     "qtr_default_voxel_map_params", "qtr_voxel_map_create", "qtr_voxel_map_destroy", "qtr_voxel_map_clear",
     "qtr_voxel_map_get_info", "qtr_voxel_map_insert", "qtr_voxel_map_insert_keyframe", "qtr_voxel_map_register",
     "qtr_voxel_map_register_keyframe", "qtr_voxel_map_fetch",
 ]
-# the C ABI of include/quatro_voxelmap_keep.h: libquatro_voxelmap_keep.so, the map's upkeep, a third library likewise
-VOXELMAP_KEEP_EXPORTS = ["qtr_voxel_map_evict", "qtr_voxel_map_restore"]
-# the C ABI of include/quatro_deskew.h: libquatro_deskew.so, sweep deskew, a fourth library likewise
-DESKEW_EXPORTS = ["qtr_deskew", "qtr_keyframe_create_deskewed", "qtr_deskew_pose_at"]
-# the C ABI of include/quatro_voxelmap_carve.h: libquatro_voxelmap_carve.so, the map's visibility carving, a fifth likewise
-VOXELMAP_CARVE_EXPORTS = ["qtr_default_carve_params", "qtr_voxel_map_carve", "qtr_voxel_map_carve_keyframes"]
-# the C ABI of include/quatro_voxelmap_batch.h: libquatro_voxelmap_batch.so, the grouped map registration, a sixth likewise
-VOXELMAP_BATCH_EXPORTS = ["qtr_voxel_map_register_batch", "qtr_voxel_map_batch_fetch"]
-# the C ABI of include/quatro_voxelmap_eval.h: libquatro_voxelmap_eval.so, poses evaluated against the map, a seventh likewise
+VOXELMAP_KEEP_EXPORTS = ["qtr_voxel_map_evict", "qtr_voxel_map_restore"]  # include/quatro_voxelmap_keep.h
+DESKEW_EXPORTS = ["qtr_deskew", "qtr_keyframe_create_deskewed", "qtr_deskew_pose_at"]  # include/quatro_deskew.h
+VOXELMAP_CARVE_EXPORTS = ["qtr_default_carve_params", "qtr_voxel_map_carve", "qtr_voxel_map_carve_keyframes"]  # ..._carve.h
+VOXELMAP_BATCH_EXPORTS = ["qtr_voxel_map_register_batch", "qtr_voxel_map_batch_fetch"]  # include/quatro_voxelmap_batch.h
 VOXELMAP_EVAL_EXPORTS = ["qtr_default_vmap_eval_params", "qtr_voxel_map_evaluate", "qtr_voxel_map_evaluate_keyframe",
-                         "qtr_voxel_map_evaluate_batch", "qtr_voxel_map_eval_fetch"]
+                         "qtr_voxel_map_evaluate_batch", "qtr_voxel_map_eval_fetch"]  # include/quatro_voxelmap_eval.h
+EXT_EXPORTS = (VOXELMAP_EXPORTS + VOXELMAP_KEEP_EXPORTS + DESKEW_EXPORTS + VOXELMAP_CARVE_EXPORTS + VOXELMAP_BATCH_EXPORTS
+               + VOXELMAP_EVAL_EXPORTS)
 
 _lib = None
 
@@ -451,22 +448,22 @@ def load(path: str | None = None):
     return lib
 
 
-VOXELMAP_LIB_PATH = os.environ.get("QTR_VOXELMAP_LIB") or os.path.join(_HERE, "libquatro_voxelmap.so")
-_vmap_lib = None
+EXT_LIB_PATH = os.environ.get("QTR_EXT_LIB") or os.path.join(_HERE, "libquatro_ext.so")
+_ext_lib = None
 
 
-def load_voxelmap():
-    """libquatro_voxelmap.so (include/quatro_voxelmap.h): the voxel map's entry points.  They take the handles of load()'s
-    library; both come from the same build (quatro_amd.build.build_voxelmap)."""
-    global _vmap_lib
-    if _vmap_lib is not None:
-        return _vmap_lib
+def load_ext():
+    """libquatro_ext.so: the entry points of the six extension headers (EXT_EXPORTS).  They take the handles, keyframes and
+    maps of load()'s library; both come from the same build (quatro_amd.build.build_ext)."""
+    global _ext_lib
+    if _ext_lib is not None:
+        return _ext_lib
     load()  # (first: one HIP runtime per process)
-    if not os.path.exists(VOXELMAP_LIB_PATH):
+    if not os.path.exists(EXT_LIB_PATH):
         raise FileNotFoundError(
-            f"{VOXELMAP_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
+            f"{EXT_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
             "(or __graft_entry__.build()) first.")
-    lib = C.CDLL(VOXELMAP_LIB_PATH)
+    lib = C.CDLL(EXT_LIB_PATH)
     lib.qtr_default_voxel_map_params.argtypes = [C.POINTER(VoxelMapParams)]
     lib.qtr_default_voxel_map_params.restype = None
     lib.qtr_voxel_map_create.argtypes = [C.c_void_p, C.POINTER(VoxelMapParams), C.POINTER(C.c_void_p)]
@@ -484,129 +481,25 @@ def load_voxelmap():
                                                     C.POINTER(IcpParams), C.POINTER(IcpResult)]
     lib.qtr_voxel_map_fetch.restype = C.c_longlong
     lib.qtr_voxel_map_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
-    _vmap_lib = lib
-    return lib
-
-
-VOXELMAP_KEEP_LIB_PATH = os.environ.get("QTR_VOXELMAP_KEEP_LIB") or os.path.join(_HERE, "libquatro_voxelmap_keep.so")
-_vmap_keep_lib = None
-
-
-def load_voxelmap_keep():
-    """libquatro_voxelmap_keep.so (include/quatro_voxelmap_keep.h): the map's upkeep, evict and restore.  They take the
-    handles and maps of the other two libraries; all three come from the same build
-    (quatro_amd.build.build_voxelmap_keep)."""
-    global _vmap_keep_lib
-    if _vmap_keep_lib is not None:
-        return _vmap_keep_lib
-    load_voxelmap()
-    if not os.path.exists(VOXELMAP_KEEP_LIB_PATH):
-        raise FileNotFoundError(
-            f"{VOXELMAP_KEEP_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
-            "(or __graft_entry__.build()) first.")
-    lib = C.CDLL(VOXELMAP_KEEP_LIB_PATH)
     lib.qtr_voxel_map_evict.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double * 3), C.c_double,
                                         C.POINTER(VoxelMapEvictInfo)]
     lib.qtr_voxel_map_restore.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-    _vmap_keep_lib = lib
-    return lib
-
-
-DESKEW_LIB_PATH = os.environ.get("QTR_DESKEW_LIB") or os.path.join(_HERE, "libquatro_deskew.so")
-_deskew_lib = None
-
-
-def load_deskew():
-    """libquatro_deskew.so (include/quatro_deskew.h): motion compensation of a raw sweep.  Its calls take the handles of
-    libquatro_hip.so; both come from the same build (quatro_amd.build.build_deskew)."""
-    global _deskew_lib
-    if _deskew_lib is not None:
-        return _deskew_lib
-    load()
-    if not os.path.exists(DESKEW_LIB_PATH):
-        raise FileNotFoundError(
-            f"{DESKEW_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
-            "(or __graft_entry__.build()) first.")
-    lib = C.CDLL(DESKEW_LIB_PATH)
     lib.qtr_deskew.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                C.c_double, C.c_void_p, C.c_int, C.POINTER(DeskewInfo)]
     lib.qtr_keyframe_create_deskewed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                                  C.c_int, C.c_double, C.POINTER(FrontendParams), C.c_int,
                                                  C.POINTER(C.c_void_p), C.POINTER(DeskewInfo)]
     lib.qtr_deskew_pose_at.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p]
-    _deskew_lib = lib
-    return lib
-
-
-VOXELMAP_CARVE_LIB_PATH = os.environ.get("QTR_VOXELMAP_CARVE_LIB") or os.path.join(_HERE, "libquatro_voxelmap_carve.so")
-_vmap_carve_lib = None
-
-
-def load_voxelmap_carve():
-    """libquatro_voxelmap_carve.so (include/quatro_voxelmap_carve.h): the map's visibility carving.  Its calls take the
-    handles, keyframes and maps of the other libraries; all come from the same build
-    (quatro_amd.build.build_voxelmap_carve)."""
-    global _vmap_carve_lib
-    if _vmap_carve_lib is not None:
-        return _vmap_carve_lib
-    load_voxelmap()
-    if not os.path.exists(VOXELMAP_CARVE_LIB_PATH):
-        raise FileNotFoundError(
-            f"{VOXELMAP_CARVE_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
-            "(or __graft_entry__.build()) first.")
-    lib = C.CDLL(VOXELMAP_CARVE_LIB_PATH)
     lib.qtr_default_carve_params.argtypes = [C.POINTER(CarveParams)]
     lib.qtr_default_carve_params.restype = None
     lib.qtr_voxel_map_carve.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                         C.POINTER(CarveParams), C.c_int, C.POINTER(VoxelMapCarveInfo)]
     lib.qtr_voxel_map_carve_keyframes.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_int,
                                                   C.POINTER(CarveParams), C.POINTER(VoxelMapCarveInfo)]
-    _vmap_carve_lib = lib
-    return lib
-
-
-VOXELMAP_BATCH_LIB_PATH = os.environ.get("QTR_VOXELMAP_BATCH_LIB") or os.path.join(_HERE, "libquatro_voxelmap_batch.so")
-_vmap_batch_lib = None
-
-
-def load_voxelmap_batch():
-    """libquatro_voxelmap_batch.so (include/quatro_voxelmap_batch.h): the grouped map registration.  Its calls take the
-    handles, keyframes and maps of the other libraries; all come from the same build
-    (quatro_amd.build.build_voxelmap_batch)."""
-    global _vmap_batch_lib
-    if _vmap_batch_lib is not None:
-        return _vmap_batch_lib
-    load_voxelmap()
-    if not os.path.exists(VOXELMAP_BATCH_LIB_PATH):
-        raise FileNotFoundError(
-            f"{VOXELMAP_BATCH_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
-            "(or __graft_entry__.build()) first.")
-    lib = C.CDLL(VOXELMAP_BATCH_LIB_PATH)
     lib.qtr_voxel_map_register_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(VmapRegItem), C.c_int,
                                                  C.POINTER(IcpParams), C.POINTER(IcpResult)]
     lib.qtr_voxel_map_batch_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     lib.qtr_voxel_map_batch_fetch.restype = C.c_longlong
-    _vmap_batch_lib = lib
-    return lib
-
-
-VOXELMAP_EVAL_LIB_PATH = os.environ.get("QTR_VOXELMAP_EVAL_LIB") or os.path.join(_HERE, "libquatro_voxelmap_eval.so")
-_vmap_eval_lib = None
-
-
-def load_voxelmap_eval():
-    """libquatro_voxelmap_eval.so (include/quatro_voxelmap_eval.h): poses evaluated against the map.  Its calls take the
-    handles, keyframes and maps of the other libraries; all come from the same build
-    (quatro_amd.build.build_voxelmap_eval)."""
-    global _vmap_eval_lib
-    if _vmap_eval_lib is not None:
-        return _vmap_eval_lib
-    load_voxelmap()
-    if not os.path.exists(VOXELMAP_EVAL_LIB_PATH):
-        raise FileNotFoundError(
-            f"{VOXELMAP_EVAL_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
-            "(or __graft_entry__.build()) first.")
-    lib = C.CDLL(VOXELMAP_EVAL_LIB_PATH)
     lib.qtr_default_vmap_eval_params.argtypes = [C.POINTER(VmapEvalParams)]
     lib.qtr_default_vmap_eval_params.restype = None
     lib.qtr_voxel_map_evaluate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -617,13 +510,13 @@ def load_voxelmap_eval():
                                                  C.POINTER(VmapEvalParams), C.POINTER(VmapEvalResult)]
     lib.qtr_voxel_map_eval_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     lib.qtr_voxel_map_eval_fetch.restype = C.c_longlong
-    _vmap_eval_lib = lib
+    _ext_lib = lib
     return lib
 
 
 def default_vmap_eval_params(per_point: bool = False) -> VmapEvalParams:
     p = VmapEvalParams()
-    load_voxelmap_eval().qtr_default_vmap_eval_params(C.byref(p))
+    load_ext().qtr_default_vmap_eval_params(C.byref(p))
     p.per_point = 1 if per_point else 0
     return p
 
@@ -639,7 +532,7 @@ def default_carve_params(**kw) -> CarveParams:
     """qtr_default_carve_params (64 x 1024 pixels over [-25.5, 2.5] degrees, window 2, min_votes 1, margin_abs 0 = the map's
     voxel_size, ranges 1 .. 80 m), with the given fields replaced."""
     p = CarveParams()
-    load_voxelmap_carve().qtr_default_carve_params(C.byref(p))
+    load_ext().qtr_default_carve_params(C.byref(p))
     for k, v in kw.items():
         if k not in dict(CarveParams._fields_) or k == "reserved":
             raise TypeError(f"default_carve_params: no parameter {k!r}")
@@ -661,7 +554,7 @@ def deskew_pose_at(knot_times, knot_poses, t: float) -> np.ndarray:
     geodesic of the knot interval, translation linearly, the first / last interval extrapolated outside the knots."""
     kt, kp = _knots(knot_times, knot_poses)
     T = np.zeros(16, dtype=np.float64)
-    rc = load_deskew().qtr_deskew_pose_at(kt.ctypes.data, kp.ctypes.data, int(kt.shape[0]), float(t), T.ctypes.data)
+    rc = load_ext().qtr_deskew_pose_at(kt.ctypes.data, kp.ctypes.data, int(kt.shape[0]), float(t), T.ctypes.data)
     if rc != QTR_OK:
         raise QuatroHipError(rc, "qtr_deskew_pose_at: the knots are refused (2 .. 256 of them, finite and strictly increasing "
                                  "times, finite poses, at most pi / 2 of rotation between two)")
@@ -842,7 +735,7 @@ class VoxelMap:
     insert / insert_keyframe / clear are the caller's to serialise."""
 
     def __init__(self, handle: "Handle", ptr: int):
-        self._handle, self._m, self._vlib = handle, C.c_void_p(ptr), load_voxelmap()
+        self._handle, self._m, self._vlib = handle, C.c_void_p(ptr), load_ext()
 
     def info(self) -> dict:
         info = VoxelMapInfo()
@@ -925,7 +818,7 @@ class VoxelMap:
 
     def register_batch_raw(self, items, params: IcpParams | None = None, slot: int = 0):
         """qtr_voxel_map_register_batch on at most VMAP_BATCH_MAX items as it stands: (return code, the IcpResult array)."""
-        h, blib = self._handle, load_voxelmap_batch()
+        h, blib = self._handle, load_ext()
         prm = params or default_icp_params(method=ICP_VOXEL_PLANE_TO_PLANE)
         items = list(items)
         arr, keep = self._batch_items(items)
@@ -952,7 +845,7 @@ class VoxelMap:
         """Of item `item` of the slot's last batch (qtr_voxel_map_batch_fetch): VMAP_BATCH_TRACE -> float64 [iterations, 18],
         VMAP_BATCH_CORR -> int32 [n] (0 matched, -1 none, at the last evaluation), VMAP_BATCH_TIMES -> float32 [2] (device ms
         before the loop and of the loop; the whole batch's)."""
-        h, blib = self._handle, load_voxelmap_batch()
+        h, blib = self._handle, load_ext()
         dtype, cols = {VMAP_BATCH_TRACE: (np.float64, 18), VMAP_BATCH_CORR: (np.int32, 0), VMAP_BATCH_TIMES: (np.float32, 0)}[what]
         nbytes = blib.qtr_voxel_map_batch_fetch(h._h, slot, item, what, None, 0)
         if nbytes < 0:
@@ -967,7 +860,7 @@ class VoxelMap:
         (qtr_voxel_map_evaluate): valid, n_source, n_corr, overlap, sum_d2, inlier_rmse (distance to the voxel means), sum_w,
         chi2, rmse (the registration's at T), information (6 x 6, Open3D's form, rotation first, on the voxel means), hessian
         (the registration's normal matrix at T) and gradient.  per_point keeps the labels eval_fetch serves."""
-        h, elib = self._handle, load_voxelmap_eval()
+        h, elib = self._handle, load_ext()
         keep_p, keep_n, pp, pn, mem = self._cloud(xyz4, normals4)
         g, prm, res = _guess16(T), default_vmap_eval_params(per_point), VmapEvalResult()
         rc = elib.qtr_voxel_map_evaluate(h._h, slot, self._m, pp, pn, int(keep_p.shape[0]), mem,
@@ -977,7 +870,7 @@ class VoxelMap:
 
     def evaluate_keyframe(self, kf: Keyframe, T, per_point: bool = False, slot: int = 0) -> dict:
         """evaluate of the keyframe's stored voxels and normals, read in place (qtr_voxel_map_evaluate_keyframe)."""
-        h, elib = self._handle, load_voxelmap_eval()
+        h, elib = self._handle, load_ext()
         g, prm, res = _guess16(T), default_vmap_eval_params(per_point), VmapEvalResult()
         rc = elib.qtr_voxel_map_evaluate_keyframe(h._h, slot, self._m, kf._kf, None if g is None else g.ctypes.data,
                                                   C.byref(prm), C.byref(res))
@@ -986,7 +879,7 @@ class VoxelMap:
 
     def evaluate_batch_raw(self, items, per_point: bool = False, slot: int = 0):
         """qtr_voxel_map_evaluate_batch on the items as they stand: (return code, the VmapEvalResult array)."""
-        h, elib = self._handle, load_voxelmap_eval()
+        h, elib = self._handle, load_ext()
         items = list(items)
         arr, keep = self._batch_items(items)
         prm, res = default_vmap_eval_params(per_point), (VmapEvalResult * max(len(items), 1))()
@@ -1012,7 +905,7 @@ class VoxelMap:
         """Of item `item` of the slot's last evaluation (qtr_voxel_map_eval_fetch): VMAP_EVAL_CORR -> int32 [n] (0 matched, -1
         none), VMAP_EVAL_POINT -> float64 [n, 2] ((w d^T M d, w) of a matched point, (0, 0) otherwise; both only after a
         per_point call), VMAP_EVAL_TIMES -> float32 [1] (device ms of the upload and the launch)."""
-        h, elib = self._handle, load_voxelmap_eval()
+        h, elib = self._handle, load_ext()
         dtype, cols = {VMAP_EVAL_CORR: (np.int32, 0), VMAP_EVAL_POINT: (np.float64, 2), VMAP_EVAL_TIMES: (np.float32, 0)}[what]
         nbytes = elib.qtr_voxel_map_eval_fetch(h._h, slot, item, what, None, 0)
         if nbytes < 0:
@@ -1044,7 +937,7 @@ class VoxelMap:
         """Sliding-window eviction (qtr_voxel_map_evict): with C = floor(centre / voxel_size) and R = floor(radius /
         voxel_size), the voxels with |coordinates - C|^2 > R^2 (in integers) leave the map; the others stay bit for bit.
         Returns n_kept, n_evicted, n_members_evicted."""
-        h, klib = self._handle, load_voxelmap_keep()
+        h, klib = self._handle, load_ext()
         c = (C.c_double * 3)(*[float(x) for x in np.asarray(centre, dtype=np.float64).reshape(3)])
         info = VoxelMapEvictInfo()
         h._check(klib.qtr_voxel_map_evict(h._h, slot, self._m, C.byref(c), float(radius), C.byref(info)))
@@ -1056,7 +949,7 @@ class VoxelMap:
         — the centre pixel of its range image is filled and no filled pixel of the window around it holds a range
         <= r_v + margin — leaves the map; the others stay bit for bit.  Carve with the raw sweep, not a ground-removed
         cloud.  Returns n_kept, n_carved, n_tested, n_members_carved."""
-        h, clib = self._handle, load_voxelmap_carve()
+        h, clib = self._handle, load_ext()
         if isinstance(xyz4, np.ndarray) or not hasattr(xyz4, "data_ptr"):
             xyz4 = _f4(xyz4)
         else:
@@ -1071,7 +964,7 @@ class VoxelMap:
         """Visibility carving with 0 .. 64 keyframes of this handle, each under its pose ([K, 4, 4]), their stored voxels read
         in place (qtr_voxel_map_carve_keyframes); a voxel leaves when at least params.min_votes of them saw through it.
         Not for merged (submap) keyframes: they have no single viewpoint."""
-        h, clib = self._handle, load_voxelmap_carve()
+        h, clib = self._handle, load_ext()
         kfs = list(kfs)
         P = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 16))
         if P.shape[0] != len(kfs):
@@ -1090,7 +983,7 @@ class VoxelMap:
         """Puts voxels given as the fetch sections VMAP_COORDS (int32 [n, 3]), VMAP_COUNT (int32 [n]) and VMAP_SUMS (float64
         [n, 9]) into this map, which must hold no voxel (qtr_voxel_map_restore): numpy arrays (host) or contiguous torch
         tensors, all three on the device."""
-        h, klib = self._handle, load_voxelmap_keep()
+        h, klib = self._handle, load_ext()
         if isinstance(coords, np.ndarray) or not hasattr(coords, "data_ptr"):
             coords = np.ascontiguousarray(coords, dtype=np.int32).reshape(-1, 3)
             count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
@@ -1567,7 +1460,7 @@ class Handle:
                 raise ValueError("a deskewed keyframe needs times, knot_times and knot_poses")
             times, pt, kt, kp = self._deskew_args(raw4, times, mem, knot_times, knot_poses)
             info = DeskewInfo()
-            self._check(load_deskew().qtr_keyframe_create_deskewed(
+            self._check(load_ext().qtr_keyframe_create_deskewed(
                 self._h, slot, ptr, pt, int(raw4.shape[0]), kt.ctypes.data, kp.ctypes.data, int(kt.shape[0]), float(t_ref),
                 C.byref(fp), mem, C.byref(kf), C.byref(info)))
             out = Keyframe(self, kf.value)
@@ -1610,7 +1503,7 @@ class Handle:
         assert mem == mo and tuple(out.shape) == tuple(cloud.shape)
         times, pt, kt, kp = self._deskew_args(cloud, times, mem, knot_times, knot_poses)
         info = DeskewInfo()
-        self._check(load_deskew().qtr_deskew(self._h, slot, pc, pt, int(cloud.shape[0]), kt.ctypes.data, kp.ctypes.data,
+        self._check(load_ext().qtr_deskew(self._h, slot, pc, pt, int(cloud.shape[0]), kt.ctypes.data, kp.ctypes.data,
                                              int(kt.shape[0]), float(t_ref), po, mem, C.byref(info)))
         return out, {n: getattr(info, n) for n, _ in DeskewInfo._fields_}
 
@@ -1689,7 +1582,7 @@ class Handle:
         room for `capacity` of them."""
         if self._lib is not load():  # (another build of the library has other structures behind the handle)
             raise QuatroHipError(QTR_ERR_BAD_ARG, "voxel maps belong to handles of the product library libquatro_hip.so")
-        vlib = load_voxelmap()
+        vlib = load_ext()
         prm, out = VoxelMapParams(), C.c_void_p()
         vlib.qtr_default_voxel_map_params(C.byref(prm))
         prm.voxel_size, prm.capacity = float(voxel_size), int(capacity)

@@ -1,8 +1,8 @@
 """Sweep deskew without a GPU: include/qtr_deskew_math.h (through the g++ restatement, tests/deskew_ref/deskew_ref.cpp, and
-through qtr_deskew_pose_at of libquatro_deskew.so, which is host code) against a second model in numpy that shares nothing
+through qtr_deskew_pose_at of libquatro_ext.so, which is host code) against a second model in numpy that shares nothing
 with the header (deskew_restate.model_*: numpy's sin, cos and arctan2, 2 sin^2(th/2)/th^2 for the second Rodrigues
 coefficient); the interval, skip and identity rules; every refusal; the round trip through the skew synthesiser; and the
-boundary of the fourth library.
+header's entry points in the extension library's symbol table.
 
 The asserted differences are ten times what was measured when the test was written (the project's convention); every test
 prints what it measures."""
@@ -233,31 +233,16 @@ def test_constant_velocity_knots():
 
 
 def test_the_three_entry_points_are_declared_exported_and_bound():
-    """include/quatro_deskew.h is the whole dynamic symbol table of libquatro_deskew.so, the three entry points have their
-    ctypes signatures, none of the other three libraries exports them, and the info struct is its ctypes mirror."""
+    """The entry points of include/quatro_deskew.h are three of libquatro_ext.so's exports, they have their ctypes
+    signatures, libquatro_hip.so exports none of them, and the info struct is its ctypes mirror."""
     import ctypes
     import os
-    import re
     import subprocess
     import tempfile
-    from quatro_amd import build as qbuild
+    import ext_abi
     from quatro_amd import lib as ql
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    dpath = qbuild.build_deskew(force=False, verbose=False)
-    hdr = open(os.path.join(root, "include", "quatro_deskew.h")).read()
-    declared = set(re.findall(r"^QTR_DESKEW_API [^\n(]*?\b(qtr_[a-z_0-9]+)\s*\(", hdr, flags=re.M))
-    assert declared == set(re.findall(r"\b(qtr_[a-z_0-9]+)\s*\(", hdr)) == set(ql.DESKEW_EXPORTS)
-    assert declared == {"qtr_deskew", "qtr_keyframe_create_deskewed", "qtr_deskew_pose_at"}
-
-    def table(path):
-        out = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert table(dpath) == declared
-    for other in (qbuild.LIB, qbuild.VOXELMAP_LIB, qbuild.VOXELMAP_KEEP_LIB):
-        assert not (table(other) & declared), other
-    assert not (set(ql.EXPORTS) | set(ql.VOXELMAP_EXPORTS) | set(ql.VOXELMAP_KEEP_EXPORTS)) & declared
-    dlib = ql.load_deskew()
-    assert all(getattr(dlib, n).argtypes is not None for n in declared)
+    assert ext_abi.check_header("quatro_deskew.h") == {"qtr_deskew", "qtr_keyframe_create_deskewed", "qtr_deskew_pose_at"}
     src = r"""
 #include <stdio.h>
 #include <stddef.h>

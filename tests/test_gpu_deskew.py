@@ -1,4 +1,4 @@
-"""Sweep deskew on the MI355X (qtr_deskew / qtr_keyframe_create_deskewed, libquatro_deskew.so): bit-parity of the output and
+"""Sweep deskew on the MI355X (qtr_deskew / qtr_keyframe_create_deskewed, libquatro_ext.so): bit-parity of the output and
 the counts with the host restatement (tests/deskew_ref/deskew_ref.cpp) across the workgroup and knot-table sizes, on the
 edge times and skipped points of the CPU test, from host and device memory, in place; the keyframe of a raw sweep against
 the keyframe of its deskewed cloud; the refusals; deskewing scan-to-map odometry against the composition of the
@@ -179,7 +179,7 @@ def test_refusals_leave_the_slot_usable(hip, skewed_scan):
     got, _ = hip.deskew(cloud, t4, np.array([0.0, 0.1]), np.stack([base, under]), 0.0)  # just under the limit: admitted
     _same(got, D.deskew(cloud, t4, np.array([0.0, 0.1]), np.stack([base, under]), 0.0)[0], "just under the limit")
     # NULL arrays with P > 0, P < 0, and P > max_points: through the C ABI itself
-    dlib, out4, info = ql.load_deskew(), np.zeros((4, 4), np.float32), ql.DeskewInfo()
+    dlib, out4, info = ql.load_ext(), np.zeros((4, 4), np.float32), ql.DeskewInfo()
     gkt, gkp = ql._knots(kt, kp)
     kfp = C.c_void_p()
 
@@ -321,11 +321,11 @@ def test_cpp_deskew_demo_prints_what_the_python_calls_return(hip, skewed_scan, t
     from quatro_amd import synth
     skewed, times, kt, kp = skewed_scan
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    libpath = qbuild.build_deskew(force=False, verbose=False)
+    libpath = qbuild.build_ext(force=False, verbose=False)
     exe = str(tmp_path / "deskew_demo")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
                            os.path.join(root, "tests", "cpp", "deskew_demo.cpp"), "-o", exe, "-L", os.path.dirname(libpath),
-                           "-lquatro_hip", "-lquatro_deskew", "-Wl,-rpath," + os.path.dirname(libpath),
+                           "-lquatro_hip", "-lquatro_ext", "-Wl,-rpath," + os.path.dirname(libpath),
                            "-Wl,-rpath,/opt/rocm/lib"])
     sweep, tfile, kfile = str(tmp_path / "sweep.bin"), str(tmp_path / "times.f32"), str(tmp_path / "knots.txt")
     synth.save_kitti_bin(sweep, skewed)

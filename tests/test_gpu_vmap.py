@@ -2,7 +2,7 @@
 (tests/vmap_ref/vmap_ref.cpp) of the records after every insert and of every iteration of a registration, a crowded table
 whose probe chains wrap, the capacity refusal, the equality with the merged method 3 on positive-octant targets, the
 single-call loops in blocks (QTR_ICP_BLOCK) against the unblocked ones, the path equalities, scan-to-map odometry and build_map, the refusals, the C++ demo and the two libraries' symbol tables.  Everything
-goes through the C ABI (quatro_amd.lib; the map's entry points are libquatro_voxelmap.so's, include/quatro_voxelmap.h)."""
+goes through the C ABI (quatro_amd.lib; the map's entry points are libquatro_ext.so's, include/quatro_voxelmap.h)."""
 import os
 import subprocess
 
@@ -413,11 +413,11 @@ def test_cpp_voxelmap_demo_prints_what_the_python_calls_return(hip, vox_pair, tm
     from quatro_amd import build as qbuild
     from quatro_amd import synth
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    libpath = qbuild.build_voxelmap(force=False, verbose=False)
+    libpath = qbuild.build_ext(force=False, verbose=False)
     exe = str(tmp_path / "voxelmap_demo")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
                            os.path.join(root, "tests", "cpp", "voxelmap_demo.cpp"), "-o", exe, "-L", os.path.dirname(libpath),
-                           "-lquatro_hip", "-lquatro_voxelmap", "-Wl,-rpath," + os.path.dirname(libpath), "-Wl,-rpath,/opt/rocm/lib"])
+                           "-lquatro_hip", "-lquatro_ext", "-Wl,-rpath," + os.path.dirname(libpath), "-Wl,-rpath,/opt/rocm/lib"])
     vs, vt, ns, nt, Tgt = vox_pair
     pose_a, pose_b = R.rigid(R.rot(0.0, 0.0, 0.2), [1.0, 2.0, 0.0]), None
     pose_b = pose_a @ np.linalg.inv(Tgt)  # the source cloud under the pose that lays it over the target

@@ -1,4 +1,4 @@
-"""The grouped map registration on the MI355X (qtr_voxel_map_register_batch, libquatro_voxelmap_batch.so): every item of every
+"""The grouped map registration on the MI355X (qtr_voxel_map_register_batch, libquatro_ext.so): every item of every
 named case bit-equal to the single call's restatement (vmap_restate.RefMap.register) and to the single calls on the same
 slot, the group shapes, the blocked loop, repeatability and what a batch must leave untouched, relocalisation on top of it,
 the refusals and the C++ demo.  Everything goes through the C ABI (quatro_amd.lib)."""
@@ -327,7 +327,7 @@ def test_relocalize_and_relocalize_in_map_on_the_trajectory(hip, traj):
 def test_every_refusal_leaves_not_run_records_and_the_map_unchanged(hip, hand, traj):
     from quatro_amd import lib as ql
     vm, ref = hand
-    blib = ql.load_voxelmap_batch()
+    blib = ql.load_ext()
     items, _ = BC.CASES["invalid_beside_good"]()
     p, a, g = items[0]
     before = _sections(vm)
@@ -398,11 +398,11 @@ def test_every_refusal_leaves_not_run_records_and_the_map_unchanged(hip, hand, t
 def test_cpp_voxelmap_batch_demo_prints_what_the_python_calls_return(hip, tmp_path):
     from quatro_amd import api, synth
     from quatro_amd import build as qbuild
-    libpath = qbuild.build_voxelmap_batch(force=False, verbose=False)
+    libpath = qbuild.build_ext(force=False, verbose=False)
     exe = str(tmp_path / "voxelmap_batch_demo")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
                            os.path.join(ROOT, "tests", "cpp", "voxelmap_batch_demo.cpp"), "-o", exe, "-L", os.path.dirname(libpath),
-                           "-lquatro_hip", "-lquatro_voxelmap", "-lquatro_voxelmap_batch", "-Wl,-rpath," + os.path.dirname(libpath),
+                           "-lquatro_hip", "-lquatro_ext", "-Wl,-rpath," + os.path.dirname(libpath),
                            "-Wl,-rpath,/opt/rocm/lib"])
     inserts, (q, qa), _ = BC.room()
     pts, nrm, pose = inserts[0]

@@ -1,5 +1,5 @@
 """Visibility carving of the voxel map on the MI355X (qtr_voxel_map_carve / qtr_voxel_map_carve_keyframes,
-libquatro_voxelmap_carve.so): all five fetch sections and the info bit-equal to the numpy restatement
+libquatro_ext.so): all five fetch sections and the info bit-equal to the numpy restatement
 (tests/vmap_carve_restate.py) over map sizes, capacities, cloud sizes, numbers of keyframes, image sizes and windows, from
 host and device memory; the same call twice; inserts and registrations after a carve; the refusals; build_map(carve=) and
 scan_to_map_odometry(carve=); and the C++ demo.  Everything goes through the C ABI (quatro_amd.lib)."""
@@ -263,7 +263,7 @@ def test_refusals_leave_the_map_as_it_was(hip, hand, hand_scans, trajectory):
                 b[k][rc] = v
                 _refused(ql.QTR_ERR_BAD_ARG, f"pose {k}", vm.carve_keyframes, kfs, b, wide)
         # what the Python layer never passes, through the C ABI itself: NULL arrays with a count, a memory kind that is none
-        clib, info = ql.load_voxelmap_carve(), ql.VoxelMapCarveInfo()
+        clib, info = ql.load_ext(), ql.VoxelMapCarveInfo()
         arr = (ctypes.c_void_p * 2)(kfs[0]._kf.value, kfs[1]._kf.value)
         P2 = np.ascontiguousarray(kf_poses[:2])
         c0 = np.array(cloud)
@@ -400,11 +400,11 @@ def test_cpp_voxelmap_carve_demo_prints_what_the_python_calls_return(hip, hand, 
     from quatro_amd import build as qbuild
     from quatro_amd import synth
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    libpath = qbuild.build_voxelmap_carve(force=False, verbose=False)
+    libpath = qbuild.build_ext(force=False, verbose=False)
     exe = str(tmp_path / "voxelmap_carve_demo")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
                            os.path.join(root, "tests", "cpp", "voxelmap_carve_demo.cpp"), "-o", exe, "-L", os.path.dirname(libpath),
-                           "-lquatro_hip", "-lquatro_voxelmap", "-lquatro_voxelmap_carve", "-Wl,-rpath," + os.path.dirname(libpath),
+                           "-lquatro_hip", "-lquatro_ext", "-Wl,-rpath," + os.path.dirname(libpath),
                            "-Wl,-rpath,/opt/rocm/lib"])
     _, clouds, poses = hand_scans
     p, n, pose = hand[0][1]

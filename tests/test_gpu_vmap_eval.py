@@ -1,4 +1,4 @@
-"""The evaluation of poses against the voxel map on the MI355X (qtr_voxel_map_evaluate*, libquatro_voxelmap_eval.so): every
+"""The evaluation of poses against the voxel map on the MI355X (qtr_voxel_map_evaluate*, libquatro_ext.so): every
 named case bit-equal to the restatement (tests/vmap_eval_restate.py) through the cloud entry with host and device memory,
 the keyframe entry and the batch; batch = single; the largest group; mixed items; repeatability; what an evaluation must
 leave untouched; two slots; relocalize(keep=); the corridor; localisation -> evaluation -> pose-graph edge end to end; the
@@ -327,7 +327,7 @@ def test_localise_evaluate_and_optimise_end_to_end(hip, traj):
 def test_every_refusal_leaves_not_run_records(hip, maps, traj):
     from quatro_amd import lib as ql
     vm, items, want, _ = maps["sizes"]
-    elib = ql.load_voxelmap_eval()
+    elib = ql.load_ext()
     its = items[2:5]
     p, a, T = its[0]
     before = _sections(vm)
@@ -408,7 +408,7 @@ def test_fetch_before_the_slot_s_first_evaluation_is_refused():
     from quatro_amd import lib as ql
     h = ql.Handle(0)
     try:
-        assert ql.load_voxelmap_eval().qtr_voxel_map_eval_fetch(h._h, 0, 0, ql.VMAP_EVAL_TIMES, None, 0) == -1
+        assert ql.load_ext().qtr_voxel_map_eval_fetch(h._h, 0, 0, ql.VMAP_EVAL_TIMES, None, 0) == -1
     finally:
         h.close()
 
@@ -416,12 +416,11 @@ def test_fetch_before_the_slot_s_first_evaluation_is_refused():
 def test_cpp_voxelmap_eval_demo_prints_what_the_python_calls_return(hip, tmp_path):
     from quatro_amd import api, synth
     from quatro_amd import build as qbuild
-    libpath = qbuild.build_voxelmap_eval(force=False, verbose=False)
+    libpath = qbuild.build_ext(force=False, verbose=False)
     exe = str(tmp_path / "voxelmap_eval_demo")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-ffp-contract=off", "-I", os.path.join(ROOT, "include"),
                            os.path.join(ROOT, "tests", "cpp", "voxelmap_eval_demo.cpp"), "-o", exe, "-L", os.path.dirname(libpath),
-                           "-lquatro_hip", "-lquatro_voxelmap", "-lquatro_voxelmap_batch", "-lquatro_voxelmap_eval",
-                           "-Wl,-rpath," + os.path.dirname(libpath), "-Wl,-rpath,/opt/rocm/lib"])
+                           "-lquatro_hip", "-lquatro_ext", "-Wl,-rpath," + os.path.dirname(libpath), "-Wl,-rpath,/opt/rocm/lib"])
     inserts, (q, qa), _ = BC.room()
     pts, nrm, pose = inserts[0]
     base = api.pose_hypothesis(BC.ROOM_TRUE, 0.03, 0.2, -0.15)

@@ -1,4 +1,4 @@
-"""The voxel map's upkeep on the MI355X (qtr_voxel_map_evict / qtr_voxel_map_restore, libquatro_voxelmap_keep.so): bit-parity
+"""The voxel map's upkeep on the MI355X (qtr_voxel_map_evict / qtr_voxel_map_restore, libquatro_ext.so): bit-parity
 with the host restatement (tests/vmap_ref/vmap_keep_ref.cpp) of all five fetch sections and the info after an eviction and
 after the inserts that follow it, a crowded table whose wrapping probe chains lose voxels from their middle, the windows
 that keep everything and nothing, restore into maps of other capacities from host and device memory with its refusals, save
@@ -421,11 +421,11 @@ def test_cpp_voxelmap_keep_demo_prints_what_the_python_calls_return(hip, hand, t
     from quatro_amd import build as qbuild
     from quatro_amd import synth
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    libpath = qbuild.build_voxelmap_keep(force=False, verbose=False)
+    libpath = qbuild.build_ext(force=False, verbose=False)
     exe = str(tmp_path / "voxelmap_keep_demo")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
                            os.path.join(root, "tests", "cpp", "voxelmap_keep_demo.cpp"), "-o", exe, "-L", os.path.dirname(libpath),
-                           "-lquatro_hip", "-lquatro_voxelmap", "-lquatro_voxelmap_keep", "-Wl,-rpath," + os.path.dirname(libpath),
+                           "-lquatro_hip", "-lquatro_ext", "-Wl,-rpath," + os.path.dirname(libpath),
                            "-Wl,-rpath,/opt/rocm/lib"])
     p, n, pose = hand[0][1]
     args = [repr(K.SIDE)]

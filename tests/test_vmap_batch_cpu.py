@@ -1,17 +1,17 @@
-"""The grouped map registration without a GPU: the sixth library's symbol table against its header, binding and export map
-(and the other five tables as they were), the two host-side helpers of include/qtr_vmap_batch_math.h compiled with g++
+"""The grouped map registration without a GPU: the header's entry points against the binding and the extension
+library's symbol table (tests/ext_abi.py), the two host-side helpers of include/qtr_vmap_batch_math.h compiled with g++
 against their Python restatement bit for bit, and the named cases of tests/vmap_batch_cases.py: each makes the branch it
 claims, shown with the single call's restatement (vmap_restate.RefMap.register), which is the reference of every item."""
 import ctypes
 import math
 import os
-import re
 import subprocess
 import tempfile
 
 import numpy as np
 import pytest
 
+import ext_abi
 import icp_restate as R
 import vmap_batch_cases as BC
 import vmap_restate as M
@@ -42,29 +42,10 @@ def ref_lib():
 
 
 def test_the_two_entry_points_are_declared_exported_and_bound(ref_lib):
-    """include/quatro_voxelmap_batch.h is the whole dynamic symbol table of libquatro_voxelmap_batch.so; header, binding and
-    export map name the same two entry points; none of the other five libraries exports them and their tables are what
-    they were; the item and the constants are their ctypes mirrors."""
-    from quatro_amd import build as qbuild
+    """The entry points of include/quatro_voxelmap_batch.h are two of libquatro_ext.so's exports; header and binding name the
+    same two; libquatro_hip.so exports neither; the item and the constants are their ctypes mirrors."""
     from quatro_amd import lib as ql
-    bpath = qbuild.build_voxelmap_batch(force=False, verbose=False)
-    hdr = open(os.path.join(ROOT, "include", "quatro_voxelmap_batch.h")).read()
-    declared = set(re.findall(r"^QTR_VMAP_BATCH_API [^\n(]*?\b(qtr_[a-z_0-9]+)\s*\(", hdr, flags=re.M))
-    assert declared == set(re.findall(r"\b(qtr_[a-z_0-9]+)\s*\(", hdr)) == set(ql.VOXELMAP_BATCH_EXPORTS) == TWO
-    emap = open(os.path.join(ROOT, "quatro_amd", "csrc", "exports_voxelmap_batch.map")).read()
-    assert set(re.findall(r"\b(qtr_[a-z_0-9]+)\s*;", emap)) == TWO
-
-    def table(path):
-        out = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert table(bpath) == TWO
-    others = (qbuild.LIB, qbuild.VOXELMAP_LIB, qbuild.VOXELMAP_KEEP_LIB, qbuild.DESKEW_LIB, qbuild.VOXELMAP_CARVE_LIB)
-    names = (ql.EXPORTS, ql.VOXELMAP_EXPORTS, ql.VOXELMAP_KEEP_EXPORTS, ql.DESKEW_EXPORTS, ql.VOXELMAP_CARVE_EXPORTS)
-    for o, n in zip(others, names):
-        assert table(o) == set(n) and not (set(n) & TWO), o
-    assert [len(table(o)) for o in others] == [75, 10, 2, 3, 3]
-    blib = ql.load_voxelmap_batch()
-    assert all(getattr(blib, n).argtypes is not None for n in TWO)
+    assert ext_abi.check_header("quatro_voxelmap_batch.h") == TWO
     got = np.zeros(12, np.int32)
     ref_lib.vmap_batch_ref_layout(got.ctypes.data)
     I = ql.VmapRegItem

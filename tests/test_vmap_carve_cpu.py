@@ -1,8 +1,8 @@
 """The contract of the voxel map's visibility carving (include/qtr_vmap_carve_math.h) on the host: the header under g++
 (tests/vmap_carve_ref/vmap_carve_ref.cpp) against the numpy restatement (tests/vmap_carve_restate.py) bit for bit on the
 named cases, the pixel function against an independent numpy model (np.arctan2, np.hypot), the named edge cases, the
-refusals, what a carve does to a map, the quality of the rule on a scene with a moving box, and the fifth library's symbol
-table."""
+refusals, what a carve does to a map, the quality of the rule on a scene with a moving box, and the header's entry points in
+the extension library's symbol table."""
 import numpy as np
 import pytest
 
@@ -347,34 +347,18 @@ def test_quality_on_a_scene_with_a_moving_box(vegetation):
 
 
 def test_the_three_entry_points_are_declared_exported_and_bound():
-    """include/quatro_voxelmap_carve.h is the whole dynamic symbol table of libquatro_voxelmap_carve.so, the entry points have
-    their ctypes signatures, none of the other four libraries exports them, the structs are their ctypes mirrors and the
-    defaults are the documented ones."""
+    """The entry points of include/quatro_voxelmap_carve.h are three of libquatro_ext.so's exports, they have their ctypes
+    signatures, libquatro_hip.so exports none of them, the structs are their ctypes mirrors and the defaults are the
+    documented ones."""
     import ctypes
     import os
-    import re
     import subprocess
     import tempfile
-    from quatro_amd import build as qbuild
+    import ext_abi
     from quatro_amd import lib as ql
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    cpath = qbuild.build_voxelmap_carve(force=False, verbose=False)
-    hdr = open(os.path.join(root, "include", "quatro_voxelmap_carve.h")).read()
-    declared = set(re.findall(r"^QTR_VMAP_CARVE_API [^\n(]*?\b(qtr_[a-z_0-9]+)\s*\(", hdr, flags=re.M))
-    assert declared == set(re.findall(r"\b(qtr_[a-z_0-9]+)\s*\(", hdr)) == set(ql.VOXELMAP_CARVE_EXPORTS)
-    assert declared == {"qtr_default_carve_params", "qtr_voxel_map_carve", "qtr_voxel_map_carve_keyframes"}
-
-    def table(path):
-        out = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert table(cpath) == declared
-    others = (qbuild.LIB, qbuild.VOXELMAP_LIB, qbuild.VOXELMAP_KEEP_LIB, qbuild.DESKEW_LIB)
-    assert all(not (table(o) & declared) for o in others)
-    assert [len(table(o)) for o in others] == [75, 10, 2, 3]
-    for names in (ql.EXPORTS, ql.VOXELMAP_EXPORTS, ql.VOXELMAP_KEEP_EXPORTS, ql.DESKEW_EXPORTS):
-        assert not (set(names) & declared)
-    clib = ql.load_voxelmap_carve()
-    assert all(getattr(clib, n).argtypes is not None for n in declared)
+    assert ext_abi.check_header("quatro_voxelmap_carve.h") == {"qtr_default_carve_params", "qtr_voxel_map_carve",
+                                                               "qtr_voxel_map_carve_keyframes"}
     src = r"""
 #include <stdio.h>
 #include <stddef.h>

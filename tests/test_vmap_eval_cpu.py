@@ -1,17 +1,15 @@
-"""The evaluation of poses against the voxel map without a GPU: the seventh library's symbol table against its header,
-binding and export map (and the other six tables as they were), the struct layouts, the restatement
+"""The evaluation of poses against the voxel map without a GPU: the header's entry points against the binding and
+the extension library's symbol table (tests/ext_abi.py), the struct layouts, the restatement
 (tests/vmap_eval_restate.py, g++ from include/qtr_vmap_eval_math.h) against an independent numpy implementation and against
 the registration's own first iteration, what `information` means, qtr_vmap_eval_best against api.best_evaluation, the
 named cases of tests/vmap_eval_cases.py (each makes the branch it claims), the pose-graph helpers on
 tests/pgo_restate.optimize, and the refusals that need no device."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
+import ext_abi
 import icp_restate as R
 import pgo_restate as PG
 import vmap_batch_cases as BC
@@ -20,7 +18,6 @@ import vmap_eval_cases as EC
 import vmap_eval_restate as E
 import vmap_restate as M
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 FIVE = {"qtr_default_vmap_eval_params", "qtr_voxel_map_evaluate", "qtr_voxel_map_evaluate_keyframe",
         "qtr_voxel_map_evaluate_batch", "qtr_voxel_map_eval_fetch"}
 
@@ -44,31 +41,9 @@ def _evals(name, ref=None):
 
 # ---- symbol tables and layouts -------------------------------------------------------------------------------------------
 def test_the_five_entry_points_are_declared_exported_and_bound():
-    """include/quatro_voxelmap_eval.h is the whole dynamic symbol table of libquatro_voxelmap_eval.so; header, binding and
-    export map name the same five entry points; none of the other six libraries exports them and their tables are what they
-    were."""
-    from quatro_amd import build as qbuild
-    from quatro_amd import lib as ql
-    epath = qbuild.build_voxelmap_eval(force=False, verbose=False)
-    hdr = open(os.path.join(ROOT, "include", "quatro_voxelmap_eval.h")).read()
-    declared = set(re.findall(r"^QTR_VMAP_EVAL_API [^\n(]*?\b(qtr_[a-z_0-9]+)\s*\(", hdr, flags=re.M))
-    assert declared == set(re.findall(r"\b(qtr_[a-z_0-9]+)\s*\(", hdr)) == set(ql.VOXELMAP_EVAL_EXPORTS) == FIVE
-    emap = open(os.path.join(ROOT, "quatro_amd", "csrc", "exports_voxelmap_eval.map")).read()
-    assert set(re.findall(r"\b(qtr_[a-z_0-9]+)\s*;", emap)) == FIVE
-
-    def table(path):
-        out = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert table(epath) == FIVE
-    others = (qbuild.LIB, qbuild.VOXELMAP_LIB, qbuild.VOXELMAP_KEEP_LIB, qbuild.DESKEW_LIB, qbuild.VOXELMAP_CARVE_LIB,
-              qbuild.VOXELMAP_BATCH_LIB)
-    names = (ql.EXPORTS, ql.VOXELMAP_EXPORTS, ql.VOXELMAP_KEEP_EXPORTS, ql.DESKEW_EXPORTS, ql.VOXELMAP_CARVE_EXPORTS,
-             ql.VOXELMAP_BATCH_EXPORTS)
-    for o, n in zip(others, names):
-        assert table(o) == set(n) and not (set(n) & FIVE), o
-    assert [len(table(o)) for o in others] == [75, 10, 2, 3, 3, 2]
-    elib = ql.load_voxelmap_eval()
-    assert all(getattr(elib, n).argtypes is not None for n in FIVE)
+    """The entry points of include/quatro_voxelmap_eval.h are five of libquatro_ext.so's exports; header and binding name the
+    same five; libquatro_hip.so exports none of them."""
+    assert ext_abi.check_header("quatro_voxelmap_eval.h") == FIVE
 
 
 def test_struct_layouts_match_their_ctypes_mirrors():
@@ -305,7 +280,7 @@ def test_pose_graph_localization_edges():
 # ---- refusals that need no device -------------------------------------------------------------------------------------------
 def test_refusals_without_a_device():
     from quatro_amd import lib as ql
-    elib = ql.load_voxelmap_eval()
+    elib = ql.load_ext()
     prm = ql.default_vmap_eval_params()
     assert prm.per_point == 0 and ql.default_vmap_eval_params(True).per_point == 1
     res = (ql.VmapEvalResult * 2)()

@@ -1,7 +1,7 @@
 """The contract of the voxel map's upkeep (include/qtr_vmap_keep_math.h) on the host: the window rule at its edges, the
 restatement (tests/vmap_ref/vmap_keep_ref.cpp, compiled by g++ from the shared headers) against an independent model in plain
 Python (a dict keyed by coordinate triples, the rule in Python integers), evict followed by inserts, restore and its refusals,
-and the third library's symbol table."""
+and the header's entry points in the extension library's symbol table."""
 import math
 
 import numpy as np
@@ -234,30 +234,16 @@ def test_restore_gives_the_map_back_for_any_capacity_and_refuses_the_rest():
 
 
 def test_the_two_entry_points_are_declared_exported_and_bound():
-    """include/quatro_voxelmap_keep.h is the whole dynamic symbol table of libquatro_voxelmap_keep.so, both entry points have
-    their ctypes signatures, neither of the other two libraries exports them, and the info struct is its ctypes mirror."""
+    """The entry points of include/quatro_voxelmap_keep.h are two of libquatro_ext.so's exports, both have their ctypes
+    signatures, libquatro_hip.so exports neither, and the info struct is its ctypes mirror."""
     import ctypes
     import os
-    import re
     import subprocess
     import tempfile
-    from quatro_amd import build as qbuild
+    import ext_abi
     from quatro_amd import lib as ql
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    kpath = qbuild.build_voxelmap_keep(force=False, verbose=False)
-    hdr = open(os.path.join(root, "include", "quatro_voxelmap_keep.h")).read()
-    declared = set(re.findall(r"^QTR_VMAP_KEEP_API [^\n(]*?\b(qtr_[a-z_0-9]+)\s*\(", hdr, flags=re.M))
-    assert declared == set(re.findall(r"\b(qtr_[a-z_0-9]+)\s*\(", hdr)) == set(ql.VOXELMAP_KEEP_EXPORTS)
-    assert declared == {"qtr_voxel_map_evict", "qtr_voxel_map_restore"}
-
-    def table(path):
-        out = subprocess.check_output(["nm", "-D", "--defined-only", path], text=True)
-        return {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert table(kpath) == declared
-    assert not (table(qbuild.LIB) & declared) and not (table(qbuild.VOXELMAP_LIB) & declared)
-    assert not (set(ql.EXPORTS) & declared) and not (set(ql.VOXELMAP_EXPORTS) & declared)
-    klib = ql.load_voxelmap_keep()
-    assert all(getattr(klib, n).argtypes is not None for n in declared)
+    assert ext_abi.check_header("quatro_voxelmap_keep.h") == {"qtr_voxel_map_evict", "qtr_voxel_map_restore"}
     src = r"""
 #include <stdio.h>
 #include <stddef.h>
