@@ -56,6 +56,12 @@
       hipLaunchKernelGGL((kern<false>), grid, block, lds, st, (ViewExt<MatchView>{nullptr, {0, 0, 0}}), (a).one, ##__VA_ARGS__);            \
   } while (0)
 
+// A query's slot in best_small / best_large while it has no candidate yet: a distance field no real distance reaches
+// (a NaN pattern: every key of a real candidate compares below it) with row 0 — what a query without a candidate
+// answers (the oracle's nn33: a NaN distance never wins, no candidate answers row 0).  ~0 is left to the rows of the
+// larger cloud that were never asked: the tails decode it as -1 and as "not hit".
+#define NN_NO_CANDIDATE 0xffffffff00000000ULL
+
 __device__ __forceinline__ float l2_flann33(const float* a, const float* b /* LDS row, stride-36 */) {
   float result = 0.f;
 #pragma unroll
@@ -109,7 +115,7 @@ __global__ __launch_bounds__(256) void k_nn_exact(ViewExt<MatchView> x, MatchVie
       }
     }
   }
-  if (a_idx >= 0 && bi >= 0) atomicMin(&D.best[a_idx], ((u64)__float_as_uint(bd) << 32) | (u32)bi);
+  if (a_idx >= 0) atomicMin(&D.best[a_idx], bi >= 0 ? (((u64)__float_as_uint(bd) << 32) | (u32)bi) : NN_NO_CANDIDATE);
 }
 
 // =================================================================================================
@@ -928,7 +934,7 @@ __global__ __launch_bounds__(NN_FIN_THREADS) void k_nn_finish(ViewExt<MatchView>
   if (unsafe) i1 = -1;
   const bool certified = i1 >= 0 && (b2 == INFINITY || b2 - b1 > gap);
   const bool listed = valid && !certified;
-  if (valid) D.best[row] = certified ? (u64)(u32)i1 : ~0ULL;
+  if (valid) D.best[row] = certified ? (u64)(u32)i1 : NN_NO_CANDIDATE;  // (listed: the re-check's atomicMin replaces it)
   // ordered append: ranks inside the workgroup from ballots, one atomic per workgroup
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const u64 bal = __ballot(listed);
@@ -1135,7 +1141,9 @@ __global__ __launch_bounds__(256) void k_nn_finish_f16(ViewExt<MatchView> x, Mat
     const float thr_e = (i1 >= 0) ? (e1 - cna) + u * (42.0f * cna + 42.0f * e1 + 0.5f * cadd) * 1.02f + 1e-30f : INFINITY;
     const bool certified = i1 >= 0 && (c2 == INFINITY || c2 - c1 > gap || c2 > thr_e);
     const bool listed = valid && !certified;
-    if (valid) D.best[crow] = certified ? (u64)(u32)i1 : ~0ULL;
+    // (a listed row waits for the re-check's atomicMin; one that finds no candidate there — a NaN descriptor — answers row 0,
+    // asked and answered, in either direction: not the ~0 of a row that was never asked)
+    if (valid) D.best[crow] = certified ? (u64)(u32)i1 : NN_NO_CANDIDATE;
     const u64 bal = __ballot(listed);
     int base = 0;
     if (lane == 0 && bal) base = atomicAdd(V.mcounts + D.rc_slot, __popcll(bal));  // one atomic per workgroup
