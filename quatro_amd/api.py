@@ -904,6 +904,63 @@ def close_loop(handle, index, keyframes, query_kf, k, id_lo=0, id_hi=None, fp=No
     return out
 
 
+def find_loops(index, min_gap, k, max_distance=None, first=0, last=None):
+    """Loop detection over a finished run: every entry i of [first, last) (last = None: the index's size) queries the entries
+    [0, i - min_gap] of its own index, as grouped calls (PlaceIndex.query_batch, entry items read in place).  The entries are
+    taken in chunks such that a call has at most PLACE_BATCH_MAX queries and PLACE_BATCH_MAX_PAIRS (query, entry) pairs of
+    its union range [0, b - min_gap) — b the chunk's end.  Returns one list of match dicts per entry, in order; with
+    max_distance only the matches whose distance is at most that are kept (filtered on the host: the search still
+    returns the k best)."""
+    if min_gap < 0:
+        raise ValueError("find_loops: min_gap must be >= 0")
+    size = len(index)
+    last = size if last is None else min(int(last), size)
+    first = max(int(first), 0)
+    q_cap, pair_cap = int(_ql.PLACE_BATCH_MAX), int(_ql.PLACE_BATCH_MAX_PAIRS)
+    out = []
+    a = first
+    while a < last:
+        b = min(a + q_cap, last)
+        while b - a > 1 and (b - a) * max(b - min_gap, 0) > pair_cap:
+            b -= 1
+        got = index.query_batch([(i, (0, i - min_gap + 1)) for i in range(a, b)], k)
+        for ms in got:
+            out.append(ms if max_distance is None else [m for m in ms if m["distance"] <= max_distance])
+        a = b
+    return out
+
+
+def close_loops(handle, index, keyframes, queries, k, id_lo=0, id_hi=None, fp=None, params=None, icp=None):
+    """close_loop for a group of queries: ONE index.query_batch picks every query's k entries, ONE
+    Handle.register_batch_keyframes registers all (query, candidate) pairs, in the queries' order and, per query, in the
+    order the search returned them.  queries: Keyframes, or (Keyframe, (id_lo, id_hi)) for a range of the query's own
+    (default: [id_lo, id_hi) for all).  Returns per query what close_loop returns — "matches", "records" (and "refined"
+    with icp), "best", "best_id" — without its submap and evaluate options."""
+    fp = fp or _ql.default_frontend_params()
+    kfs, items = [], []
+    for q in queries:
+        kf, rng = q if isinstance(q, tuple) else (q, (id_lo, id_hi))
+        kfs.append(kf)
+        items.append((kf, tuple(rng)))
+    matches = index.query_batch(items, k) if items else []
+    pairs = [(kf, keyframes[m["id"]], int(fp.seed)) for kf, ms in zip(kfs, matches) for m in ms]
+    records, refined = [], []
+    if pairs:
+        got = handle.register_batch_keyframes(pairs, fp, params, icp)
+        records, refined = (got, []) if icp is None else got
+    outs, at = [], 0
+    for ms in matches:
+        o = {"matches": ms, "records": records[at:at + len(ms)], "best": -1, "best_id": -1}
+        if icp is not None:
+            o["refined"] = refined[at:at + len(ms)]
+        at += len(ms)
+        o["best"] = best_candidate(o["records"])
+        if o["best"] >= 0:
+            o["best_id"] = ms[o["best"]]["id"]
+        outs.append(o)
+    return outs
+
+
 def default_line_process_weight(edges, max_correspondence_distance, preference_loop_closure=1.0):
     """Open3D's rule for the line process weight mu: preference_loop_closure x max_correspondence_distance^2 x the mean of
     information[5][5] over the UNCERTAIN edges (information[5][5] is n_corr in the evaluation's matrix).  edges: (s, t, T,

@@ -22,6 +22,9 @@ TEST_LIB = os.path.join(HERE, "libquatro_hip_testengines.so")
 # registration and evaluation, sweep deskew) is exported by ONE extension library over the same sources, -DQTR_EXT_LIB with
 # exports_ext.map: libquatro_hip.so's dynamic symbol table stays the C ABI of include/quatro_hip.h
 EXT_LIB = os.path.join(HERE, "libquatro_ext.so")
+# both tables above are pinned by the test-suite, so what is added after them (include/quatro_place_batch.h onwards) is
+# exported by a second extension library over the same sources, -DQTR_EXT2_LIB with exports_ext2.map
+EXT2_LIB = os.path.join(HERE, "libquatro_ext2.so")
 INCLUDE = os.path.join(HERE, "..", "include")
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))) + sorted(
     os.path.join("..", "..", "include", f) for f in os.listdir(INCLUDE)
@@ -44,6 +47,11 @@ def build_ext(force: bool = False, verbose: bool = True) -> str:
     return build(force, verbose, lib=EXT_LIB, defines=("-DQTR_EXT_LIB",), exports="exports_ext.map")
 
 
+def build_ext2(force: bool = False, verbose: bool = True) -> str:
+    build(False, verbose)  # (as build_ext: the product library, where it is stale)
+    return build(force, verbose, lib=EXT2_LIB, defines=("-DQTR_EXT2_LIB",), exports="exports_ext2.map")
+
+
 def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=(), exports: str = "exports.map") -> str:
     if not force and not is_stale(lib):
         return lib
@@ -61,4 +69,5 @@ def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=(),
 if __name__ == "__main__":
     build(force="--force" in sys.argv)
     build_ext(force="--force" in sys.argv)
+    build_ext2(force="--force" in sys.argv)
     build_test_engines(force="--force" in sys.argv)

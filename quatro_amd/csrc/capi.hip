@@ -77,6 +77,7 @@ struct Slot {
   void* deskew_dev = nullptr;  // copy of the table with the counters behind it (allocated on the slot's first deskew)
   struct VmapBatch* vbatch = nullptr;  // voxelmap_batch.hip: the slot's batch arena (allocated on the slot's first batch)
   struct VmapEval* veval = nullptr;    // voxelmap_eval.hip: the slot's map-evaluation arena (allocated on its first evaluation)
+  struct PlaceBatch* pbatch = nullptr;  // place_batch.hip: the slot's grouped-query arena (allocated on its first batch)
 };
 
 // What a batch lane is waiting for: the mail of the chain it enqueued last (lane_poll).
@@ -181,6 +182,7 @@ static std::atomic<unsigned long long> g_handle_uid{0};
 static void vmap_free_all(qtr_handle* h);  // (voxelmap.hip)
 static void vmap_batch_free(Slot& s);      // (voxelmap_batch.hip)
 static void vmap_eval_free(Slot& s);       // (voxelmap_eval.hip)
+static void place_batch_free(Slot& s);     // (place_batch.hip)
 
 #define QTR_TRY(expr)                  \
   do {                                 \
@@ -484,6 +486,7 @@ void qtr_destroy(qtr_handle* h) {
     if (s.deskew_dev) (void)hipFree(s.deskew_dev);
     vmap_batch_free(s);
     vmap_eval_free(s);
+    place_batch_free(s);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.stream2) (void)hipStreamDestroy(s.stream2);
     if (s.stream3) (void)hipStreamDestroy(s.stream3);

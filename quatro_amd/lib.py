@@ -146,6 +146,11 @@ class PlaceIndexInfo(C.Structure):
     _fields_ = [("params", PlaceParams), ("size", C.c_int), ("capacity", C.c_int), ("device_bytes", C.c_ulonglong)]
 
 
+class PlaceQueryItem(C.Structure):  # qtr_place_query_item (include/quatro_place_batch.h)
+    _fields_ = [("kf", C.c_void_p), ("desc", C.c_void_p), ("from_", C.c_void_p), ("entry", C.c_int), ("mem", C.c_int),
+                ("id_lo", C.c_int), ("id_hi", C.c_int)]
+
+
 class VoxelMapParams(C.Structure):
     _fields_ = [("voxel_size", C.c_double), ("capacity", C.c_int), ("reserved", C.c_int * 5)]
 
@@ -205,6 +210,9 @@ VMAP_COORDS, VMAP_COUNT, VMAP_SUMS, VMAP_RECORDS, VMAP_CLOUD = 1, 2, 3, 4, 5
 VMAP_MAX_CAPACITY = 1 << 24
 PLACE_DESC, PLACE_COLNORM2 = 1, 2
 PLACE_MAX_K = 64
+PLACE_BATCH_MAX, PLACE_BATCH_MAX_PAIRS = 1024, 1 << 26
+PLACE_BATCH_DIST, PLACE_BATCH_SHIFT = 1, 2
+PLACE_MATCH_DTYPE = np.dtype([("id", "<i4"), ("shift", "<i4"), ("distance", "<f4"), ("yaw", "<f4")])  # qtr_place_match
 SUBMAP_MAX_KEYFRAMES = 64
 EVAL_MAX_PAIRS = 64
 DBG_EVAL_CORR = 18
@@ -241,6 +249,10 @@ VOXELMAP_EVAL_EXPORTS = ["qtr_default_vmap_eval_params", "qtr_voxel_map_evaluate
                          "qtr_voxel_map_evaluate_batch", "qtr_voxel_map_eval_fetch"]  # include/quatro_voxelmap_eval.h
 EXT_EXPORTS = (VOXELMAP_EXPORTS + VOXELMAP_KEEP_EXPORTS + DESKEW_EXPORTS + VOXELMAP_CARVE_EXPORTS + VOXELMAP_BATCH_EXPORTS
                + VOXELMAP_EVAL_EXPORTS)
+
+# the C ABI added after both tables above were pinned, per header; libquatro_ext2.so exports their concatenation
+PLACE_BATCH_EXPORTS = ["qtr_place_query_batch", "qtr_place_batch_fetch"]  # include/quatro_place_batch.h
+EXT2_EXPORTS = PLACE_BATCH_EXPORTS
 
 _lib = None
 
@@ -511,6 +523,30 @@ def load_ext():
     lib.qtr_voxel_map_eval_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     lib.qtr_voxel_map_eval_fetch.restype = C.c_longlong
     _ext_lib = lib
+    return lib
+
+
+EXT2_LIB_PATH = os.environ.get("QTR_EXT2_LIB") or os.path.join(_HERE, "libquatro_ext2.so")
+_ext2_lib = None
+
+
+def load_ext2():
+    """libquatro_ext2.so: the entry points added after libquatro_ext.so's table was pinned (EXT2_EXPORTS).  They take the
+    handles, keyframes and indexes of load()'s library; all come from the same build (quatro_amd.build.build_ext2)."""
+    global _ext2_lib
+    if _ext2_lib is not None:
+        return _ext2_lib
+    load()  # (first: one HIP runtime per process)
+    if not os.path.exists(EXT2_LIB_PATH):
+        raise FileNotFoundError(
+            f"{EXT2_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
+            "(or __graft_entry__.build()) first.")
+    lib = C.CDLL(EXT2_LIB_PATH)
+    lib.qtr_place_query_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PlaceQueryItem), C.c_int, C.c_int,
+                                          C.c_void_p, C.c_void_p]
+    lib.qtr_place_batch_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+    lib.qtr_place_batch_fetch.restype = C.c_longlong
+    _ext2_lib = lib
     return lib
 
 
@@ -1094,6 +1130,55 @@ class PlaceIndex:
         ptr, mem = _ptr(self._desc(desc))
         h._check(h._lib.qtr_place_query_desc(h._h, slot, self._ix, ptr, mem, int(id_lo), hi, int(k), out, C.byref(n)))
         return self._matches(out, n.value)
+
+    def _batch_item(self, item, keep: list) -> PlaceQueryItem:
+        """One item of query_batch: a Keyframe, a descriptor (numpy, or a contiguous torch device tensor), an entry id of this
+        index or (PlaceIndex, id) — alone, or as (source, (id_lo, id_hi)).  `keep` holds what the pointers point into."""
+        rng = None
+        if (isinstance(item, tuple) and len(item) == 2 and not isinstance(item[0], PlaceIndex)
+                and (item[1] is None or isinstance(item[1], (tuple, list)))):
+            item, rng = item  # ((PlaceIndex, id), range) comes through here too: its first member is a tuple
+        it = PlaceQueryItem()
+        it.id_lo, it.id_hi = (0, 2 ** 31 - 1) if rng is None else (int(rng[0]), 2 ** 31 - 1 if rng[1] is None else int(rng[1]))
+        it.entry = -1
+        if isinstance(item, Keyframe):
+            it.kf = item._kf
+        elif isinstance(item, tuple) and len(item) == 2 and isinstance(item[0], PlaceIndex):
+            it.from_, it.entry = item[0]._ix, int(item[1])
+        elif isinstance(item, (int, np.integer)):
+            it.entry = int(item)
+        else:
+            d = self._desc(item)
+            keep.append(d)
+            it.desc, it.mem = _ptr(d)
+        return it
+
+    def query_batch(self, items, k: int = 10, slot: int = 0, raw: bool = False):
+        """qtr_place_query_batch: every item's query in one chain of launches and one host wait.  Returns one list of
+        match dicts per item (what query / query_desc return for it); raw=True returns the records themselves, a
+        [Q, k] array of PLACE_MATCH_DTYPE (rows filled up to n[q], the rest zero) and n, int32 [Q]."""
+        h, keep = self._handle, []
+        Q = len(items)
+        arr = (PlaceQueryItem * max(Q, 1))(*[self._batch_item(x, keep) for x in items])
+        out = np.zeros((Q, max(int(k), 0)), dtype=PLACE_MATCH_DTYPE)
+        n = np.zeros(Q, dtype=np.int32)
+        h._check(load_ext2().qtr_place_query_batch(h._h, slot, self._ix, arr, Q, int(k), out.ctypes.data, n.ctypes.data))
+        if raw:
+            return out, n
+        return [[{"id": int(r["id"]), "shift": int(r["shift"]), "distance": np.float32(r["distance"]), "yaw": float(r["yaw"])}
+                 for r in out[q, :n[q]]] for q in range(Q)]
+
+    def batch_fetch(self, query: int, what: int = PLACE_BATCH_DIST, slot: int = 0) -> np.ndarray:
+        """qtr_place_batch_fetch: PLACE_BATCH_DIST -> float32, PLACE_BATCH_SHIFT -> int32, one value per entry of the
+        clamped range of query `query` of the slot's last query_batch, in id order."""
+        h, lib = self._handle, load_ext2()
+        nbytes = lib.qtr_place_batch_fetch(h._h, slot, int(query), what, None, 0)
+        if nbytes < 0:
+            raise QuatroHipError(-1, "qtr_place_batch_fetch failed")
+        out = np.zeros(nbytes // 4, dtype=np.float32 if what == PLACE_BATCH_DIST else np.int32)
+        if nbytes and lib.qtr_place_batch_fetch(h._h, slot, int(query), what, out.ctypes.data, nbytes) < 0:
+            raise QuatroHipError(-1, "qtr_place_batch_fetch failed")
+        return out
 
     def close(self):
         if self._ix and getattr(self._handle, "_h", None):
