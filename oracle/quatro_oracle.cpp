@@ -37,6 +37,11 @@
 //      build-dependent).  Agreement with an SVD evaluation is checked in tests to 1e-12.
 //   D7 libm atan2f/acosf/sinf/cosf replaced by the binary64 evaluations of qtr_math.h.
 //   D8 stdout prints removed.
+//   D9 non-finite coordinates in the two raw-scan stages: a point with a non-finite x, y or z belongs to no
+//      Patchwork patch (the reference sorts heights with `z < z`, no strict weak order once a NaN is among them:
+//      its answer is undefined and would depend on where the point stands), and a point with a NaN coordinate
+//      belongs to no range-image pixel (the reference's float -> size_t conversions of NaN, read as x86-64
+//      performs them: the most negative integer, which fails the range check).
 //
 // Build: see oracle/Makefile (g++ -O2 -ffp-contract=off -fopenmp).
 #include <algorithm>
@@ -1143,7 +1148,11 @@ double cote_estimate(const std::vector<double>& X, double range, bool median_sel
 //   * the plane normal is the smallest eigenvector from the closed-form pcl::eigen33 restatement used for the
 //     normals (instead of Eigen::JacobiSVD), oriented so that n_z >= 0 (the SVD's sign is an artefact; for
 //     ground-like patches it points up), and the singular values are the |eigenvalues| of the same solve,
-//   * atan2 / sqrt of the polar binning in binary64 through qm_atan2d.
+//   * atan2 / sqrt of the polar binning in binary64 through qm_atan2d,
+//   * a point with a non-finite x, y or z belongs to no patch and appears in neither output (the reference's
+//     `z < z` comparator is no strict weak order once a NaN is among the heights, so its sort, and with it every
+//     patch, has no defined answer; dropping such points is the only answer that does not depend on where they
+//     stand in the input).
 struct PwParams {
   double sensor_height;
   int num_iter, num_lpr, num_min_pts;
@@ -1234,8 +1243,12 @@ static void pw_estimate_plane(const float* xyz4, const int* ids, int n, const st
 // ground4 / nonground4: x,y,z,w of the input points in the reference's output order; returns counts
 static void patchwork(const float* xyz4, int P, const PwParams& pw, float* ground4, int* n_ground, float* nonground4,
                       int* n_nonground, int* patch_of /* optional [P]: patch id or -1 */) {
-  std::vector<int> order((size_t)P);
-  for (int i = 0; i < P; ++i) order[i] = i;
+  std::vector<int> order;
+  order.reserve((size_t)P);
+  for (int i = 0; i < P; ++i) {  // non-finite points belong to no patch (declared above)
+    const float* q = xyz4 + 4 * (size_t)i;
+    if (std::isfinite(q[0]) && std::isfinite(q[1]) && std::isfinite(q[2])) order.push_back(i);
+  }
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return xyz4[4 * (size_t)a + 2] < xyz4[4 * (size_t)b + 2]; });
   int base[5] = {0, 0, 0, 0, 0};
   for (int k = 0; k < pw.num_zones; ++k) base[k + 1] = base[k] + pw.num_rings_each_zone[k] * pw.num_sectors_each_zone[k];
@@ -1248,7 +1261,7 @@ static void patchwork(const float* xyz4, int P, const PwParams& pw, float* groun
   }
   std::vector<std::vector<int>> patch((size_t)npatch);
   if (patch_of) std::fill(patch_of, patch_of + P, -1);
-  for (int t = 0; t < P; ++t) {
+  for (size_t t = 0; t < order.size(); ++t) {
     const int i = order[t];
     const float* q = xyz4 + 4 * (size_t)i;
     if ((double)q[2] < -1.8 * pw.sensor_height) continue;  // mirror reflections under the ground (:351-361)
@@ -1347,7 +1360,9 @@ static void patchwork(const float* xyz4, int P, const PwParams& pw, float* groun
 // rule (size >= num_min_pts, or size >= 5 and >= 3 rows holding a pixel other than the seed), labels numbered in
 // row-major order of the components' first pixels.  Declared divergences: atan2f / sin / cos come from qtr_math.h
 // (D7); the float -> size_t conversions of negative values (undefined behaviour in the reference) are defined as
-// truncation toward zero followed by the range check, which is what x86-64 does.
+// truncation toward zero followed by the range check, which is what x86-64 does; the same reading of a NaN (x86-64
+// converts it to the most negative integer, which fails the range check) is spelled out: a point with a NaN
+// coordinate belongs to no pixel (its row comes out as NaN; the column is NaN only when the row is).
 struct IpParams {
   int n_scan, horizon_scan;
   float ang_res_x, ang_res_y, ang_bottom;
@@ -1360,6 +1375,7 @@ struct IpParams {
 static bool ip_pixel_of(const IpParams& ip, float x, float y, float z, int* row, int* col, float* range) {
   const float va = (float)((double)(qm_atan2f(z, sqrtf(x * x + y * y)) * 180) / M_PI);
   const float rf = (va + ip.ang_bottom) / ip.ang_res_y;
+  if (rf != rf) return false;  // NaN: no pixel (declared above)
   const long long r = (long long)rf;  // size_t conversion in the reference; negative values wrap and fail the test
   if (r < 0 || r >= ip.n_scan) return false;
   const float ha = (float)((double)(qm_atan2f(x, y) * 180) / M_PI);

@@ -46,7 +46,7 @@ struct PwBufs {
 
 __global__ __launch_bounds__(256) void k_pw_keys(const float4* __restrict__ pts, int P, u64* __restrict__ keys) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < P) keys[i] = ((u64)enc_f32(pts[i].z) << 32) | (u32)i;
+  if (i < P) keys[i] = ((u64)enc_f32(pts[i].z + 0.0f) << 32) | (u32)i;  // -0.0f + 0.0f = +0.0f: equal heights, one key
 }
 
 __global__ __launch_bounds__(256) void k_pw_bin(const float4* __restrict__ pts, int P, PwDev pw,
@@ -56,7 +56,8 @@ __global__ __launch_bounds__(256) void k_pw_bin(const float4* __restrict__ pts, 
   const u32 i = (u32)zsorted[t];
   const float4 q = pts[i];
   u32 pid = PW_DROPPED;
-  if (!((double)q.z < -1.8 * pw.sensor_height)) {
+  const bool finite = (q.x - q.x == 0.f) && (q.y - q.y == 0.f) && (q.z - q.z == 0.f);  // else: in no patch
+  if (finite && !((double)q.z < -1.8 * pw.sensor_height)) {
     const double x = q.x, y = q.y;
     const double r = sqrt(x * x + y * y);
     if ((r <= pw.max_range) && (r > pw.min_range)) {

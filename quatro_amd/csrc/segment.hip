@@ -46,6 +46,7 @@ struct SegBufs {
 __device__ __forceinline__ bool ip_pixel_of(const IpDev& ip, float x, float y, float z, int* pix) {
   const float va = (float)((double)(qm_atan2f(z, sqrtf(x * x + y * y)) * 180) / M_PI);
   const float rf = (va + ip.ang_bottom) / ip.ang_res_y;
+  if (rf != rf) return false;  // NaN: no pixel (the conversion below would give 0 here, the most negative value on x86)
   const long long r = (long long)rf;
   if (r < 0 || r >= ip.n_scan) return false;
   const float ha = (float)((double)(qm_atan2f(x, y) * 180) / M_PI);
