@@ -2370,9 +2370,8 @@ static int place_scratch_ensure(qtr_handle* h, Slot& s, int stride, int cap) {
   if (sc.arena && stride <= sc.stride && cap <= sc.cap) return QTR_OK;
   stride = std::max(stride, sc.stride);
   cap = std::max(std::max(cap, sc.cap), 1);
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t o_keys = up((size_t)stride * 4), o_shifts = o_keys + up((size_t)cap * 8), o_out = o_shifts + up((size_t)cap * 4),
-               total = o_out + up(sizeof(qtr_place_match) * QTR_PLACE_MAX_K);
+  const size_t o_keys = qtr_up256((size_t)stride * 4), o_shifts = o_keys + qtr_up256((size_t)cap * 8), o_out = o_shifts + qtr_up256((size_t)cap * 4),
+               total = o_out + qtr_up256(sizeof(qtr_place_match) * QTR_PLACE_MAX_K);
   if (sc.arena) {
     QTR_HIP_TRY(h, hipStreamSynchronize(s.stream));
     (void)hipFree(sc.arena);
@@ -3797,8 +3796,8 @@ static int eval_device(qtr_handle* h, Slot& s, const EvalPair* P, int B, double 
     for (int k = 0; k < 16; ++k) out[b].T[k] = P[b].T[k];
     eval_result_from(&out[b], empty);
     const int nchunk = qtr_div_up(P[b].ns, QTR_ICP_CHUNK);
-    var += eval_up((size_t)nchunk * QTR_EVAL_NT * 8) + 2 * eval_up((size_t)P[b].nt * 16) + eval_up((size_t)P[b].nt * 8) +
-           eval_up((size_t)P[b].ns * 4);
+    var += qtr_up256((size_t)nchunk * QTR_EVAL_NT * 8) + 2 * qtr_up256((size_t)P[b].nt * 16) + qtr_up256((size_t)P[b].nt * 8) +
+           qtr_up256((size_t)P[b].ns * 4);
     max_nt = std::max(max_nt, P[b].nt);
     max_nchunk = std::max(max_nchunk, nchunk);
   }
@@ -3808,7 +3807,7 @@ static int eval_device(qtr_handle* h, Slot& s, const EvalPair* P, int B, double 
   char* p = E.d_var;
   auto take = [&](size_t n) {
     char* r = p;
-    p += eval_up(n);
+    p += qtr_up256(n);
     return r;
   };
   for (int b = 0; b < B; ++b) {

@@ -18,6 +18,7 @@
 
 #include "../../include/qtr_math.h"
 #include "../../include/quatro_hip.h"
+#include "vmap_group_plan.h"  // qtr_up256: the one 256-byte round-up
 
 // -DQTR_NN_TIMING (diagnostic build, tests/probe/nn_stamps.py — never the shipped library): QTR_STAMP(kernel, point) lets
 // thread 0 of the first 32 workgroups (x) of a launch's (y, z) = (0, 0) plane record the shader clock and the 100 MHz wall
@@ -195,11 +196,6 @@ __device__ __forceinline__ void mail_store_line(int* __restrict__ line, int t, i
 }
 
 // ---- host-side plumbing ------------------------------------------------------------------------
-struct QtrDeviceBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
 #define QTR_HIP_TRY(h, expr)                                                                       \
   do {                                                                                             \
     hipError_t _e = (expr);                                                                        \
@@ -223,7 +219,7 @@ struct ViewStage {
   size_t cap = 0, off = 0;
 };
 static inline const void* stage_push(ViewStage* s, const void* src, size_t bytes, hipStream_t st) {
-  const size_t padded = (bytes + 255) & ~(size_t)255;
+  const size_t padded = qtr_up256(bytes);
   if (!s || !s->h || s->off + padded > s->cap) return nullptr;
   memcpy(s->h + s->off, src, bytes);
   if (hipMemcpyAsync(s->d + s->off, s->h + s->off, padded, hipMemcpyHostToDevice, st) != hipSuccess) return nullptr;

@@ -98,24 +98,23 @@ struct EvalBufs {
   int last_ns = 0;
 };
 
-static size_t eval_up(size_t n) { return (n + 255) & ~(size_t)255; }
 static size_t eval_fixed_bytes() {
-  return eval_up((sizeof(IcpView) + sizeof(QtrIcpState)) * QTR_EVAL_MAX_BATCH) + eval_up(sizeof(QtrIcpState) * QTR_EVAL_MAX_BATCH) +
-         eval_up(32 * QTR_EVAL_MAX_BATCH) + eval_up(64 * QTR_EVAL_MAX_BATCH) + eval_up(sizeof(QtrEvalRecord) * QTR_EVAL_MAX_BATCH);
+  return qtr_up256((sizeof(IcpView) + sizeof(QtrIcpState)) * QTR_EVAL_MAX_BATCH) + qtr_up256(sizeof(QtrIcpState) * QTR_EVAL_MAX_BATCH) +
+         qtr_up256(32 * QTR_EVAL_MAX_BATCH) + qtr_up256(64 * QTR_EVAL_MAX_BATCH) + qtr_up256(sizeof(QtrEvalRecord) * QTR_EVAL_MAX_BATCH);
 }
 
 static hipError_t eval_reserve(EvalBufs& E, size_t var_bytes) {
   if (!E.pin) {
-    const size_t pb = eval_up((sizeof(IcpView) + sizeof(QtrIcpState)) * QTR_EVAL_MAX_BATCH) + eval_up(32 * QTR_EVAL_MAX_BATCH) +
-                      eval_up(sizeof(QtrEvalRecord) * QTR_EVAL_MAX_BATCH);
+    const size_t pb = qtr_up256((sizeof(IcpView) + sizeof(QtrIcpState)) * QTR_EVAL_MAX_BATCH) + qtr_up256(32 * QTR_EVAL_MAX_BATCH) +
+                      qtr_up256(sizeof(QtrEvalRecord) * QTR_EVAL_MAX_BATCH);
     hipError_t e = hipHostMalloc((void**)&E.pin, pb);
     if (e != hipSuccess) return e;
     char* p = E.pin;
     E.h_views = (IcpView*)p;
     E.h_init = (QtrIcpState*)(E.h_views + QTR_EVAL_MAX_BATCH);
-    p += eval_up((sizeof(IcpView) + sizeof(QtrIcpState)) * QTR_EVAL_MAX_BATCH);
+    p += qtr_up256((sizeof(IcpView) + sizeof(QtrIcpState)) * QTR_EVAL_MAX_BATCH);
     E.h_boxes = (int*)p;
-    p += eval_up(32 * QTR_EVAL_MAX_BATCH);
+    p += qtr_up256(32 * QTR_EVAL_MAX_BATCH);
     E.h_rec = (QtrEvalRecord*)p;
   }
   const size_t need = eval_fixed_bytes() + var_bytes;
@@ -132,15 +131,15 @@ static hipError_t eval_reserve(EvalBufs& E, size_t var_bytes) {
   char* p = (char*)E.arena;
   E.d_views = (IcpView*)p;
   E.d_init = (QtrIcpState*)(E.d_views + QTR_EVAL_MAX_BATCH);
-  p += eval_up((sizeof(IcpView) + sizeof(QtrIcpState)) * QTR_EVAL_MAX_BATCH);
+  p += qtr_up256((sizeof(IcpView) + sizeof(QtrIcpState)) * QTR_EVAL_MAX_BATCH);
   E.d_state = (QtrIcpState*)p;
-  p += eval_up(sizeof(QtrIcpState) * QTR_EVAL_MAX_BATCH);
+  p += qtr_up256(sizeof(QtrIcpState) * QTR_EVAL_MAX_BATCH);
   E.d_boxes = (int*)p;
-  p += eval_up(32 * QTR_EVAL_MAX_BATCH);
+  p += qtr_up256(32 * QTR_EVAL_MAX_BATCH);
   E.d_tickets = (unsigned*)p;
-  p += eval_up(64 * QTR_EVAL_MAX_BATCH);
+  p += qtr_up256(64 * QTR_EVAL_MAX_BATCH);
   E.d_rec = (QtrEvalRecord*)p;
-  p += eval_up(sizeof(QtrEvalRecord) * QTR_EVAL_MAX_BATCH);
+  p += qtr_up256(sizeof(QtrEvalRecord) * QTR_EVAL_MAX_BATCH);
   E.d_var = p;
   return hipSuccess;
 }

@@ -180,7 +180,6 @@ __global__ __launch_bounds__(1024) void k_place_select_group(const u64* __restri
   if (tid == 0) n_out[blockIdx.x] = round;
 }
 
-static inline size_t pb_up(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int qtr_place_query_batch(qtr_handle* h, int slot, const qtr_place_index* ix, const qtr_place_query_item* items, int Q, int k,
                           qtr_place_match* out, int* n_out) {
@@ -273,12 +272,12 @@ int qtr_place_query_batch(qtr_handle* h, int slot, const qtr_place_index* ix, co
   // other slots directly behind them, the score table, the records and counts (one copy back)
   const int ns = nh + nd + nk;
   const size_t slot_bytes = (size_t)stride * 4;
-  const size_t o_qtab = 0, o_kftab = o_qtab + pb_up((size_t)Q * sizeof(PbQuery)), o_gtab = o_kftab + pb_up((size_t)nk * sizeof(PbKf)),
-               o_slots = o_gtab + pb_up((size_t)nd * sizeof(PbGather)), head_bytes = o_slots + (size_t)nh * slot_bytes,
-               o_keys = pb_up(o_slots + (size_t)ns * slot_bytes), o_shifts = o_keys + pb_up((size_t)Q * U * 8),
-               o_back = o_shifts + pb_up((size_t)Q * U * 4), out_bytes = (size_t)Q * k * sizeof(qtr_place_match),
-               back_bytes = out_bytes + (size_t)Q * 4, need = o_back + pb_up(back_bytes);
-  const size_t o_pin_back = pb_up(head_bytes), pin_need = o_pin_back + back_bytes;
+  const size_t o_qtab = 0, o_kftab = o_qtab + qtr_up256((size_t)Q * sizeof(PbQuery)), o_gtab = o_kftab + qtr_up256((size_t)nk * sizeof(PbKf)),
+               o_slots = o_gtab + qtr_up256((size_t)nd * sizeof(PbGather)), head_bytes = o_slots + (size_t)nh * slot_bytes,
+               o_keys = qtr_up256(o_slots + (size_t)ns * slot_bytes), o_shifts = o_keys + qtr_up256((size_t)Q * U * 8),
+               o_back = o_shifts + qtr_up256((size_t)Q * U * 4), out_bytes = (size_t)Q * k * sizeof(qtr_place_match),
+               back_bytes = out_bytes + (size_t)Q * 4, need = o_back + qtr_up256(back_bytes);
+  const size_t o_pin_back = qtr_up256(head_bytes), pin_need = o_pin_back + back_bytes;
   if (need > pb.dev_bytes) {
     QTR_HIP_TRY(h, hipStreamSynchronize(st));
     if (pb.dev) (void)hipFree(pb.dev);

@@ -23,6 +23,7 @@
 #include "voxelmap.hip"
 #include "voxelmap_keep.hip"
 #include "voxelmap_carve.hip"
+#include "voxelmap_group.hip"
 #include "voxelmap_batch.hip"
 #include "voxelmap_eval.hip"
 #include "deskew.hip"

@@ -289,6 +289,16 @@ static int vmap_check_kf(qtr_handle* h, const qtr_keyframe* kf) {
   return QTR_OK;
 }
 
+// a keyframe as the map's entries read it, in place: its voxel centroids, their normals, their number
+struct VmapKfCloud {
+  const float4 *pts, *nrm;
+  int n;
+};
+static VmapKfCloud vmap_kf_cloud(const qtr_keyframe* kf) {
+  const KfLayout lay = kf_layout(kf->info.n_voxels);
+  return {(const float4*)((const char*)kf->dev + lay.vox), (const float4*)((const char*)kf->dev + lay.normals), kf->info.n_voxels};
+}
+
 static void vmap_release(qtr_voxel_map* m) {
   if (m->stream) {
     (void)hipStreamSynchronize(m->stream);
@@ -335,7 +345,7 @@ int qtr_voxel_map_create(qtr_handle* h, const qtr_voxel_map_params* params, qtr_
   while (S < (size_t)2 * (size_t)prm.capacity) S <<= 1;
   qtr_voxel_map* m = new (std::nothrow) qtr_voxel_map();
   if (!m) return QTR_ERR_CAPACITY;
-  const size_t rec_bytes = (S * sizeof(QtrIcpVoxel) + 255) & ~(size_t)255;
+  const size_t rec_bytes = qtr_up256(S * sizeof(QtrIcpVoxel));
   const size_t bytes = S * 8 + S * 72 + rec_bytes + 3 * S * 4 + 1024;
   hipError_t e = hipMalloc(&m->table, bytes);
   if (e == hipSuccess) e = hipHostMalloc((void**)&m->pin, VM_CTR_INTS * sizeof(int));
@@ -477,16 +487,15 @@ static int vmap_insert_device(qtr_handle* h, Slot& s, qtr_voxel_map* m, const fl
   return QTR_OK;
 }
 
-// What the two cloud entries do with their cloud before anything runs: the argument checks in the entry's own words (verb:
-// "insert" / "register"; nrm_name: its normals' argument; pose: the insert's, null for a registration, whose guess is checked
-// before), then a host cloud and its normals into in_src / in_tgt.  pts / nrm come back as device pointers.
-static int vmap_stage(qtr_handle* h, Slot& s, const char* verb, const char* nrm_name, const double* pose, int mem, int n,
-                      const float4** pts, const float4** nrm) {
-  if (n < 0 || (n > 0 && !*pts) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) {
+// The check of a cloud given by pointers, for every entry that takes one, in the entry's own words (verb: "insert" /
+// "register" / "evaluate"; nrm_name: its normals' argument; pose: the insert's, null where a guess or pose is checked apart).
+static int vmap_check_cloud(qtr_handle* h, const char* verb, const char* nrm_name, const double* pose, int mem, int n,
+                            const void* pts, const void* nrm) {
+  if (n < 0 || (n > 0 && !pts) || (mem != QTR_MEM_HOST && mem != QTR_MEM_DEVICE)) {
     snprintf(h->err, sizeof(h->err), "bad voxel map %s arguments", verb);
     return QTR_ERR_BAD_ARG;
   }
-  if (!*nrm) {
+  if (!nrm) {
     snprintf(h->err, sizeof(h->err), "voxel map %s: %s is NULL (the cloud entries do not compute normals)", verb, nrm_name);
     return QTR_ERR_BAD_ARG;
   }
@@ -495,6 +504,14 @@ static int vmap_stage(qtr_handle* h, Slot& s, const char* verb, const char* nrm_
     snprintf(h->err, sizeof(h->err), "voxel map %s: n=%d exceeds max_points=%d", verb, n, h->lim.max_points);
     return QTR_ERR_CAPACITY;
   }
+  return QTR_OK;
+}
+
+// What the two cloud entries do with their cloud before anything runs: vmap_check_cloud, then a host cloud and its normals
+// into in_src / in_tgt.  pts / nrm come back as device pointers.
+static int vmap_stage(qtr_handle* h, Slot& s, const char* verb, const char* nrm_name, const double* pose, int mem, int n,
+                      const float4** pts, const float4** nrm) {
+  QTR_TRY(vmap_check_cloud(h, verb, nrm_name, pose, mem, n, *pts, *nrm));
   QTR_HIP_TRY(h, hipSetDevice(h->device));
   if (mem == QTR_MEM_HOST && n > 0) {
     QTR_HIP_TRY(h, hipMemcpyAsync(s.in_src, *pts, (size_t)n * 16, hipMemcpyHostToDevice, s.stream));
@@ -526,9 +543,8 @@ int qtr_voxel_map_insert_keyframe(qtr_handle* h, int slot, qtr_voxel_map* m, con
   QTR_TRY(vmap_check_kf(h, kf));
   QTR_TRY(vmap_check_pose(h, "insert", "pose", pose));
   QTR_HIP_TRY(h, hipSetDevice(h->device));
-  const KfLayout lay = kf_layout(kf->info.n_voxels);
-  return vmap_insert_device(h, *sp, m, (const float4*)((const char*)kf->dev + lay.vox),
-                            (const float4*)((const char*)kf->dev + lay.normals), kf->info.n_voxels, pose, out);
+  const VmapKfCloud c = vmap_kf_cloud(kf);
+  return vmap_insert_device(h, *sp, m, c.pts, c.nrm, c.n, pose, out);
 }
 
 // the registration of ns device-resident points with their normals: icp_loop (capi.hip) with the empty grid, only the
@@ -599,11 +615,10 @@ int qtr_voxel_map_register_keyframe(qtr_handle* h, int slot, const qtr_voxel_map
   if (rc != QTR_OK) return res->status = rc;
   rc = [&]() -> int {
     QTR_HIP_TRY(h, hipSetDevice(h->device));
-    const KfLayout lay = kf_layout(kf->info.n_voxels);
+    const VmapKfCloud c = vmap_kf_cloud(kf);
     double g[16];
     vmap_guess(guess, g);
-    return vmap_register_device(h, *sp, m, (const float4*)((const char*)kf->dev + lay.vox), kf->info.n_voxels,
-                                (const float4*)((const char*)kf->dev + lay.normals), g, prm, res);
+    return vmap_register_device(h, *sp, m, c.pts, c.n, c.nrm, g, prm, res);
   }();
   return res->status = rc;
 }

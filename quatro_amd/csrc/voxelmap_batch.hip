@@ -20,10 +20,9 @@
 //
 // The arena is the slot's own (Slot::vbatch), never its IcpBufs: the slot's single-call ICP state and what qtr_debug_fetch
 // serves for it stay as they were.  Per item it holds one IcpView, one QtrIcpState, a ticket on a line of its own, the partial
-// sums (ceil(n / QTR_ICP_CHUNK) x QTR_ICP_NT doubles), the trace (max_iterations x 18 doubles) and corr (n ints).  Keyframes
-// and device-resident clouds are read in place, so items that name the same keyframe or the same device pointers share their
-// source arrays; host items with the same pointers share one staged copy.  Allocated on the slot's first batch, grown to a
-// call's need, freed with the handle.
+// sums (ceil(n / QTR_ICP_CHUNK) x QTR_ICP_NT doubles), the trace (max_iterations x 18 doubles) and corr (n ints); behind
+// them lie the staged host clouds.  The arena itself, the item check, the staging and the fetch's tail are voxelmap_group.hip,
+// shared with the evaluation (voxelmap_eval.hip).
 // The map is only read.  No kernel waits for another workgroup, none is launched cooperatively, all stores are plain vector
 // stores.
 #include "../../include/quatro_voxelmap_batch.h"
@@ -47,43 +46,25 @@ __global__ __launch_bounds__(256) void k_vmap_iter_group(ViewExt<IcpView> x, Vma
 
 // ---- host side ----------------------------------------------------------------------------------------------------
 enum { VB_EV_BEGIN = 0, VB_EV_LOOP, VB_EV_END, VB_EV_COUNT };
+static_assert(VB_EV_COUNT <= VG_EV_MAX, "the arena's events");
 
-struct VmapBatch {
-  void* dev = nullptr;  // the arena
-  size_t dev_bytes = 0;
-  void* pin = nullptr;  // pinned: QTR_VMAP_BATCH_MAX views, initial states and read-back states
-  hipEvent_t ev[VB_EV_COUNT] = {};
-  // the slot's last batch, for qtr_voxel_map_batch_fetch
-  int B = -1;  // (-1: none)
+// the slot's arena (voxelmap_group.hip) and what qtr_voxel_map_batch_fetch serves of its last batch; pinned:
+// QTR_VMAP_BATCH_MAX views, initial states and read-back states
+struct VmapBatch : VmapArena {
   int n[QTR_VMAP_BATCH_MAX] = {}, iters[QTR_VMAP_BATCH_MAX] = {};
   const double* trace[QTR_VMAP_BATCH_MAX] = {};
   const int* corr[QTR_VMAP_BATCH_MAX] = {};
   float ms[2] = {0.f, 0.f};
 };
 
-static constexpr size_t vb_up(size_t b) { return (b + 255) & ~(size_t)255; }
 // (pinned: the views and, behind them, the initial states of a call; then the read-back states)
-static const size_t kVbPinBack = vb_up(QTR_VMAP_BATCH_MAX * sizeof(IcpView)) + vb_up(QTR_VMAP_BATCH_MAX * sizeof(QtrIcpState));
-static const size_t kVbPinBytes = kVbPinBack + vb_up(QTR_VMAP_BATCH_MAX * sizeof(QtrIcpState));
+static const size_t kVbPinBack = qtr_up256(QTR_VMAP_BATCH_MAX * sizeof(IcpView)) + qtr_up256(QTR_VMAP_BATCH_MAX * sizeof(QtrIcpState));
+static const size_t kVbPinBytes = kVbPinBack + qtr_up256(QTR_VMAP_BATCH_MAX * sizeof(QtrIcpState));
 
-static void vmap_batch_free(Slot& s) {
-  VmapBatch* vb = s.vbatch;
-  if (!vb) return;
-  if (vb->dev) (void)hipFree(vb->dev);
-  if (vb->pin) (void)hipHostFree(vb->pin);
-  for (hipEvent_t e : vb->ev)
-    if (e) (void)hipEventDestroy(e);
-  delete vb;
-  s.vbatch = nullptr;
-}
+static void vmap_batch_free(Slot& s) { vmap_arena_free(s.vbatch); }
 
-// one item as the run sees it: device-resident or to be staged
-struct VbItem {
-  const float4 *src = nullptr, *nrm = nullptr;  // the caller's pointers (host or device)
-  int n = 0;
-  bool host = false;
-  int same_as = -1;  // host item: an earlier host item with the same pointers and size, whose staged copy it reads
-  size_t o_partials = 0, o_trace = 0, o_corr = 0, o_src = 0, o_nrm = 0;  // offsets into the arena
+struct VbItem : VmapGroupItem {
+  size_t o_partials = 0, o_trace = 0, o_corr = 0;  // offsets into the arena
 };
 
 static int vmap_batch_check(qtr_handle* h, const qtr_voxel_map* m, const qtr_vmap_reg_item* items, int B, const qtr_icp_params* prm,
@@ -94,102 +75,34 @@ static int vmap_batch_check(qtr_handle* h, const qtr_voxel_map* m, const qtr_vma
     snprintf(h->err, sizeof(h->err), "voxel map register batch: method must be QTR_ICP_VOXEL_PLANE_TO_PLANE");
     return QTR_ERR_BAD_ARG;
   }
-  for (int i = 0; i < B; ++i) {
-    const qtr_vmap_reg_item& a = items[i];
-    int rc = QTR_OK;
-    if (a.kf) {
-      rc = vmap_check_kf(h, a.kf);
-      if (rc == QTR_OK) {
-        const KfLayout lay = kf_layout(a.kf->info.n_voxels);
-        it[i].src = (const float4*)((const char*)a.kf->dev + lay.vox);
-        it[i].nrm = (const float4*)((const char*)a.kf->dev + lay.normals);
-        it[i].n = a.kf->info.n_voxels;
-        it[i].host = false;
-      }
-    } else if (a.n < 0 || (a.n > 0 && !a.src4) || (a.mem != QTR_MEM_HOST && a.mem != QTR_MEM_DEVICE)) {
-      snprintf(h->err, sizeof(h->err), "bad voxel map register arguments");
-      rc = QTR_ERR_BAD_ARG;
-    } else if (!a.src_normals4) {
-      snprintf(h->err, sizeof(h->err), "voxel map register: src_normals4 is NULL (the cloud entries do not compute normals)");
-      rc = QTR_ERR_BAD_ARG;
-    } else if (a.n > h->lim.max_points) {
-      snprintf(h->err, sizeof(h->err), "voxel map register: n=%d exceeds max_points=%d", a.n, h->lim.max_points);
-      rc = QTR_ERR_CAPACITY;
-    } else {
-      it[i].src = (const float4*)a.src4;
-      it[i].nrm = (const float4*)a.src_normals4;
-      it[i].n = a.n;
-      it[i].host = a.mem == QTR_MEM_HOST;
-    }
-    if (rc == QTR_OK) rc = vmap_check_pose(h, "register", "guess", a.guess);
-    if (rc != QTR_OK) {
-      char msg[sizeof(h->err)];
-      snprintf(msg, sizeof(msg), "%s", h->err);
-      snprintf(h->err, sizeof(h->err), "batch item %d: %.480s", i, msg);
-      return rc;
-    }
-  }
-  return QTR_OK;
+  return vmap_group_check(h, "register", "guess", "batch item", items, B, it);
 }
 
 static int vmap_batch_run(qtr_handle* h, Slot& s, const qtr_voxel_map* m, const qtr_vmap_reg_item* items, int B,
                           const qtr_icp_params* prm, VbItem* it, qtr_icp_result* results) {
   QTR_HIP_TRY(h, hipSetDevice(h->device));
-  if (!s.vbatch) {
-    VmapBatch* nb = new (std::nothrow) VmapBatch();
-    if (!nb) return QTR_ERR_CAPACITY;
-    s.vbatch = nb;  // (from here on the handle frees whatever of it exists)
-    QTR_HIP_TRY(h, hipHostMalloc(&nb->pin, kVbPinBytes));
-    for (hipEvent_t& e : nb->ev) QTR_HIP_TRY(h, hipEventCreate(&e));
-  }
+  QTR_TRY(vmap_arena_open(h, s.vbatch, kVbPinBytes, VB_EV_COUNT));
   VmapBatch& vb = *s.vbatch;
-  if (!vb.pin) QTR_HIP_TRY(h, hipHostMalloc(&vb.pin, kVbPinBytes));
-  for (hipEvent_t& e : vb.ev)
-    if (!e) QTR_HIP_TRY(h, hipEventCreate(&e));
   const hipStream_t st = s.stream;
   const int maxit = prm->max_iterations;
 
-  // the arena's layout for this call
-  size_t need = 0;
-  const auto take = [&](size_t bytes) {
-    const size_t at = need;
-    need += vb_up(bytes ? bytes : 1);
-    return at;
-  };
-  const size_t o_views = take((size_t)B * sizeof(IcpView));
-  const size_t o_init = take((size_t)B * sizeof(QtrIcpState));
-  const size_t o_state = take((size_t)B * sizeof(QtrIcpState));
-  const size_t o_ticket = take((size_t)B * 64);
+  // the arena's layout for this call: the head, every item's own sections, then the staged clouds
+  VmapCursor cur;
+  const size_t o_views = cur.take((size_t)B * sizeof(IcpView));
+  const size_t o_init = cur.take((size_t)B * sizeof(QtrIcpState));
+  const size_t o_state = cur.take((size_t)B * sizeof(QtrIcpState));
+  const size_t o_ticket = cur.take((size_t)B * 64);
   const size_t head_bytes = o_init + (size_t)B * sizeof(QtrIcpState);  // views and initial states: one upload
   int max_chunks = 0;
   for (int i = 0; i < B; ++i) {
     const int nchunk = qtr_div_up(it[i].n, QTR_ICP_CHUNK);
     max_chunks = std::max(max_chunks, nchunk);
-    it[i].o_partials = take((size_t)nchunk * QTR_ICP_NT * 8);
-    it[i].o_trace = take((size_t)maxit * 18 * 8);
-    it[i].o_corr = take((size_t)it[i].n * 4);
-    it[i].same_as = -1;
-    if (it[i].host && it[i].n > 0) {
-      for (int j = 0; j < i && it[i].same_as < 0; ++j)
-        if (it[j].host && it[j].n == it[i].n && it[j].src == it[i].src && it[j].nrm == it[i].nrm) it[i].same_as = j;
-      if (it[i].same_as < 0) {
-        it[i].o_src = take((size_t)it[i].n * 16);
-        it[i].o_nrm = take((size_t)it[i].n * 16);
-      } else {
-        it[i].o_src = it[it[i].same_as].o_src;
-        it[i].o_nrm = it[it[i].same_as].o_nrm;
-      }
-    }
+    it[i].o_partials = cur.take((size_t)nchunk * QTR_ICP_NT * 8);
+    it[i].o_trace = cur.take((size_t)maxit * 18 * 8);
+    it[i].o_corr = cur.take((size_t)it[i].n * 4);
   }
-  vb.B = -1;  // (the last batch's sections are gone once this one writes the arena)
-  if (need > vb.dev_bytes) {
-    QTR_HIP_TRY(h, hipStreamSynchronize(st));
-    if (vb.dev) (void)hipFree(vb.dev);
-    vb.dev = nullptr;
-    vb.dev_bytes = 0;
-    QTR_HIP_TRY(h, hipMalloc(&vb.dev, need));
-    vb.dev_bytes = need;
-  }
+  vmap_group_plan(it, B, cur);
+  QTR_TRY(vmap_arena_grow(h, vb, cur.need, st));
   char* const dev = (char*)vb.dev;
   // (the upload's layout is this call's: the initial states follow the B views as they do in the arena)
   IcpView* const hv = (IcpView*)vb.pin;
@@ -198,21 +111,13 @@ static int vmap_batch_run(qtr_handle* h, Slot& s, const qtr_voxel_map* m, const 
   QtrIcpState* const dstate = (QtrIcpState*)(dev + o_state);
 
   QTR_HIP_TRY(h, hipEventRecord(vb.ev[VB_EV_BEGIN], st));
+  QTR_TRY(vmap_group_upload(h, dev, it, B, st));
   for (int i = 0; i < B; ++i) {
     double g[16];
     vmap_guess(items[i].guess, g);
     qtr_icp_init(&hinit[i], g);
-    const float4 *src = it[i].src, *nrm = it[i].nrm;
-    if (it[i].host && it[i].n > 0) {
-      if (it[i].same_as < 0) {
-        QTR_HIP_TRY(h, hipMemcpyAsync(dev + it[i].o_src, src, (size_t)it[i].n * 16, hipMemcpyHostToDevice, st));
-        QTR_HIP_TRY(h, hipMemcpyAsync(dev + it[i].o_nrm, nrm, (size_t)it[i].n * 16, hipMemcpyHostToDevice, st));
-      }
-      src = (const float4*)(dev + it[i].o_src);
-      nrm = (const float4*)(dev + it[i].o_nrm);
-    }
     IcpView v{};
-    icp_view_bind(v, prm, src, it[i].n, nrm, nullptr, 0, nullptr);
+    icp_view_bind(v, prm, (const float4*)it[i].src, it[i].n, (const float4*)it[i].nrm, nullptr, 0, nullptr);
     v.ncell = v.dims[0] = v.dims[1] = v.dims[2] = 0;
     v.cfg.max_d2 = m->v.side * m->v.side;  // (not read: the side is the map's)
     v.st = dstate + i;
@@ -310,11 +215,5 @@ long long qtr_voxel_map_batch_fetch(qtr_handle* h, int slot, int item, int what,
     case QTR_VMAP_BATCH_CORR: src = vb.corr[item]; have = (size_t)vb.n[item] * 4; break;
     default: return -1;
   }
-  const size_t n = have < bytes ? have : bytes;
-  if (dst && n > 0) {
-    if (hipSetDevice(h->device) != hipSuccess) return -1;
-    if (hipStreamSynchronize(sp->stream) != hipSuccess) return -1;
-    if (hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  }
-  return (long long)have;
+  return vmap_group_fetch(h, *sp, src, have, dst, bytes);
 }

@@ -16,9 +16,10 @@
 //                   verdict goes to one byte per slot (0 no voxel, 1 kept, 2 carved), and the counts (kept, carved, tested,
 //                   carved members as 64-bit) are summed per workgroup in LDS and leave it as at most four atomics
 //   (host)          nothing carved: return, the table was only read.
-//   k_carve_stage   k_vmap_keep_stage's pattern with the byte as the verdict: every survivor's key, count, acc and record
-//                   into the eviction's staging;  then k_vmap_clear and k_vmap_keep_put, exactly as qtr_voxel_map_evict ends.
-//                   The table is rebuilt, never punched (voxelmap_keep.hip says why).
+//   (rebuild)       vmap_keep_rebuild (voxelmap_keep.hip), the end qtr_voxel_map_evict has too, with k_carve_stage as its
+//                   staging kernel: d_vmap_stage_kept with the byte as the verdict, every survivor's key, count, acc and
+//                   record into the eviction's staging; then k_vmap_clear and k_vmap_keep_put.  The table is rebuilt, never
+//                   punched (voxelmap_keep.hip says why).
 // The mark pass visits every slot and not a compacted list of the live ones: with capacity-sized tables most lanes see an
 // empty key and leave at once, and a compaction would be a pass over the same S keys.  The two were not measured against
 // each other.
@@ -107,40 +108,10 @@ __global__ __launch_bounds__(256) void k_carve_mark(VmapView m, QtrCarveCfg c, c
   }
 }
 
-// The survivors' key, count, acc and record into staging: k_vmap_keep_stage with the verdict read from the byte array.  S and
-// the grid's stride are multiples of the wave, so a wave is in the loop with all its lanes or with none.
+// the rebuild's staging pass (d_vmap_stage_kept, voxelmap_keep.hip) with the mark byte as the verdict
 __global__ __launch_bounds__(256) void k_carve_stage(VmapView m, const unsigned char* __restrict__ mark, VmapStage st, int n_kept) {
-  __shared__ int s_n, s_base, s_cursor;
-  if (threadIdx.x == 0) {
-    s_n = 0;
-    s_cursor = 0;
-  }
-  __syncthreads();
-  int mine = 0;
-  for (u64 e = blockIdx.x * (u64)blockDim.x + threadIdx.x; e <= m.mask; e += (u64)gridDim.x * blockDim.x)
-    mine += mark[e] == CV_KEPT ? 1 : 0;
-  if (mine) atomicAdd(&s_n, mine);
-  __syncthreads();
-  if (threadIdx.x == 0) s_base = s_n ? atomicAdd(st.ctr + VK_CTR_STAGED, s_n) : 0;
-  __syncthreads();
-  if (s_n == 0) return;
-  const int base = s_base;
-  for (u64 e = blockIdx.x * (u64)blockDim.x + threadIdx.x; e <= m.mask; e += (u64)gridDim.x * blockDim.x) {
-    const bool keep = mark[e] == CV_KEPT;
-    const u64 bal = __ballot(keep);
-    if (!bal) continue;  // (the whole wave)
-    int at = 0;
-    if (qk_lane() == 0) at = atomicAdd(&s_cursor, __popcll(bal));
-    at = __shfl(at, 0, 64);
-    const int j = base + at + __popcll(bal & lanemask_lt());
-    if (keep && j >= 0 && j < n_kept) {  // (the bounds: never outside, the mark pass counted exactly these slots)
-      st.keys[j] = m.keys[e];
-      st.cnt[j] = m.cnt[e];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) st.acc[(size_t)j * 9 + k] = m.acc[(size_t)e * 9 + k];
-      st.rec[j] = m.rec[e];
-    }
-  }
+  d_vmap_stage_kept(m, st, n_kept, blockIdx.x * (u64)blockDim.x + threadIdx.x, (u64)gridDim.x * blockDim.x,
+                    [&](u64 e) { return mark[e] == CV_KEPT; });
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
@@ -237,23 +208,9 @@ static int carve_device(qtr_handle* h, Slot& s, qtr_voxel_map* m, const CarveSca
   info.n_carved = m->pin[VK_CTR_EVICTED];
   info.n_tested = m->pin[CV_CTR_TESTED];
   memcpy(&info.n_members_carved, m->pin + VK_CTR_MEMBERS64, 8);
-  if (info.n_kept + info.n_carved != m->info.n_voxels) {
-    snprintf(h->err, sizeof(h->err), "voxel map carve: the table holds %d voxels, the map says %d", info.n_kept + info.n_carved,
-             m->info.n_voxels);
-    return QTR_ERR_HIP;
-  }
-  if (info.n_carved > 0) {
-    if (info.n_kept > 0) hipLaunchKernelGGL(k_carve_stage, tgrid, blk, 0, q, m->v, m->carve_mark, st, info.n_kept);
-    hipLaunchKernelGGL(k_vmap_clear, tgrid, blk, 0, q, m->v, m->ins.tcnt);
-    if (info.n_kept > 0) hipLaunchKernelGGL(k_vmap_keep_put, dim3(qtr_div_up(info.n_kept, 256)), blk, 0, q, m->v, st, info.n_kept);
-    QTR_TRY(vmap_keep_read(h, m, st, q));
-    m->info.n_voxels = info.n_kept;
-    m->info.n_members -= info.n_members_carved;
-    if (m->pin[VK_CTR_DUP]) {  // (never: the survivors' keys are distinct and fewer than the slots)
-      snprintf(h->err, sizeof(h->err), "voxel map carve: the rebuild met a key twice");
-      return QTR_ERR_HIP;
-    }
-  }
+  QTR_TRY(vmap_keep_rebuild(h, m, st, q, "carve", info.n_kept, info.n_carved, info.n_members_carved, [&](dim3 grid, dim3 blk) {
+    hipLaunchKernelGGL(k_carve_stage, grid, blk, 0, q, m->v, m->carve_mark, st, info.n_kept);
+  }));
   if (out) *out = info;
   return QTR_OK;
 }
@@ -315,9 +272,9 @@ int qtr_voxel_map_carve_keyframes(qtr_handle* h, int slot, qtr_voxel_map* m, con
   CarveScans sc = {};
   std::vector<double> P((size_t)n_kf * 12);
   for (int k = 0; k < n_kf; ++k) {
-    const KfLayout lay = kf_layout(kfs[k]->info.n_voxels);
-    sc.pts[k] = (const float4*)((const char*)kfs[k]->dev + lay.vox);
-    sc.n[k] = kfs[k]->info.n_voxels;
+    const VmapKfCloud kc = vmap_kf_cloud(kfs[k]);
+    sc.pts[k] = kc.pts;
+    sc.n[k] = kc.n;
     for (int j = 0; j < 12; ++j) P[(size_t)k * 12 + j] = poses[16 * (size_t)k + j];
   }
   return carve_device(h, *sp, m, sc, P.data(), n_kf, c, st, out);

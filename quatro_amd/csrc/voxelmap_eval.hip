@@ -20,8 +20,8 @@
 //
 // The arena is the slot's own (Slot::veval), never its IcpBufs, EvalBufs or batch arena.  Per item it holds one view (with
 // T), a ticket on a line of its own, ceil(n / QTR_ICP_CHUNK) x QTR_VMAP_EVAL_NT partial sums, the record and, with per-point
-// output, n ints and 2 n doubles.  Keyframes and device-resident clouds are read in place; host items with the same pointers
-// share one staged copy.  Allocated on the slot's first evaluation, grown to a call's need, freed with the handle.
+// output, n ints and 2 n doubles; behind them lie the staged host clouds.  The arena itself, the item check, the staging and
+// the fetch's tail are voxelmap_group.hip, shared with the grouped registration (voxelmap_batch.hip).
 // The map is only read.  No kernel waits for another workgroup, none is launched cooperatively, all stores are plain vector
 // stores.
 #include "../../include/quatro_voxelmap_eval.h"
@@ -89,13 +89,9 @@ __global__ __launch_bounds__(256) void k_vmap_eval_group(ViewExt<VevalView> x, V
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-struct VmapEval {
-  void* dev = nullptr;  // the arena
-  size_t dev_bytes = 0;
-  char* pin = nullptr;  // pinned: QTR_VMAP_EVAL_MAX views with their tickets' zeros behind them, then the records' read-back
-  hipEvent_t ev[2] = {};
-  // the slot's last evaluation, for qtr_voxel_map_eval_fetch
-  int B = -1;  // (-1: none)
+// the slot's arena (voxelmap_group.hip) and what qtr_voxel_map_eval_fetch serves of its last evaluation; pinned:
+// QTR_VMAP_EVAL_MAX views with their tickets' zeros behind them, then the records' read-back
+struct VmapEval : VmapArena {
   int per_point = 0;
   int n[QTR_VMAP_BATCH_MAX] = {};
   const int* corr[QTR_VMAP_BATCH_MAX] = {};
@@ -103,69 +99,14 @@ struct VmapEval {
   float ms = 0.f;
 };
 
-static constexpr size_t ve_up(size_t b) { return (b + 255) & ~(size_t)255; }
-static const size_t kVePinBack = ve_up(QTR_VMAP_EVAL_MAX * sizeof(VevalView)) + ve_up((size_t)QTR_VMAP_EVAL_MAX * 64);
-static const size_t kVePinBytes = kVePinBack + ve_up(QTR_VMAP_EVAL_MAX * sizeof(QtrVmapEvalRecord));
+static const size_t kVePinBack = qtr_up256(QTR_VMAP_EVAL_MAX * sizeof(VevalView)) + qtr_up256((size_t)QTR_VMAP_EVAL_MAX * 64);
+static const size_t kVePinBytes = kVePinBack + qtr_up256(QTR_VMAP_EVAL_MAX * sizeof(QtrVmapEvalRecord));
 
-static void vmap_eval_free(Slot& s) {
-  VmapEval* ve = s.veval;
-  if (!ve) return;
-  if (ve->dev) (void)hipFree(ve->dev);
-  if (ve->pin) (void)hipHostFree(ve->pin);
-  for (hipEvent_t e : ve->ev)
-    if (e) (void)hipEventDestroy(e);
-  delete ve;
-  s.veval = nullptr;
-}
+static void vmap_eval_free(Slot& s) { vmap_arena_free(s.veval); }
 
-// one item as the run sees it: device-resident or to be staged
-struct VeItem {
-  const float4 *src = nullptr, *nrm = nullptr;  // the caller's pointers (host or device)
-  int n = 0;
-  bool host = false;
-  int same_as = -1;  // host item: an earlier host item with the same pointers and size, whose staged copy it reads
-  size_t o_partials = 0, o_corr = 0, o_point = 0, o_src = 0, o_nrm = 0;  // offsets into the arena
+struct VeItem : VmapGroupItem {
+  size_t o_partials = 0, o_corr = 0, o_point = 0;  // offsets into the arena
 };
-
-static int vmap_eval_check(qtr_handle* h, const qtr_voxel_map* m, const qtr_vmap_reg_item* items, int B, VeItem* it) {
-  QTR_TRY(vmap_check(h, m));
-  for (int i = 0; i < B; ++i) {
-    const qtr_vmap_reg_item& a = items[i];
-    int rc = QTR_OK;
-    if (a.kf) {
-      rc = vmap_check_kf(h, a.kf);
-      if (rc == QTR_OK) {
-        const KfLayout lay = kf_layout(a.kf->info.n_voxels);
-        it[i].src = (const float4*)((const char*)a.kf->dev + lay.vox);
-        it[i].nrm = (const float4*)((const char*)a.kf->dev + lay.normals);
-        it[i].n = a.kf->info.n_voxels;
-        it[i].host = false;
-      }
-    } else if (a.n < 0 || (a.n > 0 && !a.src4) || (a.mem != QTR_MEM_HOST && a.mem != QTR_MEM_DEVICE)) {
-      snprintf(h->err, sizeof(h->err), "bad voxel map evaluate arguments");
-      rc = QTR_ERR_BAD_ARG;
-    } else if (!a.src_normals4) {
-      snprintf(h->err, sizeof(h->err), "voxel map evaluate: src_normals4 is NULL (the cloud entries do not compute normals)");
-      rc = QTR_ERR_BAD_ARG;
-    } else if (a.n > h->lim.max_points) {
-      snprintf(h->err, sizeof(h->err), "voxel map evaluate: n=%d exceeds max_points=%d", a.n, h->lim.max_points);
-      rc = QTR_ERR_CAPACITY;
-    } else {
-      it[i].src = (const float4*)a.src4;
-      it[i].nrm = (const float4*)a.src_normals4;
-      it[i].n = a.n;
-      it[i].host = a.mem == QTR_MEM_HOST;
-    }
-    if (rc == QTR_OK) rc = vmap_check_pose(h, "evaluate", "pose", a.guess);
-    if (rc != QTR_OK) {
-      char msg[sizeof(h->err)];
-      snprintf(msg, sizeof(msg), "%s", h->err);
-      snprintf(h->err, sizeof(h->err), "evaluate item %d: %.480s", i, msg);
-      return rc;
-    }
-  }
-  return QTR_OK;
-}
 
 static void vmap_eval_result_from(qtr_vmap_eval_result* res, const QtrVmapEvalRecord& r) {
   res->status = QTR_OK;
@@ -186,79 +127,40 @@ static void vmap_eval_result_from(qtr_vmap_eval_result* res, const QtrVmapEvalRe
 static int vmap_eval_run(qtr_handle* h, Slot& s, const qtr_voxel_map* m, const qtr_vmap_reg_item* items, int B, bool per_point,
                          VeItem* it, qtr_vmap_eval_result* results) {
   QTR_HIP_TRY(h, hipSetDevice(h->device));
-  if (!s.veval) {
-    VmapEval* ne = new (std::nothrow) VmapEval();
-    if (!ne) return QTR_ERR_CAPACITY;
-    s.veval = ne;  // (from here on the handle frees whatever of it exists)
-  }
+  QTR_TRY(vmap_arena_open(h, s.veval, kVePinBytes, 2));
   VmapEval& ve = *s.veval;
-  if (!ve.pin) QTR_HIP_TRY(h, hipHostMalloc((void**)&ve.pin, kVePinBytes));
-  for (hipEvent_t& e : ve.ev)
-    if (!e) QTR_HIP_TRY(h, hipEventCreate(&e));
   const hipStream_t st = s.stream;
 
-  // the arena's layout for this call: the views and, directly behind them, the tickets (one upload), the records, then
-  // every item's own arrays
-  size_t need = 0;
-  const auto take = [&](size_t bytes) {
-    const size_t at = need;
-    need += ve_up(bytes ? bytes : 1);
-    return at;
-  };
-  const size_t o_views = take((size_t)B * sizeof(VevalView));
-  const size_t o_ticket = take((size_t)B * 64);
+  // the arena's layout for this call: the views and, directly behind them, the tickets (one upload), the records, every
+  // item's own arrays, then the staged clouds
+  VmapCursor cur;
+  const size_t o_views = cur.take((size_t)B * sizeof(VevalView));
+  const size_t o_ticket = cur.take((size_t)B * 64);
   const size_t head_bytes = o_ticket + (size_t)B * 64;
-  const size_t o_rec = take((size_t)B * sizeof(QtrVmapEvalRecord));
+  const size_t o_rec = cur.take((size_t)B * sizeof(QtrVmapEvalRecord));
   int max_chunks = 0;
   for (int i = 0; i < B; ++i) {
     const int nchunk = qtr_div_up(it[i].n, QTR_ICP_CHUNK);
     max_chunks = std::max(max_chunks, nchunk);
-    it[i].o_partials = take((size_t)nchunk * QTR_VMAP_EVAL_NT * 8);
+    it[i].o_partials = cur.take((size_t)nchunk * QTR_VMAP_EVAL_NT * 8);
     if (per_point) {
-      it[i].o_corr = take((size_t)it[i].n * 4);
-      it[i].o_point = take((size_t)it[i].n * 16);
-    }
-    it[i].same_as = -1;
-    if (it[i].host && it[i].n > 0) {
-      for (int j = 0; j < i && it[i].same_as < 0; ++j)
-        if (it[j].host && it[j].n == it[i].n && it[j].src == it[i].src && it[j].nrm == it[i].nrm) it[i].same_as = j;
-      if (it[i].same_as < 0) {
-        it[i].o_src = take((size_t)it[i].n * 16);
-        it[i].o_nrm = take((size_t)it[i].n * 16);
-      } else {
-        it[i].o_src = it[it[i].same_as].o_src;
-        it[i].o_nrm = it[it[i].same_as].o_nrm;
-      }
+      it[i].o_corr = cur.take((size_t)it[i].n * 4);
+      it[i].o_point = cur.take((size_t)it[i].n * 16);
     }
   }
-  ve.B = -1;  // (the last call's sections are gone once this one writes the arena)
-  if (need > ve.dev_bytes) {
-    QTR_HIP_TRY(h, hipStreamSynchronize(st));
-    if (ve.dev) (void)hipFree(ve.dev);
-    ve.dev = nullptr;
-    ve.dev_bytes = 0;
-    QTR_HIP_TRY(h, hipMalloc(&ve.dev, need));
-    ve.dev_bytes = need;
-  }
+  vmap_group_plan(it, B, cur);
+  QTR_TRY(vmap_arena_grow(h, ve, cur.need, st));
   char* const dev = (char*)ve.dev;
   VevalView* const hv = (VevalView*)ve.pin;
   QtrVmapEvalRecord* const hrec = (QtrVmapEvalRecord*)(ve.pin + kVePinBack);
   QtrVmapEvalRecord* const drec = (QtrVmapEvalRecord*)(dev + o_rec);
 
   QTR_HIP_TRY(h, hipEventRecord(ve.ev[0], st));
+  QTR_TRY(vmap_group_upload(h, dev, it, B, st));
   for (int i = 0; i < B; ++i) {
-    const float4 *src = it[i].src, *nrm = it[i].nrm;
-    if (it[i].host && it[i].n > 0) {
-      if (it[i].same_as < 0) {
-        QTR_HIP_TRY(h, hipMemcpyAsync(dev + it[i].o_src, src, (size_t)it[i].n * 16, hipMemcpyHostToDevice, st));
-        QTR_HIP_TRY(h, hipMemcpyAsync(dev + it[i].o_nrm, nrm, (size_t)it[i].n * 16, hipMemcpyHostToDevice, st));
-      }
-      src = (const float4*)(dev + it[i].o_src);
-      nrm = (const float4*)(dev + it[i].o_nrm);
-    }
     VevalView v{};
-    v.src = src;
-    v.nrm = nrm;
+    v.src = (const float4*)it[i].src;
+    v.nrm = (const float4*)it[i].nrm;
     v.ns = it[i].n;
     vmap_guess(items[i].guess, v.T);
     v.partials = (double*)(dev + it[i].o_partials);
@@ -332,7 +234,8 @@ int qtr_voxel_map_evaluate_batch(qtr_handle* h, int slot, const qtr_voxel_map* m
     return QTR_ERR_BAD_ARG;
   }
   std::vector<VeItem> it((size_t)B);
-  QTR_TRY(vmap_eval_check(h, m, items, B, it.data()));
+  QTR_TRY(vmap_check(h, m));
+  QTR_TRY(vmap_group_check(h, "evaluate", "pose", "evaluate item", items, B, it.data()));
   return vmap_eval_run(h, *sp, m, items, B, prm->per_point != 0, it.data(), results);
 }
 
@@ -394,11 +297,5 @@ long long qtr_voxel_map_eval_fetch(qtr_handle* h, int slot, int item, int what, 
     case QTR_VMAP_EVAL_POINT: src = ve.point[item]; have = (size_t)ve.n[item] * 16; break;
     default: return -1;
   }
-  const size_t n = have < bytes ? have : bytes;
-  if (dst && n > 0) {
-    if (hipSetDevice(h->device) != hipSuccess) return -1;
-    if (hipStreamSynchronize(sp->stream) != hipSuccess) return -1;
-    if (hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) != hipSuccess) return -1;
-  }
-  return (long long)have;
+  return vmap_group_fetch(h, *sp, src, have, dst, bytes);
 }

@@ -19,8 +19,10 @@
 //   k_vmap_keep_mark   a pass over the S keys that only reads: the rule, counts of kept and evicted voxels and of evicted
 //                      members (64-bit), summed per workgroup
 //   (host)             nothing evicted: return, the table was only read.
-//   k_vmap_keep_stage  every survivor takes a staging index (a workgroup reserves its survivors' range with one atomic;
-//                      the order is free) and its key, count, acc and record go to staging;  k_vmap_clear;  k_vmap_keep_put
+//   (rebuild)          vmap_keep_rebuild, the end evict shares with carve (voxelmap_carve.hip): k_vmap_keep_stage — every
+//                      survivor takes a staging index (a workgroup reserves its survivors' range with one atomic; the order
+//                      is free) and its key, count, acc and record go to staging —, k_vmap_clear, k_vmap_keep_put.  The
+//                      staging pass is d_vmap_stage_kept under the caller's verdict: the window here, carve's mark byte there.
 // The staging index is given in phase two and not in phase one: the pass that usually ends the call then writes nothing
 // and takes no atomic per voxel.
 // Restore: the caller's arrays go to the staging buffer as they are (coords into the record area, which a restore does
@@ -91,11 +93,15 @@ __global__ __launch_bounds__(256) void k_vmap_keep_mark(VmapView m, QtrVmapWindo
   }
 }
 
-// Phase two, first kernel: the survivors' key, count, acc and record into staging.  A workgroup counts the survivors among
-// its slots, reserves that many staging indices with one atomic, and hands them out in a second pass over the same slots
-// (a wave's ballot and a cursor in LDS: the order is free).  S and the grid's stride are multiples of the wave, so a wave
-// is in the loop with all its lanes or with none.
-__global__ __launch_bounds__(256) void k_vmap_keep_stage(VmapView m, QtrVmapWindow w, VmapStage st, int n_kept) {
+// The staging pass of a rebuild: the survivors' key, count, acc and record into staging.  keep(e) is the verdict on slot e:
+// the window here, the mark byte in voxelmap_carve.hip.  A workgroup counts the survivors among its slots, reserves that
+// many staging indices with one atomic, and hands them out in a second pass over the same slots (a wave's ballot and a
+// cursor in LDS: the order is free).  A thread walks the slots first, first + stride, ... (the kernel states its grid, as
+// d_vmap_iter's callers do); S and the stride are multiples of the wave, so a wave is in the loop with all its lanes or with
+// none.
+template <class Keep>
+__device__ __forceinline__ void d_vmap_stage_kept(const VmapView& m, const VmapStage& st, int n_kept, u64 first, u64 stride,
+                                                  const Keep& keep) {
   __shared__ int s_n, s_base, s_cursor;
   if (threadIdx.x == 0) {
     s_n = 0;
@@ -103,36 +109,39 @@ __global__ __launch_bounds__(256) void k_vmap_keep_stage(VmapView m, QtrVmapWind
   }
   __syncthreads();
   int mine = 0;
-  for (u64 e = blockIdx.x * (u64)blockDim.x + threadIdx.x; e <= m.mask; e += (u64)gridDim.x * blockDim.x) {
-    u64 key;
-    bool keep;
-    const int n = d_vmap_keep_verdict(m, w, e, &key, &keep);
-    mine += (n > 0 && keep) ? 1 : 0;
-  }
+  for (u64 e = first; e <= m.mask; e += stride) mine += keep(e) ? 1 : 0;
   if (mine) atomicAdd(&s_n, mine);
   __syncthreads();
   if (threadIdx.x == 0) s_base = s_n ? atomicAdd(st.ctr + VK_CTR_STAGED, s_n) : 0;
   __syncthreads();
   if (s_n == 0) return;
   const int base = s_base;
-  for (u64 e = blockIdx.x * (u64)blockDim.x + threadIdx.x; e <= m.mask; e += (u64)gridDim.x * blockDim.x) {
-    u64 key;
-    bool keep;
-    const int n = d_vmap_keep_verdict(m, w, e, &key, &keep);
-    const u64 bal = __ballot(keep);
+  for (u64 e = first; e <= m.mask; e += stride) {
+    const bool kept = keep(e);
+    const u64 bal = __ballot(kept);
     if (!bal) continue;  // (the whole wave)
     int at = 0;
     if (qk_lane() == 0) at = atomicAdd(&s_cursor, __popcll(bal));
     at = __shfl(at, 0, 64);
     const int j = base + at + __popcll(bal & lanemask_lt());
-    if (keep && j >= 0 && j < n_kept) {  // (the bounds: never outside, phase one counted exactly these slots)
-      st.keys[j] = key;
-      st.cnt[j] = n;
+    if (kept && j >= 0 && j < n_kept) {  // (the bounds: never outside, the mark pass counted exactly these slots)
+      st.keys[j] = m.keys[e];
+      st.cnt[j] = m.cnt[e];
 #pragma unroll
       for (int k = 0; k < 9; ++k) st.acc[(size_t)j * 9 + k] = m.acc[(size_t)e * 9 + k];
       st.rec[j] = m.rec[e];
     }
   }
+}
+
+// phase two of evict, first kernel: the window is the verdict, as in phase one
+__global__ __launch_bounds__(256) void k_vmap_keep_stage(VmapView m, QtrVmapWindow w, VmapStage st, int n_kept) {
+  d_vmap_stage_kept(m, st, n_kept, blockIdx.x * (u64)blockDim.x + threadIdx.x, (u64)gridDim.x * blockDim.x, [&](u64 e) {
+    u64 key;
+    bool keep;
+    d_vmap_keep_verdict(m, w, e, &key, &keep);
+    return keep;
+  });
 }
 
 // restore: range and count of every voxel, its key (the empty key for a refused one), the sum of the counts
@@ -231,6 +240,32 @@ static int vmap_keep_read(qtr_handle* h, qtr_voxel_map* m, const VmapStage& st, 
   return QTR_OK;
 }
 
+// How evict and carve (verb) end, with the mark pass's counters on the host: n_kept survivors, n_gone voxels that leave
+// with members_gone members.  Nothing leaves: the table was only read.  Otherwise the table is rebuilt: stage(grid, block)
+// launches the caller's staging kernel for the n_kept survivors, then k_vmap_clear, k_vmap_keep_put and one read-back.
+template <class Stage>
+static int vmap_keep_rebuild(qtr_handle* h, qtr_voxel_map* m, const VmapStage& st, hipStream_t s, const char* verb, int n_kept,
+                             int n_gone, long long members_gone, const Stage& stage) {
+  if (n_kept + n_gone != m->info.n_voxels) {
+    snprintf(h->err, sizeof(h->err), "voxel map %s: the table holds %d voxels, the map says %d", verb, n_kept + n_gone,
+             m->info.n_voxels);
+    return QTR_ERR_HIP;
+  }
+  if (n_gone == 0) return QTR_OK;
+  const dim3 tgrid = vmap_keep_table_grid(m), blk(256);
+  if (n_kept > 0) stage(tgrid, blk);
+  hipLaunchKernelGGL(k_vmap_clear, tgrid, blk, 0, s, m->v, m->ins.tcnt);
+  if (n_kept > 0) hipLaunchKernelGGL(k_vmap_keep_put, dim3(qtr_div_up(n_kept, 256)), blk, 0, s, m->v, st, n_kept);
+  QTR_TRY(vmap_keep_read(h, m, st, s));
+  m->info.n_voxels = n_kept;
+  m->info.n_members -= members_gone;
+  if (m->pin[VK_CTR_DUP]) {  // (never: the survivors' keys are distinct and fewer than the slots)
+    snprintf(h->err, sizeof(h->err), "voxel map %s: the rebuild met a key twice", verb);
+    return QTR_ERR_HIP;
+  }
+  return QTR_OK;
+}
+
 int qtr_voxel_map_evict(qtr_handle* h, int slot, qtr_voxel_map* m, const double centre[3], double radius,
                         qtr_voxel_map_evict_info* out) {
   if (out) memset(out, 0, sizeof(*out));
@@ -255,30 +290,15 @@ int qtr_voxel_map_evict(qtr_handle* h, int slot, qtr_voxel_map* m, const double 
     VmapStage st;
     QTR_TRY(vmap_keep_reserve(h, m, (size_t)m->info.n_voxels, &st));
     const hipStream_t s = sp->stream;
-    const dim3 tgrid = vmap_keep_table_grid(m), blk(256);
     QTR_HIP_TRY(h, hipMemsetAsync(st.ctr, 0, VM_CTR_INTS * sizeof(int), s));
-    hipLaunchKernelGGL(k_vmap_keep_mark, tgrid, blk, 0, s, m->v, w, st.ctr);
+    hipLaunchKernelGGL(k_vmap_keep_mark, vmap_keep_table_grid(m), dim3(256), 0, s, m->v, w, st.ctr);
     QTR_TRY(vmap_keep_read(h, m, st, s));
     info.n_kept = m->pin[VK_CTR_KEPT];
     info.n_evicted = m->pin[VK_CTR_EVICTED];
     memcpy(&info.n_members_evicted, m->pin + VK_CTR_MEMBERS64, 8);
-    if (info.n_kept + info.n_evicted != m->info.n_voxels) {
-      snprintf(h->err, sizeof(h->err), "voxel map evict: the table holds %d voxels, the map says %d", info.n_kept + info.n_evicted,
-               m->info.n_voxels);
-      return QTR_ERR_HIP;
-    }
-    if (info.n_evicted > 0) {
-      if (info.n_kept > 0) hipLaunchKernelGGL(k_vmap_keep_stage, tgrid, blk, 0, s, m->v, w, st, info.n_kept);
-      hipLaunchKernelGGL(k_vmap_clear, tgrid, blk, 0, s, m->v, m->ins.tcnt);
-      if (info.n_kept > 0) hipLaunchKernelGGL(k_vmap_keep_put, dim3(qtr_div_up(info.n_kept, 256)), blk, 0, s, m->v, st, info.n_kept);
-      QTR_TRY(vmap_keep_read(h, m, st, s));
-      m->info.n_voxels = info.n_kept;
-      m->info.n_members -= info.n_members_evicted;
-      if (m->pin[VK_CTR_DUP]) {  // (never: the survivors' keys are distinct and fewer than the slots)
-        snprintf(h->err, sizeof(h->err), "voxel map evict: the rebuild met a key twice");
-        return QTR_ERR_HIP;
-      }
-    }
+    QTR_TRY(vmap_keep_rebuild(h, m, st, s, "evict", info.n_kept, info.n_evicted, info.n_members_evicted, [&](dim3 grid, dim3 blk) {
+      hipLaunchKernelGGL(k_vmap_keep_stage, grid, blk, 0, s, m->v, w, st, info.n_kept);
+    }));
   }
   if (out) *out = info;
   return QTR_OK;

@@ -280,6 +280,55 @@ def test_repeatable_and_leaves_the_map_and_the_single_call_state_alone(hip, hand
     assert vm.info() == info
 
 
+def _single(h, vm, item):
+    """The single call on slot 0 with its trace and corr sections (the slot's debug sections)."""
+    from quatro_amd import lib as ql
+    r = vm.register(*item)
+    return r, h.debug_fetch(ql.DBG_ICP_TRACE, np.float64).reshape(-1, 18), h.debug_fetch(ql.DBG_ICP_CORR, np.int32)
+
+
+def _same_as_single(h, vm, items, got, fetched, what):
+    for i, item in enumerate(items):
+        r, trace, corr = _single(h, vm, item)
+        _same_icp(got[i], r, f"{what}, item {i}")
+        assert fetched[i][0].shape == trace.shape and np.array_equal(_bits(fetched[i][0]), _bits(trace)), (what, i)
+        assert np.array_equal(fetched[i][1], corr), (what, i)
+
+
+def test_host_items_of_the_same_arrays_share_a_staged_copy_and_a_copy_of_them_does_not_matter(hip, hand):
+    """Three host items of 257 points (two chunks): items 0 and 2 are the same arrays under two guesses (one staged copy),
+    item 1 is a copy of them under item 0's guess (a staged copy of its own)."""
+    vm, _ = hand
+    p, a = BC.plane_cloud(257, 35)
+    items = [(p, a, BC.small(80)), (p.copy(), a.copy(), BC.small(80)), (p, a, BC.small(81))]
+    got = vm.register_batch(items)
+    fetched = _fetched(vm, 3)
+    _same_icp(got[1], got[0], "the copy against the arrays")
+    assert np.array_equal(_bits(fetched[1][0]), _bits(fetched[0][0])) and np.array_equal(fetched[1][1], fetched[0][1])
+    _same_as_single(hip, vm, items, got, fetched, "shared staging")
+
+
+def test_the_arena_follows_a_small_a_large_and_a_small_call_on_a_fresh_handle():
+    """B = 1 with n = 1, then B = 3 with n = 513, then B = 1 with n = 1 on a handle's first batches: the arena is made, grown
+    and reused; every call is the single calls', and the fetch after the third serves the third."""
+    from quatro_amd import lib as ql
+    h = ql.Handle(0)
+    vm = None
+    try:
+        vm = BC.hand_map(h.voxel_map)
+        for k, sizes in enumerate(((1,), (513, 513, 513), (1,))):
+            items = [BC.plane_cloud(n, 90 + 3 * k + j) + (BC.small(90 + 3 * k + j),) for j, n in enumerate(sizes)]
+            got = vm.register_batch(items)
+            _same_as_single(h, vm, items, got, _fetched(vm, len(items)), f"call {k}")
+        assert vm.batch_fetch(0, ql.VMAP_BATCH_CORR).shape == (1,)
+        with pytest.raises(ql.QuatroHipError):
+            vm.batch_fetch(1, ql.VMAP_BATCH_CORR)  # (the slot's last batch had one item)
+    finally:
+        if vm is not None:
+            vm.destroy()
+        h.close()
+
+
 def test_relocalize_on_the_room_returns_the_restatement_s_winner(hip, room):
     from quatro_amd import api
     vm, ref, q, qa, hyp = room
@@ -361,6 +410,31 @@ def test_every_refusal_leaves_not_run_records_and_the_map_unchanged(hip, hand, t
         stolen._m = None  # (not this wrapper's to destroy)
         foreign_kf = other.keyframe(traj["clouds"][0][0])
         refused(ql.QTR_ERR_BAD_ARG, "another handle", [items[0], (foreign_kf, g)])
+        # the whole texts: the single call's words behind the item's prefix, for items 0, 1 and 2
+        nan, mp = np.array(g), hip.limits.max_points
+        nan[0, 3] = np.nan
+        no_normals = "voxel map register: src_normals4 is NULL (the cloud entries do not compute normals)"
+        for code, text, its in (
+                (ql.QTR_ERR_BAD_ARG, "batch item 0: " + no_normals, [(p, None, g), items[1]]),
+                (ql.QTR_ERR_BAD_ARG, "batch item 1: " + no_normals, [items[0], (p, None, g)]),
+                (ql.QTR_ERR_CAPACITY, f"batch item 2: voxel map register: n={mp + 1} exceeds max_points={mp}",
+                 [items[0], items[2], (big, big, g)]),
+                (ql.QTR_ERR_BAD_ARG, "batch item 1: voxel map register: the guess has a non-finite entry in rows 0 - 2",
+                 [items[0], (p, a, nan), items[2]]),
+                (ql.QTR_ERR_BAD_ARG, "batch item 2: voxel map register: the guess has a non-finite entry in rows 0 - 2",
+                 [items[0], items[1], (traj["kfs"][0], nan)]),
+                (ql.QTR_ERR_BAD_ARG, "batch item 1: keyframe belongs to another handle", [items[0], (foreign_kf, g)])):
+            refused(code, text, its)
+            assert hip.last_error() == text, (hip.last_error(), text)
+        # two faults in one item: the cloud's checks come first, in the single call's order, then the guess
+        refused(ql.QTR_ERR_CAPACITY, "max_points", [items[0], (big, big, nan)])
+        refused(ql.QTR_ERR_BAD_ARG, "src_normals4", [items[0], (big, None, nan)])
+        # ... and the single calls judge the pose or guess before the cloud's size
+        for call, word in ((lambda: vm.insert(big, big, nan), "voxel map insert: the pose has a non-finite entry in rows 0 - 2"),
+                           (lambda: vm.register(big, big, nan), "voxel map register: the guess has a non-finite entry in rows 0 - 2")):
+            with pytest.raises(ql.QuatroHipError) as e:
+                call()
+            assert e.value.code == ql.QTR_ERR_BAD_ARG and hip.last_error() == word, (e.value.code, hip.last_error())
         # NULL pointers and a negative count, through the C ABI as it stands
         arr, keep = vm._batch_items(items)
         res = (ql.IcpResult * 3)()
@@ -377,6 +451,9 @@ def test_every_refusal_leaves_not_run_records_and_the_map_unchanged(hip, hand, t
         assert blib.qtr_voxel_map_register_batch(h, 7, m, arr, 3, ctypes.byref(prm), res) == ql.QTR_ERR_BAD_ARG  # no such slot
         arr[1].mem = 5
         assert blib.qtr_voxel_map_register_batch(h, 0, m, arr, 3, ctypes.byref(prm), res) == ql.QTR_ERR_BAD_ARG
+        arr[1].mem = 7
+        assert blib.qtr_voxel_map_register_batch(h, 0, m, arr, 3, ctypes.byref(prm), res) == ql.QTR_ERR_BAD_ARG
+        assert hip.last_error() == "batch item 1: bad voxel map register arguments"
         arr[1].mem, arr[1].n = ql.MEM_HOST, -2
         assert blib.qtr_voxel_map_register_batch(h, 0, m, arr, 3, ctypes.byref(prm), res) == ql.QTR_ERR_BAD_ARG
         assert all(res[i].status == ql.QTR_ERR_NOT_RUN for i in range(3))

@@ -219,6 +219,40 @@ def test_named_edge_cases_on_the_device(hip):
             vm.destroy()
 
 
+@pytest.mark.parametrize("far", [(), (0,), (0, 1, 2)])
+def test_three_voxels_in_128_slots_through_every_end_of_the_rebuild(hip, far):
+    """The smallest map that takes each path behind the mark pass: nothing carved (the table is only read), exactly one
+    voxel carved (stage, clear, put) and all carved (clear alone).  Three voxels of one member each, 5 m from the sensor in
+    the middle of pixels that are five columns apart (EDGE_IMAGE: limit 7.5 m); the scan's return on a voxel's ray lies at
+    6 m (occupied: kept) or at 40 m (seen through: carved)."""
+    def ray(az_deg, r):
+        e, a = np.deg2rad(-5.0), np.deg2rad(az_deg)
+        return [r * np.cos(e) * np.cos(a), r * np.cos(e) * np.sin(a), r * np.sin(e)]
+    az = (11.0, 124.0, -124.0)
+    pts = R.f4(np.array([ray(a, 5.0) for a in az], np.float32))
+    scan = R.f4(np.array([ray(a, 40.0 if j in far else 6.0) for j, a in enumerate(az)], np.float32))
+    up = np.zeros((3, 4), np.float32)
+    up[:, 2] = 1.0
+    p = CR.Params(**CC.EDGE_IMAGE)
+    assert M.table_slots(64) == 128
+    vm, ref = hip.voxel_map(0.5, 64), CR.RefMap(0.5, 64)
+    try:
+        assert vm.insert(pts, up) == ref.insert(pts, up) and len(vm) == 3
+        before = _sections(vm)
+        got = vm.carve(scan, None, p.to_lib())
+        assert got == ref.carve(scan, None, p), far
+        assert (got["n_kept"], got["n_carved"], got["n_tested"], got["n_members_carved"]) == (3 - len(far), len(far), 3, len(far))
+        _same_map(vm, ref, far)
+        gone = _keys(np.floor(pts[list(far), :3].astype(np.float64) / 0.5).reshape(-1, 3))
+        keep = ~np.isin(_keys(before[M.COORDS]), gone)
+        assert keep.sum() == 3 - len(far)
+        _same_sections(_sections(vm), {k: before[k][keep] for k in SECTIONS}, "the rows that stay")
+        assert vm.insert(pts, up) == ref.insert(pts, up)
+        _same_map(vm, ref, "an insert after it")
+    finally:
+        vm.destroy()
+
+
 def test_refusals_leave_the_map_as_it_was(hip, hand, hand_scans, trajectory):
     import ctypes
     from quatro_amd import lib as ql

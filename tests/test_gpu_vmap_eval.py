@@ -270,6 +270,56 @@ def test_repeatable_map_unchanged_other_arenas_untouched_and_two_slots(hip, maps
     assert vm.info() == info
 
 
+def _same_as_single(vm, items, got, what):
+    """A per-point batch that has just run against the single calls: records and both per-point sections, bit for bit."""
+    from quatro_amd import lib as ql
+    fetched = [(vm.eval_fetch(i, ql.VMAP_EVAL_CORR), vm.eval_fetch(i, ql.VMAP_EVAL_POINT)) for i in range(len(items))]
+    for i, item in enumerate(items):
+        _same(got[i], vm.evaluate(*item, per_point=True), f"{what}, item {i}")
+        assert np.array_equal(fetched[i][0], vm.eval_fetch(0, ql.VMAP_EVAL_CORR)), (what, i)
+        assert np.array_equal(_bits(fetched[i][1]), _bits(vm.eval_fetch(0, ql.VMAP_EVAL_POINT))), (what, i)
+    return fetched
+
+
+def test_host_items_of_the_same_arrays_share_a_staged_copy_and_a_copy_of_them_does_not_matter(hip, maps):
+    """Three host items of 257 points (two chunks) with per-point output: items 0 and 2 are the same arrays under two poses
+    (one staged copy), item 1 is a copy of them under item 0's pose (a staged copy of its own)."""
+    vm, _, _, sec = maps["sizes"]
+    p, a = BC.plane_cloud(257, 35)
+    items = [(p, a, BC.small(80)), (p.copy(), a.copy(), BC.small(80)), (p, a, BC.small(81))]
+    got = vm.evaluate_batch(items, per_point=True)
+    fetched = _same_as_single(vm, items, got, "shared staging")
+    _same(got[1], got[0], "the copy against the arrays")
+    assert np.array_equal(fetched[1][0], fetched[0][0]) and np.array_equal(_bits(fetched[1][1]), _bits(fetched[0][1]))
+    for i in range(3):
+        _same(got[i], E.evaluate(sec, *items[i]), f"shared staging against the restatement, item {i}")
+
+
+def test_the_arena_follows_a_small_a_large_and_a_small_call_on_a_fresh_handle():
+    """B = 1 with n = 1, then B = 3 with n = 513, then B = 1 with n = 1 on a handle's first evaluations: the arena is made,
+    grown and reused; every call is the single calls', and the fetch after the third serves the third."""
+    from quatro_amd import lib as ql
+    h = ql.Handle(0, n_slots=2)
+    vm = None
+    try:
+        vm = BC.hand_map(h.voxel_map)
+        for k, sizes in enumerate(((1,), (513, 513, 513), (1,))):
+            items = [BC.plane_cloud(n, 90 + 3 * k + j) + (BC.small(90 + 3 * k + j),) for j, n in enumerate(sizes)]
+            got = vm.evaluate_batch(items, per_point=True, slot=1)
+            fetched = [(vm.eval_fetch(i, ql.VMAP_EVAL_CORR, 1), vm.eval_fetch(i, ql.VMAP_EVAL_POINT, 1)) for i in range(len(items))]
+            for i, item in enumerate(items):  # (the single calls on slot 0: slot 1's arena sees only the three groups)
+                _same(got[i], vm.evaluate(*item, per_point=True), f"call {k}, item {i}")
+                assert np.array_equal(fetched[i][0], vm.eval_fetch(0, ql.VMAP_EVAL_CORR)), (k, i)
+                assert np.array_equal(_bits(fetched[i][1]), _bits(vm.eval_fetch(0, ql.VMAP_EVAL_POINT))), (k, i)
+        assert vm.eval_fetch(0, ql.VMAP_EVAL_CORR, 1).shape == (1,)
+        with pytest.raises(ql.QuatroHipError):
+            vm.eval_fetch(1, ql.VMAP_EVAL_CORR, 1)  # (the slot's last evaluation had one item)
+    finally:
+        if vm is not None:
+            vm.destroy()
+        h.close()
+
+
 def test_relocalize_keep_returns_the_full_batch_s_winner_on_the_room(hip, maps):
     from quatro_amd import api
     vm, items, want, _ = maps["room"]
@@ -358,6 +408,25 @@ def test_every_refusal_leaves_not_run_records(hip, maps, traj):
         stolen._m = None  # (not this wrapper's to destroy)
         foreign_kf = other.keyframe(traj["clouds"][0][0])
         refused(ql.QTR_ERR_BAD_ARG, "another handle", [its[0], (foreign_kf, T)])
+        # the whole texts: the single call's words behind the item's prefix, for items 0, 1 and 2
+        nan, mp = np.array(T), hip.limits.max_points
+        nan[0, 3] = np.nan
+        no_normals = "voxel map evaluate: src_normals4 is NULL (the cloud entries do not compute normals)"
+        for code, text, bad_items in (
+                (ql.QTR_ERR_BAD_ARG, "evaluate item 0: " + no_normals, [(p, None, T), its[1]]),
+                (ql.QTR_ERR_BAD_ARG, "evaluate item 1: " + no_normals, [its[0], (p, None, T)]),
+                (ql.QTR_ERR_CAPACITY, f"evaluate item 2: voxel map evaluate: n={mp + 1} exceeds max_points={mp}",
+                 [its[0], its[2], (big, big, T)]),
+                (ql.QTR_ERR_BAD_ARG, "evaluate item 1: voxel map evaluate: the pose has a non-finite entry in rows 0 - 2",
+                 [its[0], (p, a, nan), its[2]]),
+                (ql.QTR_ERR_BAD_ARG, "evaluate item 2: voxel map evaluate: the pose has a non-finite entry in rows 0 - 2",
+                 [its[0], its[1], (traj["kfs"][0], nan)]),
+                (ql.QTR_ERR_BAD_ARG, "evaluate item 1: keyframe belongs to another handle", [its[0], (foreign_kf, T)])):
+            refused(code, text, bad_items)
+            assert hip.last_error() == text, (hip.last_error(), text)
+        # two faults in one item: the cloud's checks come first, in the single call's order, then the pose
+        refused(ql.QTR_ERR_CAPACITY, "max_points", [its[0], (big, big, nan)])
+        refused(ql.QTR_ERR_BAD_ARG, "src_normals4", [its[0], (big, None, nan)])
         # NULL pointers, a negative count and a bad mem, through the C ABI as it stands
         arr, keep = vm._batch_items(its)
         res = (ql.VmapEvalResult * 3)()
@@ -373,6 +442,9 @@ def test_every_refusal_leaves_not_run_records(hip, maps, traj):
         assert elib.qtr_voxel_map_evaluate_batch(h, 7, m, arr, 3, ctypes.byref(prm), res) == ql.QTR_ERR_BAD_ARG  # no such slot
         arr[1].mem = 5
         assert elib.qtr_voxel_map_evaluate_batch(h, 0, m, arr, 3, ctypes.byref(prm), res) == ql.QTR_ERR_BAD_ARG and not_run()
+        arr[1].mem = 7
+        assert elib.qtr_voxel_map_evaluate_batch(h, 0, m, arr, 3, ctypes.byref(prm), res) == ql.QTR_ERR_BAD_ARG and not_run()
+        assert hip.last_error() == "evaluate item 1: bad voxel map evaluate arguments"
         arr[1].mem, arr[1].n = ql.MEM_HOST, -2
         assert elib.qtr_voxel_map_evaluate_batch(h, 0, m, arr, 3, ctypes.byref(prm), res) == ql.QTR_ERR_BAD_ARG and not_run()
         del keep

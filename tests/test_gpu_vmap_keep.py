@@ -257,6 +257,31 @@ def test_windows_that_keep_everything_and_nothing(hip, hand, hand_sections):
         vm.destroy()
 
 
+@pytest.mark.parametrize("centre,radius,kept", [((0.5, 0.5, 0.5), 10.0, 3), ((0.5, 0.5, 0.5), 2.0, 2), ((100.5, 0.5, 0.5), 0.0, 0)])
+def test_three_voxels_in_128_slots_through_every_end_of_the_rebuild(hip, centre, radius, kept):
+    """The smallest map that takes each path behind the mark pass: everything kept (the table is only read), exactly one
+    voxel gone (stage, clear, put) and all gone (clear alone)."""
+    coords = np.array([(0, 0, 0), (1, 0, 0), (5, 0, 0)])
+    pts, nrm = K.cloud_of_voxels(coords, 1.0, per_voxel=(4, 2, 7), seed=12)
+    assert M.table_slots(64) == 128
+    vm, ref = hip.voxel_map(1.0, 64), KR.RefMap(1.0, 64)
+    try:
+        assert vm.insert(pts, nrm) == ref.insert(pts, nrm)
+        before = _sections(vm)
+        win = KR.window_py(centre, radius, 1.0)
+        keep = np.array([KR.kept_py(win, c) for c in before[M.COORDS]], dtype=bool)
+        assert keep.sum() == kept
+        e = vm.evict(centre, radius)
+        assert e == ref.evict(centre, radius) and (e["n_kept"], e["n_evicted"]) == (kept, 3 - kept)
+        assert e["n_members_evicted"] == int(before[M.COUNT][~keep].sum())
+        _same_map(vm, ref, f"{kept} of 3 kept")
+        _same_sections(_sections(vm), {k: before[k][keep] for k in SECTIONS}, "the rows that stay")
+        assert vm.insert(pts, nrm) == ref.insert(pts, nrm)
+        _same_map(vm, ref, "an insert after it")
+    finally:
+        vm.destroy()
+
+
 def test_restore_from_host_and_device_memory_into_other_capacities(hip, hand, hand_sections):
     import torch
     from quatro_amd import lib as ql
