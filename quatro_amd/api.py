@@ -778,8 +778,63 @@ def constant_velocity_knots(T_prev2, T_prev1, period):
     return np.array([0.0, float(period)], dtype=np.float64), np.stack([np.eye(4), np.array(M, dtype=np.float64)])
 
 
+def sample_sweep(raw, times, leaf):
+    """One RAW point of every voxel floor(p / leaf) of a sweep, on the host: the lowest-index finite point of each voxel, in
+    ascending index, with its time.  A raw point and never a centroid, so its time is exact — what VoxelMap.register_ct needs.
+    Returns (points [m, 4] float32, times [m] float32); the times are the input's, unaltered."""
+    raw = np.ascontiguousarray(raw, dtype=np.float32).reshape(-1, 4)
+    times = np.ascontiguousarray(times, dtype=np.float32).reshape(-1)
+    if times.shape[0] != raw.shape[0]:
+        raise ValueError(f"sample_sweep: {raw.shape[0]} points, {times.shape[0]} times")
+    if not float(leaf) > 0.0:
+        raise ValueError(f"sample_sweep: leaf={leaf} must be positive")
+    idx = np.flatnonzero(np.isfinite(raw[:, :3]).all(axis=1))
+    if idx.size == 0:
+        return raw[:0].copy(), times[:0].copy()
+    vox = np.floor(raw[idx, :3].astype(np.float64) / float(leaf)).astype(np.int64)
+    _, first = np.unique(vox, axis=0, return_index=True)  # (the first occurrence of every voxel: the lowest index)
+    keep = idx[np.sort(first)]
+    return raw[keep].copy(), times[keep].copy()
+
+
+def _scan_to_map_odometry_ct(handle, scans, fp, voxel_size, icp, capacity, window_radius, times, sweep_period, carve):
+    """scan_to_map_odometry(continuous_time=True): see there."""
+    period = float(sweep_period)
+    knot_times = np.array([0.0, period], dtype=np.float64)
+    vmap = handle.voxel_map(voxel_size, (1 << 20) if capacity is None else capacity)
+    starts, end_prev = [], np.eye(4)
+    try:
+        for k, scan in enumerate(scans):
+            if isinstance(scan, _ql.Keyframe):
+                raise ValueError("scan_to_map_odometry: continuous_time needs raw sweeps (a keyframe's voxels carry no times)")
+            begin = end_prev  # B_k = E_{k-1}; E_0 ends an identity motion
+            if k == 0:
+                end = np.eye(4)
+            else:
+                guess = constant_velocity_guess(starts[-1], begin)
+                pts, ts = sample_sweep(scan, times[k], fp.voxel_size)
+                normals, _ = handle.fpfh(pts, fp.normal_radius, fp.fpfh_radius)  # (the histograms are computed and not used)
+                r = vmap.register_ct(pts, normals, ts, 0.0, period, begin, guess, icp)
+                end = np.array(r["T"], dtype=np.float64) if r["valid"] else np.array(guess, dtype=np.float64)
+            kf = handle.keyframe(scan, fp, times=times[k], knot_times=knot_times, knot_poses=np.stack([begin, end]), t_ref=0.0)
+            try:
+                vmap.insert_keyframe(kf, begin)
+                if window_radius is not None:
+                    vmap.evict(begin[:3, 3], window_radius)
+                if carve is not None:
+                    vmap.carve_keyframes([kf], begin[None], carve)
+            finally:
+                kf.close()
+            starts.append(begin)
+            end_prev = end
+    except Exception:
+        vmap.destroy()
+        raise
+    return (np.stack(starts) if starts else np.zeros((0, 4, 4))), vmap
+
+
 def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capacity=None, window_radius=None, times=None,
-                         sweep_period=None, carve=None):
+                         sweep_period=None, carve=None, continuous_time=False):
     """Scan-to-map odometry: a keyframe of every scan (fp; a scan that already is a Keyframe is used as it is), the first
     inserted at the identity, every later one registered against the map from the constant-velocity guess
     T_{k-1} (T_{k-2}^-1 T_{k-1}) (the identity motion for the second scan) and inserted under the result.  A registration
@@ -800,15 +855,28 @@ def scan_to_map_odometry(handle, scans, fp=None, voxel_size=1.0, icp=None, capac
     carve = CarveParams (lib.default_carve_params): after each insert — and after its eviction where a window is set — the
     map is carved with that scan's keyframe under its pose (VoxelMap.carve_keyframes, one vote, so carve.min_votes must be
     1; ValueError before anything is built): voxels the scan saw through leave the map before the next registration.  The scans should be raw sweeps (see
-    VoxelMap.carve).  None: nothing is carved."""
+    VoxelMap.carve).  None: nothing is carved.
+
+    continuous_time = True (needs times and sweep_period; every scan a raw sweep): the deskew is the registration's result
+    and no longer a guess made before it.  Sweep k >= 1 begins at B_k = E_{k-1}, the end pose of the sweep before it (E_0 = the
+    identity: the first sweep is taken as unmoved).  One raw point per voxel of side fp.voxel_size is taken from the sweep
+    with its time (sample_sweep), its normals come from Handle.fpfh (the histograms are wasted), and VoxelMap.register_ct
+    fits the END pose E_k against the map from the constant-velocity end guess B_k (B_{k-1}^-1 B_k) with the begin pose held
+    fixed, every point carried by the pose interpolated at its own time.  The sweep is then deskewed under the two knots
+    (B_k, E_k) on its way to its keyframe and inserted under B_k.  A registration that is not valid keeps its guess as E_k.
+    The returned poses stay the sweep STARTS, B_k.  False: everything above, unchanged."""
     fp = fp or _ql.default_frontend_params()
     if carve is not None and carve.min_votes != 1:
         raise ValueError(f"scan_to_map_odometry: carve.min_votes={carve.min_votes} (one scan votes per carve: it must be 1)")
+    if continuous_time and times is None:
+        raise ValueError("scan_to_map_odometry: continuous_time needs times and sweep_period (raw sweeps with per-point times)")
     if times is not None:
         if sweep_period is None or not float(sweep_period) > 0.0:
             raise ValueError("scan_to_map_odometry: times needs sweep_period > 0 (seconds per sweep)")
         if len(times) != len(scans):
             raise ValueError(f"scan_to_map_odometry: {len(scans)} scans, {len(times)} arrays of times")
+    if continuous_time:
+        return _scan_to_map_odometry_ct(handle, scans, fp, voxel_size, icp, capacity, window_radius, times, sweep_period, carve)
     vmap = handle.voxel_map(voxel_size, (1 << 20) if capacity is None else capacity)
     poses = []
     try:

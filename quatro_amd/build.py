@@ -25,6 +25,9 @@ EXT_LIB = os.path.join(HERE, "libquatro_ext.so")
 # both tables above are pinned by the test-suite, so what is added after them (include/quatro_place_batch.h onwards) is
 # exported by a second extension library over the same sources, -DQTR_EXT2_LIB with exports_ext2.map
 EXT2_LIB = os.path.join(HERE, "libquatro_ext2.so")
+# that table is pinned too, so what is added after it (include/quatro_voxelmap_ct.h onwards) is exported by a third extension
+# library over the same sources, -DQTR_EXT3_LIB with exports_ext3.map
+EXT3_LIB = os.path.join(HERE, "libquatro_ext3.so")
 INCLUDE = os.path.join(HERE, "..", "include")
 SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))) + sorted(
     os.path.join("..", "..", "include", f) for f in os.listdir(INCLUDE)
@@ -52,6 +55,11 @@ def build_ext2(force: bool = False, verbose: bool = True) -> str:
     return build(force, verbose, lib=EXT2_LIB, defines=("-DQTR_EXT2_LIB",), exports="exports_ext2.map")
 
 
+def build_ext3(force: bool = False, verbose: bool = True) -> str:
+    build(False, verbose)  # (as build_ext: the product library, where it is stale)
+    return build(force, verbose, lib=EXT3_LIB, defines=("-DQTR_EXT3_LIB",), exports="exports_ext3.map")
+
+
 def build(force: bool = False, verbose: bool = True, lib: str = LIB, defines=(), exports: str = "exports.map") -> str:
     if not force and not is_stale(lib):
         return lib
@@ -70,4 +78,5 @@ if __name__ == "__main__":
     build(force="--force" in sys.argv)
     build_ext(force="--force" in sys.argv)
     build_ext2(force="--force" in sys.argv)
+    build_ext3(force="--force" in sys.argv)
     build_test_engines(force="--force" in sys.argv)

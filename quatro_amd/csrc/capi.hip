@@ -78,6 +78,7 @@ struct Slot {
   struct VmapBatch* vbatch = nullptr;  // voxelmap_batch.hip: the slot's batch arena (allocated on the slot's first batch)
   struct VmapEval* veval = nullptr;    // voxelmap_eval.hip: the slot's map-evaluation arena (allocated on its first evaluation)
   struct PlaceBatch* pbatch = nullptr;  // place_batch.hip: the slot's grouped-query arena (allocated on its first batch)
+  struct VmapCtBufs* vct = nullptr;     // voxelmap_ct.hip: staged times and the census counters (allocated on its first call)
 };
 
 // What a batch lane is waiting for: the mail of the chain it enqueued last (lane_poll).
@@ -183,6 +184,7 @@ static void vmap_free_all(qtr_handle* h);  // (voxelmap.hip)
 static void vmap_batch_free(Slot& s);      // (voxelmap_batch.hip)
 static void vmap_eval_free(Slot& s);       // (voxelmap_eval.hip)
 static void place_batch_free(Slot& s);     // (place_batch.hip)
+static void vmap_ct_free(Slot& s);         // (voxelmap_ct.hip)
 
 #define QTR_TRY(expr)                  \
   do {                                 \
@@ -487,6 +489,7 @@ void qtr_destroy(qtr_handle* h) {
     vmap_batch_free(s);
     vmap_eval_free(s);
     place_batch_free(s);
+    vmap_ct_free(s);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.stream2) (void)hipStreamDestroy(s.stream2);
     if (s.stream3) (void)hipStreamDestroy(s.stream3);

@@ -548,9 +548,11 @@ int qtr_voxel_map_insert_keyframe(qtr_handle* h, int slot, qtr_voxel_map* m, con
 }
 
 // the registration of ns device-resident points with their normals: icp_loop (capi.hip) with the empty grid, only the
-// state's initialisation before the loop, and k_vmap_iter as its launch
-static int vmap_register_device(qtr_handle* h, Slot& s, const qtr_voxel_map* m, const float4* d_src, int ns,
-                                const float4* d_nrm, const double* guess, const qtr_icp_params* prm, qtr_icp_result* res) {
+// state's initialisation before the loop, and `launch` (st, chunks, view) as its launch: k_vmap_iter, or the continuous-time
+// iteration of voxelmap_ct.hip
+template <class Launch>
+static int vmap_register_loop(qtr_handle* h, Slot& s, const qtr_voxel_map* m, const float4* d_src, int ns, const float4* d_nrm,
+                              const double* guess, const qtr_icp_params* prm, qtr_icp_result* res, Launch launch) {
   const hipStream_t st = s.stream;
   IcpView& v = s.icp.v;
   const auto bind = [&]() -> int {
@@ -568,8 +570,14 @@ static int vmap_register_device(qtr_handle* h, Slot& s, const qtr_voxel_map* m, 
     return QTR_OK;
   };
   const dim3 chunks(qtr_div_up(ns, QTR_ICP_CHUNK));
-  return icp_loop(h, s, ns, ns == 0, guess, prm, res, bind, before,
-                  [&](const IcpView& w) { hipLaunchKernelGGL(k_vmap_iter, chunks, dim3(256), 0, st, w, m->v); });
+  return icp_loop(h, s, ns, ns == 0, guess, prm, res, bind, before, [&](const IcpView& w) { launch(st, chunks, w); });
+}
+
+static int vmap_register_device(qtr_handle* h, Slot& s, const qtr_voxel_map* m, const float4* d_src, int ns,
+                                const float4* d_nrm, const double* guess, const qtr_icp_params* prm, qtr_icp_result* res) {
+  return vmap_register_loop(h, s, m, d_src, ns, d_nrm, guess, prm, res, [&](hipStream_t st, dim3 chunks, const IcpView& w) {
+    hipLaunchKernelGGL(k_vmap_iter, chunks, dim3(256), 0, st, w, m->v);
+  });
 }
 
 static int vmap_check_register(qtr_handle* h, const qtr_voxel_map* m, const double* guess, const qtr_icp_params* prm) {

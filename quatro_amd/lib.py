@@ -199,6 +199,10 @@ class VmapEvalResult(C.Structure):
                 ("gradient", C.c_double * 6)]
 
 
+class VmapCtInfo(C.Structure):
+    _fields_ = [("n_points", C.c_int), ("n_skipped", C.c_int), ("n_extrapolated", C.c_int)]
+
+
 VMAP_BATCH_MAX = 64
 VMAP_EVAL_MAX = 1024
 VMAP_EVAL_CORR, VMAP_EVAL_POINT, VMAP_EVAL_TIMES = 1, 2, 3
@@ -253,6 +257,10 @@ EXT_EXPORTS = (VOXELMAP_EXPORTS + VOXELMAP_KEEP_EXPORTS + DESKEW_EXPORTS + VOXEL
 # the C ABI added after both tables above were pinned, per header; libquatro_ext2.so exports their concatenation
 PLACE_BATCH_EXPORTS = ["qtr_place_query_batch", "qtr_place_batch_fetch"]  # include/quatro_place_batch.h
 EXT2_EXPORTS = PLACE_BATCH_EXPORTS
+
+# ... and what was added after that table was pinned too; libquatro_ext3.so exports their concatenation
+VMAP_CT_EXPORTS = ["qtr_voxel_map_register_ct", "qtr_voxel_map_ct_pose_at"]  # include/quatro_voxelmap_ct.h
+EXT3_EXPORTS = VMAP_CT_EXPORTS
 
 _lib = None
 
@@ -550,6 +558,41 @@ def load_ext2():
     return lib
 
 
+EXT3_LIB_PATH = os.environ.get("QTR_EXT3_LIB") or os.path.join(_HERE, "libquatro_ext3.so")
+_ext3_lib = None
+
+
+def load_ext3():
+    """libquatro_ext3.so: the entry points added after libquatro_ext2.so's table was pinned (EXT3_EXPORTS).  They take the
+    handles and maps of load()'s and load_ext()'s libraries; all come from the same build (quatro_amd.build.build_ext3)."""
+    global _ext3_lib
+    if _ext3_lib is not None:
+        return _ext3_lib
+    load()  # (first: one HIP runtime per process)
+    if not os.path.exists(EXT3_LIB_PATH):
+        raise FileNotFoundError(
+            f"{EXT3_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
+            "(or __graft_entry__.build()) first.")
+    lib = C.CDLL(EXT3_LIB_PATH)
+    lib.qtr_voxel_map_register_ct.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(IcpParams),
+                                              C.POINTER(IcpResult), C.c_int, C.POINTER(VmapCtInfo)]
+    lib.qtr_voxel_map_ct_pose_at.argtypes = [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
+    _ext3_lib = lib
+    return lib
+
+
+def ct_pose_at(t_begin: float, t_end: float, begin_pose, end_pose, t: float) -> np.ndarray:
+    """qtr_voxel_map_ct_pose_at: the 4 x 4 pose at time t between (t_begin, begin_pose) and (t_end, end_pose) by the rule of
+    VoxelMap.register_ct (host only).  ValueError where the two poses differ by a rotation above pi / 2 or the times are
+    not finite with t_begin < t_end."""
+    B, E, T = _guess16(begin_pose), _guess16(end_pose), np.zeros(16, dtype=np.float64)
+    rc = load_ext3().qtr_voxel_map_ct_pose_at(float(t_begin), float(t_end), B.ctypes.data, E.ctypes.data, float(t), T.ctypes.data)
+    if rc != QTR_OK:
+        raise ValueError("ct_pose_at: refused (times not finite with t_begin < t_end, a non-finite pose, or a rotation above pi / 2)")
+    return T.reshape(4, 4)
+
+
 def default_vmap_eval_params(per_point: bool = False) -> VmapEvalParams:
     p = VmapEvalParams()
     load_ext().qtr_default_vmap_eval_params(C.byref(p))
@@ -837,6 +880,37 @@ class VoxelMap:
                                                     C.byref(prm), C.byref(res))
         h._check(rc)
         return _icp_dict(res)
+
+    def register_ct(self, cloud, normals, times, t_begin: float, t_end: float, begin_pose, guess_end=None,
+                    icp: IcpParams | None = None, slot: int = 0) -> dict:
+        """Continuous-time registration of a RAW sweep against the map (qtr_voxel_map_register_ct): `times` [n] float32 holds
+        the time of every point, begin_pose (4 x 4, sensor at t_begin -> world) is held fixed and the sensor's pose at t_end
+        is fitted from guess_end (None: begin_pose), every point carried by the pose interpolated at its own time.  Returns
+        register's dict — T is the END pose — plus "info": n_points, n_skipped (a non-finite coordinate or time, an unusable
+        normal), n_extrapolated (times outside [t_begin, t_end]; they still take part).  cloud, normals and times are numpy
+        arrays, or torch tensors that all live on the device."""
+        h = self._handle
+        prm = icp or default_icp_params(method=ICP_VOXEL_PLANE_TO_PLANE)
+        keep_p, keep_n, pp, pn, mem = self._cloud(cloud, normals)
+        if isinstance(times, np.ndarray) or not hasattr(times, "data_ptr"):
+            times = np.ascontiguousarray(times, dtype=np.float32).reshape(-1)
+        else:
+            import torch
+            assert times.dtype == torch.float32
+        pt, mt = _ptr(times)
+        n = int(keep_p.shape[0])
+        if mt != mem:
+            raise ValueError("cloud, normals and times must all be host arrays or all be device tensors")
+        if int(times.shape[0]) != n or len(times.shape) != 1:
+            raise ValueError(f"{n} points, times of shape {tuple(times.shape)}")
+        B, g, res, info = _guess16(begin_pose), _guess16(guess_end), IcpResult(), VmapCtInfo()
+        rc = load_ext3().qtr_voxel_map_register_ct(h._h, slot, self._m, pp, n, pn, pt, float(t_begin), float(t_end),
+                                                   None if B is None else B.ctypes.data, None if g is None else g.ctypes.data,
+                                                   C.byref(prm), C.byref(res), mem, C.byref(info))
+        h._check(rc)
+        out = _icp_dict(res)
+        out["info"] = {k: getattr(info, k) for k, _ in VmapCtInfo._fields_}
+        return out
 
     def _batch_items(self, items):
         """The C items of [(Keyframe, guess) | (xyz4, normals4, guess)] and the arrays that must outlive the call."""
