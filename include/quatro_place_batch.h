@@ -1,10 +1,9 @@
-/* quatro_place_batch.h - C ABI of the grouped place query, exported by quatro_amd/libquatro_ext2.so.
+/* quatro_place_batch.h - C ABI of the grouped place query, exported by quatro_amd/libquatro_ext.so.
  *
  * The two entry points below work on the handles, keyframes and place indexes of libquatro_hip.so
- * (include/quatro_hip.h).  libquatro_ext2.so is the second extension library: the same sources as libquatro_hip.so and
- * libquatro_ext.so, built with -DQTR_EXT2_LIB, with this header's names as its whole dynamic symbol table.  All libraries a
- * process loads must come from the same build.  The host-side plan of a call is include/qtr_place_batch_math.h; the
- * arithmetic is include/qtr_place_math.h's, unchanged.
+ * (include/quatro_hip.h); include/quatro_voxelmap.h says what the extension library is.  Both libraries must come from the
+ * same build.  The host-side plan of a call is include/qtr_place_batch_math.h; the arithmetic is include/qtr_place_math.h's,
+ * unchanged.
  *
  * What qtr_submit_batch_keyframes is to registration, this is to the search in front of it: Q queries against one index in
  * ONE chain of launches and ONE host wait.  Every entry of the union of the queries' ranges is filled into LDS once per
@@ -36,8 +35,8 @@
 extern "C" {
 #endif
 
-#ifndef QTR_EXT2_API /* (the builds of the other libraries hide these: they are libquatro_ext2.so's exports) */
-#define QTR_EXT2_API QTR_API
+#ifndef QTR_EXT_API /* (libquatro_ext.so's exports: csrc/exports_ext.map lists them, csrc/exports.map does not) */
+#define QTR_EXT_API QTR_API
 #endif
 
 #define QTR_PLACE_BATCH_MAX 1024            /* queries per call */
@@ -55,13 +54,13 @@ typedef struct qtr_place_query_item {
   int id_lo, id_hi; /* this query's range, clamped to [0, size] like qtr_place_query's */
 } qtr_place_query_item;
 
-QTR_EXT2_API int qtr_place_query_batch(qtr_handle* h, int slot, const qtr_place_index* index,
-                                       const qtr_place_query_item* items, int Q, int k, qtr_place_match* out /* Q x k */,
-                                       int* n_out /* Q */);
+QTR_EXT_API int qtr_place_query_batch(qtr_handle* h, int slot, const qtr_place_index* index,
+                                      const qtr_place_query_item* items, int Q, int k, qtr_place_match* out /* Q x k */,
+                                      int* n_out /* Q */);
 /* the slot's last batch: section `what` of query `query`, n_q = the length of its clamped range, in id order.  Copies
  * min(bytes, what there is) bytes to dst (may be NULL) and returns what there is; -1: a bad slot, query or `what`, or no
  * batch has run on the slot */
-QTR_EXT2_API long long qtr_place_batch_fetch(qtr_handle* h, int slot, int query, int what, void* dst, size_t bytes);
+QTR_EXT_API long long qtr_place_batch_fetch(qtr_handle* h, int slot, int query, int what, void* dst, size_t bytes);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 // quatro_place_batch.hpp — the grouped place query over quatro_place.hpp: Q queries against one PlaceIndex in one chain of
 // launches and one host wait (include/quatro_place_batch.h).  Query q is the single query of its source, range and k.
-// Host code only; link with -lquatro_hip -lquatro_ext2.
+// Host code only; link with -lquatro_hip -lquatro_ext.
 #ifndef QUATRO_PLACE_BATCH_H
 #define QUATRO_PLACE_BATCH_H
 

@@ -1,11 +1,12 @@
 /* quatro_voxelmap.h - C ABI of the persistent Gaussian voxel map, exported by quatro_amd/libquatro_ext.so.
  *
  * libquatro_ext.so is the extension library beside libquatro_hip.so (include/quatro_hip.h, whose entry points stay exactly
- * what they were): it is built from the same sources, shares the handle, the slots, the keyframes and the slot's ICP state
+ * what they were): it is linked from the same object, shares the handle, the slots, the keyframes and the slot's ICP state
  * with it, and exports the entry points of this header and of the other extension headers (quatro_voxelmap_keep.h,
- * quatro_voxelmap_carve.h, quatro_voxelmap_batch.h, quatro_voxelmap_eval.h, quatro_deskew.h) and nothing else.  A program
- * creates its handle with qtr_create, links both libraries and passes the handle to the calls here; qtr_last_error returns
- * their messages and qtr_debug_fetch their traces like any other call's.  Both libraries must come from the same build. */
+ * quatro_voxelmap_carve.h, quatro_voxelmap_batch.h, quatro_voxelmap_eval.h, quatro_deskew.h, quatro_place_batch.h,
+ * quatro_voxelmap_ct.h) and nothing else.  A program creates its handle with qtr_create, links both libraries
+ * (-lquatro_hip -lquatro_ext) and passes the handle to the calls here; qtr_last_error returns their messages and
+ * qtr_debug_fetch their traces like any other call's.  Both libraries must come from the same build. */
 #ifndef QUATRO_VOXELMAP_C_H
 #define QUATRO_VOXELMAP_C_H
 
@@ -15,7 +16,7 @@
 extern "C" {
 #endif
 
-#ifndef QTR_EXT_API /* (the build of libquatro_hip.so itself hides these: they are libquatro_ext.so's exports) */
+#ifndef QTR_EXT_API /* (libquatro_ext.so's exports: csrc/exports_ext.map lists them, csrc/exports.map does not) */
 #define QTR_EXT_API QTR_API
 #endif
 

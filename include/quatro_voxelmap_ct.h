@@ -1,10 +1,9 @@
 /* quatro_voxelmap_ct.h - C ABI of the continuous-time registration of a RAW sweep against a voxel map, exported by
- * quatro_amd/libquatro_ext3.so.
+ * quatro_amd/libquatro_ext.so.
  *
- * The two entry points below work on the handles and maps of libquatro_hip.so / libquatro_ext.so (include/quatro_hip.h,
- * include/quatro_voxelmap.h).  libquatro_ext3.so is the third extension library: the same sources as the other libraries,
- * built with -DQTR_EXT3_LIB, with this header's names as its whole dynamic symbol table.  All libraries a process loads must
- * come from the same build.  The arithmetic is include/qtr_vmap_ct_math.h.
+ * The two entry points below work on the handles of libquatro_hip.so (include/quatro_hip.h) and the maps of
+ * include/quatro_voxelmap.h, which says what the extension library is.  Both libraries must come from the same build.  The
+ * arithmetic is include/qtr_vmap_ct_math.h.
  *
  * qtr_voxel_map_register takes a cloud that somebody deskewed under a guess of the sensor's motion and fits ONE rigid pose to
  * it.  qtr_voxel_map_register_ct takes the sweep as the sensor recorded it, with the time of every point, and fits the
@@ -34,23 +33,23 @@
 extern "C" {
 #endif
 
-#ifndef QTR_EXT3_API /* (the builds of the other libraries hide these: they are libquatro_ext3.so's exports) */
-#define QTR_EXT3_API QTR_API
+#ifndef QTR_EXT_API /* (libquatro_ext.so's exports: csrc/exports_ext.map lists them, csrc/exports.map does not) */
+#define QTR_EXT_API QTR_API
 #endif
 
 typedef struct qtr_vmap_ct_info {
   int n_points, n_skipped, n_extrapolated;
 } qtr_vmap_ct_info;
 
-QTR_EXT3_API int qtr_voxel_map_register_ct(qtr_handle* h, int slot, const qtr_voxel_map* map, const float* src4, int n,
-                                           const float* src_normals4, const float* times, double t_begin, double t_end,
-                                           const double begin_pose[16], const double guess_end[16] /* NULL = begin_pose */,
-                                           const qtr_icp_params* prm, qtr_icp_result* res, int mem,
-                                           qtr_vmap_ct_info* info /* may be NULL */);
+QTR_EXT_API int qtr_voxel_map_register_ct(qtr_handle* h, int slot, const qtr_voxel_map* map, const float* src4, int n,
+                                          const float* src_normals4, const float* times, double t_begin, double t_end,
+                                          const double begin_pose[16], const double guess_end[16] /* NULL = begin_pose */,
+                                          const qtr_icp_params* prm, qtr_icp_result* res, int mem,
+                                          qtr_vmap_ct_info* info /* may be NULL */);
 /* host only: the pose at time t between (t_begin, begin_pose) and (t_end, end_pose) by the registration's rule, row 3 =
  * (0 0 0 1).  QTR_ERR_BAD_ARG: a NULL pointer, times that are not finite with t_begin < t_end, or a refused interval */
-QTR_EXT3_API int qtr_voxel_map_ct_pose_at(double t_begin, double t_end, const double begin_pose[16], const double end_pose[16],
-                                          double t, double* T16);
+QTR_EXT_API int qtr_voxel_map_ct_pose_at(double t_begin, double t_end, const double begin_pose[16], const double end_pose[16],
+                                         double t, double* T16);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 // quatro_voxelmap_ct.hpp — the continuous-time registration of a raw sweep over quatro_voxelmap.hpp: the sensor's pose at the
 // end of the sweep is fitted against the map while its pose at the beginning stays fixed, every point carried by the pose
 // interpolated at its own time (include/quatro_voxelmap_ct.h).  Poses are 16 row-major doubles.
-// Host code only; link with -lquatro_hip -lquatro_ext -lquatro_ext3.
+// Host code only; link with -lquatro_hip -lquatro_ext.
 #ifndef QUATRO_VOXELMAP_CT_H
 #define QUATRO_VOXELMAP_CT_H
 

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#ifndef QTR_EXT_API /* (the build of libquatro_hip.so itself hides these: they are libquatro_ext.so's exports) */
+#ifndef QTR_EXT_API /* (libquatro_ext.so's exports: csrc/exports_ext.map lists them, csrc/exports.map does not) */
 #define QTR_EXT_API QTR_API
 #endif
 

@@ -2,10 +2,10 @@
 // HBM between calls.  Clouds and keyframes are inserted under poses, scans are registered against it with the VGICP
 // iteration of icp.hip, and the voxel means come back as the map cloud.  The arithmetic is include/qtr_vmap_math.h.
 //
-// The entry points are exports of the extension library, libquatro_ext.so: the same unity.hip built with -DQTR_EXT_LIB and
-// exports_ext.map, so that it shares every structure of the handle with libquatro_hip.so, whose own symbol table stays the
-// C ABI of include/quatro_hip.h.  A handle made by the product library is used by the extension library: both run the same
-// code on the same HIP runtime, and no extension entry point touches a file-scope variable of capi.hip or solver.hip (each
+// The entry points are exports of the extension library, libquatro_ext.so: the object of unity.hip that libquatro_hip.so is
+// linked from, linked once more with exports_ext.map, so that it shares every structure of the handle with libquatro_hip.so,
+// whose own symbol table (exports.map) stays the C ABI of include/quatro_hip.h.  A handle made by the product library is
+// used by the extension library: both run the same code on the same HIP runtime, and no extension entry point touches a file-scope variable of capi.hip or solver.hip (each
 // library has its own copy of g_handle_uid and t_hca_share; only the product library's are ever used).
 //
 // Table: open addressing with linear probing over S slots (a power of two >= 2 x capacity), 64-bit keys, QTR_VMAP_EMPTY for

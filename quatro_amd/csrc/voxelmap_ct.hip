@@ -3,8 +3,8 @@
 // sensor's pose E at the sweep's end, its pose B at the beginning is fixed, and every point is carried by the pose interpolated
 // at its own time inside every iteration.  With every time at t_end the call IS qtr_voxel_map_register, bit for bit.
 //
-// The two entry points are exports of the third extension library, libquatro_ext3.so (unity.hip built with -DQTR_EXT3_LIB
-// and exports_ext3.map); the other libraries carry this code hidden and export none of it.
+// The two entry points are exports of the extension library, libquatro_ext.so (voxelmap.hip says how it is built);
+// libquatro_hip.so carries this code and exports none of it.
 //
 //   k_vmap_ct_census   one launch before the loop: the skipped and the extrapolated points, which depend on the points, their
 //                      normals and their times alone and not on the iterate; one ballot per wave, at most two integer atomics

@@ -239,7 +239,8 @@ EXPORTS = [
     "qtr_evaluate_keyframes_batch",
     "qtr_default_pgo_params", "qtr_pgo_optimize",
 ]
-# the C ABI of the six extension headers, per header; libquatro_ext.so exports their concatenation over the same handle
+# the C ABI of the extension headers, per header; libquatro_ext.so exports their concatenation over the same handle.  A new
+# header include/quatro_<name>.h brings its list <NAME>_EXPORTS and joins EXT_EXPORTS (tests/ext_abi.py holds it to that)
 VOXELMAP_EXPORTS = [  # include/quatro_voxelmap.h
     "qtr_default_voxel_map_params", "qtr_voxel_map_create", "qtr_voxel_map_destroy", "qtr_voxel_map_clear",
     "qtr_voxel_map_get_info", "qtr_voxel_map_insert", "qtr_voxel_map_insert_keyframe", "qtr_voxel_map_register",
@@ -251,16 +252,10 @@ VOXELMAP_CARVE_EXPORTS = ["qtr_default_carve_params", "qtr_voxel_map_carve", "qt
 VOXELMAP_BATCH_EXPORTS = ["qtr_voxel_map_register_batch", "qtr_voxel_map_batch_fetch"]  # include/quatro_voxelmap_batch.h
 VOXELMAP_EVAL_EXPORTS = ["qtr_default_vmap_eval_params", "qtr_voxel_map_evaluate", "qtr_voxel_map_evaluate_keyframe",
                          "qtr_voxel_map_evaluate_batch", "qtr_voxel_map_eval_fetch"]  # include/quatro_voxelmap_eval.h
-EXT_EXPORTS = (VOXELMAP_EXPORTS + VOXELMAP_KEEP_EXPORTS + DESKEW_EXPORTS + VOXELMAP_CARVE_EXPORTS + VOXELMAP_BATCH_EXPORTS
-               + VOXELMAP_EVAL_EXPORTS)
-
-# the C ABI added after both tables above were pinned, per header; libquatro_ext2.so exports their concatenation
 PLACE_BATCH_EXPORTS = ["qtr_place_query_batch", "qtr_place_batch_fetch"]  # include/quatro_place_batch.h
-EXT2_EXPORTS = PLACE_BATCH_EXPORTS
-
-# ... and what was added after that table was pinned too; libquatro_ext3.so exports their concatenation
 VMAP_CT_EXPORTS = ["qtr_voxel_map_register_ct", "qtr_voxel_map_ct_pose_at"]  # include/quatro_voxelmap_ct.h
-EXT3_EXPORTS = VMAP_CT_EXPORTS
+EXT_EXPORTS = (VOXELMAP_EXPORTS + VOXELMAP_KEEP_EXPORTS + DESKEW_EXPORTS + VOXELMAP_CARVE_EXPORTS + VOXELMAP_BATCH_EXPORTS
+               + VOXELMAP_EVAL_EXPORTS + PLACE_BATCH_EXPORTS + VMAP_CT_EXPORTS)
 
 _lib = None
 
@@ -327,20 +322,35 @@ _libs = {}
 TEST_ENGINES_LIB_PATH = os.path.join(_HERE, "libquatro_hip_testengines.so")  # the -DQTR_TEST_ENGINES build (tests only)
 
 
-def load(path: str | None = None):
-    """Loads libquatro_hip.so (or another build of it: the tests' comparison-engine build, a probe's candidate).  Raises
-    if it has not been built — there is no software fallback."""
-    global _lib
-    LIB_PATH = path or globals()["LIB_PATH"]
-    if LIB_PATH in _libs:
-        return _libs[LIB_PATH]
-    if not os.path.exists(LIB_PATH):
+def _open(path: str, signatures, product_first: bool = False):
+    """What load() and load_ext() share: the library at `path`, opened once with its ctypes signatures set.  Raises if it
+    has not been built — there is no software fallback."""
+    if path in _libs:
+        return _libs[path]
+    if not os.path.exists(path):
         raise RuntimeError(
-            f"{LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
+            f"{path} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
             "(or __graft_entry__.build()). quatro_amd has no CPU fallback.")
     # torch ships its own libamdhip64.so.7; importing it first makes both share ONE HIP runtime.
     import torch  # noqa: F401
-    lib = C.CDLL(LIB_PATH)
+    if product_first:
+        load()
+    lib = C.CDLL(path)
+    signatures(lib)
+    _libs[path] = lib
+    return lib
+
+
+def load(path: str | None = None):
+    """Loads libquatro_hip.so (or another build of it: the tests' comparison-engine build, a probe's candidate)."""
+    global _lib
+    lib = _open(path or LIB_PATH, _signatures)
+    if path is None:
+        _lib = lib
+    return lib
+
+
+def _signatures(lib):
     lib.qtr_last_error.restype = C.c_char_p
     lib.qtr_slot_stream.restype = C.c_void_p
     lib.qtr_debug_fetch.restype = C.c_longlong
@@ -462,28 +472,19 @@ def load(path: str | None = None):
                                     C.POINTER(PlaceMatch), C.POINTER(C.c_int)]
     lib.qtr_place_query_desc.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.POINTER(PlaceMatch), C.POINTER(C.c_int)]
-    _libs[LIB_PATH] = lib
-    if path is None:
-        _lib = lib
-    return lib
 
 
+# QTR_EXT_LIB: the extension library that belongs to QTR_LIB's build
 EXT_LIB_PATH = os.environ.get("QTR_EXT_LIB") or os.path.join(_HERE, "libquatro_ext.so")
-_ext_lib = None
 
 
 def load_ext():
-    """libquatro_ext.so: the entry points of the six extension headers (EXT_EXPORTS).  They take the handles, keyframes and
-    maps of load()'s library; both come from the same build (quatro_amd.build.build_ext)."""
-    global _ext_lib
-    if _ext_lib is not None:
-        return _ext_lib
-    load()  # (first: one HIP runtime per process)
-    if not os.path.exists(EXT_LIB_PATH):
-        raise FileNotFoundError(
-            f"{EXT_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
-            "(or __graft_entry__.build()) first.")
-    lib = C.CDLL(EXT_LIB_PATH)
+    """libquatro_ext.so: the entry points of the extension headers (EXT_EXPORTS).  They take the handles, keyframes, indexes
+    and maps of load()'s library, which is loaded first; both are linked from one object (quatro_amd.build.build)."""
+    return _open(EXT_LIB_PATH, _ext_signatures, product_first=True)
+
+
+def _ext_signatures(lib):
     lib.qtr_default_voxel_map_params.argtypes = [C.POINTER(VoxelMapParams)]
     lib.qtr_default_voxel_map_params.restype = None
     lib.qtr_voxel_map_create.argtypes = [C.c_void_p, C.POINTER(VoxelMapParams), C.POINTER(C.c_void_p)]
@@ -530,56 +531,14 @@ def load_ext():
                                                  C.POINTER(VmapEvalParams), C.POINTER(VmapEvalResult)]
     lib.qtr_voxel_map_eval_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     lib.qtr_voxel_map_eval_fetch.restype = C.c_longlong
-    _ext_lib = lib
-    return lib
-
-
-EXT2_LIB_PATH = os.environ.get("QTR_EXT2_LIB") or os.path.join(_HERE, "libquatro_ext2.so")
-_ext2_lib = None
-
-
-def load_ext2():
-    """libquatro_ext2.so: the entry points added after libquatro_ext.so's table was pinned (EXT2_EXPORTS).  They take the
-    handles, keyframes and indexes of load()'s library; all come from the same build (quatro_amd.build.build_ext2)."""
-    global _ext2_lib
-    if _ext2_lib is not None:
-        return _ext2_lib
-    load()  # (first: one HIP runtime per process)
-    if not os.path.exists(EXT2_LIB_PATH):
-        raise FileNotFoundError(
-            f"{EXT2_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
-            "(or __graft_entry__.build()) first.")
-    lib = C.CDLL(EXT2_LIB_PATH)
     lib.qtr_place_query_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PlaceQueryItem), C.c_int, C.c_int,
                                           C.c_void_p, C.c_void_p]
     lib.qtr_place_batch_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
     lib.qtr_place_batch_fetch.restype = C.c_longlong
-    _ext2_lib = lib
-    return lib
-
-
-EXT3_LIB_PATH = os.environ.get("QTR_EXT3_LIB") or os.path.join(_HERE, "libquatro_ext3.so")
-_ext3_lib = None
-
-
-def load_ext3():
-    """libquatro_ext3.so: the entry points added after libquatro_ext2.so's table was pinned (EXT3_EXPORTS).  They take the
-    handles and maps of load()'s and load_ext()'s libraries; all come from the same build (quatro_amd.build.build_ext3)."""
-    global _ext3_lib
-    if _ext3_lib is not None:
-        return _ext3_lib
-    load()  # (first: one HIP runtime per process)
-    if not os.path.exists(EXT3_LIB_PATH):
-        raise FileNotFoundError(
-            f"{EXT3_LIB_PATH} is missing: the HIP extension has not been built. Run `python -m quatro_amd.build` "
-            "(or __graft_entry__.build()) first.")
-    lib = C.CDLL(EXT3_LIB_PATH)
     lib.qtr_voxel_map_register_ct.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(IcpParams),
                                               C.POINTER(IcpResult), C.c_int, C.POINTER(VmapCtInfo)]
     lib.qtr_voxel_map_ct_pose_at.argtypes = [C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]
-    _ext3_lib = lib
-    return lib
 
 
 def ct_pose_at(t_begin: float, t_end: float, begin_pose, end_pose, t: float) -> np.ndarray:
@@ -587,7 +546,7 @@ def ct_pose_at(t_begin: float, t_end: float, begin_pose, end_pose, t: float) -> 
     VoxelMap.register_ct (host only).  ValueError where the two poses differ by a rotation above pi / 2 or the times are
     not finite with t_begin < t_end."""
     B, E, T = _guess16(begin_pose), _guess16(end_pose), np.zeros(16, dtype=np.float64)
-    rc = load_ext3().qtr_voxel_map_ct_pose_at(float(t_begin), float(t_end), B.ctypes.data, E.ctypes.data, float(t), T.ctypes.data)
+    rc = load_ext().qtr_voxel_map_ct_pose_at(float(t_begin), float(t_end), B.ctypes.data, E.ctypes.data, float(t), T.ctypes.data)
     if rc != QTR_OK:
         raise ValueError("ct_pose_at: refused (times not finite with t_begin < t_end, a non-finite pose, or a rotation above pi / 2)")
     return T.reshape(4, 4)
@@ -904,7 +863,7 @@ class VoxelMap:
         if int(times.shape[0]) != n or len(times.shape) != 1:
             raise ValueError(f"{n} points, times of shape {tuple(times.shape)}")
         B, g, res, info = _guess16(begin_pose), _guess16(guess_end), IcpResult(), VmapCtInfo()
-        rc = load_ext3().qtr_voxel_map_register_ct(h._h, slot, self._m, pp, n, pn, pt, float(t_begin), float(t_end),
+        rc = load_ext().qtr_voxel_map_register_ct(h._h, slot, self._m, pp, n, pn, pt, float(t_begin), float(t_end),
                                                    None if B is None else B.ctypes.data, None if g is None else g.ctypes.data,
                                                    C.byref(prm), C.byref(res), mem, C.byref(info))
         h._check(rc)
@@ -1236,7 +1195,7 @@ class PlaceIndex:
         arr = (PlaceQueryItem * max(Q, 1))(*[self._batch_item(x, keep) for x in items])
         out = np.zeros((Q, max(int(k), 0)), dtype=PLACE_MATCH_DTYPE)
         n = np.zeros(Q, dtype=np.int32)
-        h._check(load_ext2().qtr_place_query_batch(h._h, slot, self._ix, arr, Q, int(k), out.ctypes.data, n.ctypes.data))
+        h._check(load_ext().qtr_place_query_batch(h._h, slot, self._ix, arr, Q, int(k), out.ctypes.data, n.ctypes.data))
         if raw:
             return out, n
         return [[{"id": int(r["id"]), "shift": int(r["shift"]), "distance": np.float32(r["distance"]), "yaw": float(r["yaw"])}
@@ -1245,7 +1204,7 @@ class PlaceIndex:
     def batch_fetch(self, query: int, what: int = PLACE_BATCH_DIST, slot: int = 0) -> np.ndarray:
         """qtr_place_batch_fetch: PLACE_BATCH_DIST -> float32, PLACE_BATCH_SHIFT -> int32, one value per entry of the
         clamped range of query `query` of the slot's last query_batch, in id order."""
-        h, lib = self._handle, load_ext2()
+        h, lib = self._handle, load_ext()
         nbytes = lib.qtr_place_batch_fetch(h._h, slot, int(query), what, None, 0)
         if nbytes < 0:
             raise QuatroHipError(-1, "qtr_place_batch_fetch failed")

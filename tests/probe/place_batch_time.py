@@ -38,7 +38,7 @@ def main():
     rng = np.random.default_rng(1)
     h = ql.Handle(0)
     h.set_stage_events(False)
-    lib, lib2 = h._lib, ql.load_ext2()
+    lib, lib2 = h._lib, ql.load_ext()
     kfs = [h.keyframe(s) for k in range(8) for s in synth.kitti64_pair(k)[:2]]
     with h.place_index(16) as small:
         for kf in kfs:

@@ -1,4 +1,4 @@
-"""The grouped place query on the MI355X, through the C ABI of libquatro_ext2.so: every row of a batch equal, as raw records,
+"""The grouped place query on the MI355X, through the C ABI of libquatro_ext.so: every row of a batch equal, as raw records,
 to the restatement (tests/place_batch_restate.py over tests/place_restate.py) AND to the single calls; every score of every
 range; the contract's edges; retrieval, api.find_loops and api.close_loops on the twelve revisits; the C++ demo."""
 import ctypes as C
@@ -298,7 +298,7 @@ def test_every_refusal_leaves_the_outputs_as_the_contract_says(hip, h2, six, mix
     from quatro_amd import lib as ql
     kfs, vox = six
     ix, E, ix2 = mixture[0], mixture[1], mixture[2]
-    lib2, bad = ql.load_ext2(), ql.QTR_ERR_BAD_ARG
+    lib2, bad = ql.load_ext(), ql.QTR_ERR_BAD_ARG
     d0 = np.ascontiguousarray(E[0])
     good = _item(entry=1)
 
@@ -475,12 +475,11 @@ def test_cpp_place_batch_demo_builds_links_and_runs(hip, tmp_path):
     from quatro_amd import synth
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     libpath = qbuild.build(force=False, verbose=False)
-    ext2 = qbuild.build_ext2(force=False, verbose=False)
-    assert os.path.dirname(ext2) == os.path.dirname(libpath)
+    assert os.path.dirname(qbuild.build_ext(force=False, verbose=False)) == os.path.dirname(libpath)
     exe = str(tmp_path / "place_batch_demo")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
                            os.path.join(root, "tests", "cpp", "place_batch_demo.cpp"), "-o", exe, "-L", os.path.dirname(libpath),
-                           "-lquatro_hip", "-lquatro_ext2", "-Wl,-rpath," + os.path.dirname(libpath), "-Wl,-rpath,/opt/rocm/lib"])
+                           "-lquatro_hip", "-lquatro_ext", "-Wl,-rpath," + os.path.dirname(libpath), "-Wl,-rpath,/opt/rocm/lib"])
     scans = [synth.kitti64_pair(k, max_xy=2.0)[1] for k in (3, 2)] + [synth.kitti64_pair(k, max_xy=2.0)[0] for k in (2, 3, 4)]
     files = []
     for k, sc in enumerate(scans):

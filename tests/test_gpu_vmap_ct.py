@@ -1,4 +1,4 @@
-"""The continuous-time registration on the MI355X (qtr_voxel_map_register_ct, libquatro_ext3.so): the device equal to the host
+"""The continuous-time registration on the MI355X (qtr_voxel_map_register_ct, libquatro_ext.so): the device equal to the host
 restatement (tests/vmap_ct_ref/vmap_ct_ref.cpp) as raw records at the chunk edges, from host and device memory; the anchor —
 all times at t_end IS VoxelMap.register, bit for bit —; skipped and extrapolated points, the stops, two slots at once; every
 refusal with its code; the accuracy scenes of tests/test_vmap_ct_cpu.py as equal records; the C++ demo.  Everything goes
@@ -216,7 +216,7 @@ def test_refusals_leave_the_map_and_the_slot_usable(hip, maps):
         refused(ql.QTR_ERR_BAD_ARG, "t_begin", t_begin=tb, t_end=te)
     refused(ql.QTR_ERR_BAD_ARG, "pi / 2", guess_end=K.BEGIN @ R.rigid(R.rot(0.0, 0.0, np.radians(100.0)), [0.0, 0.0, 0.0]))
     # the C ABI itself: NULL arrays with n > 0, a negative n, NULL times, an unknown mem
-    lib3, res, prm = ql.load_ext3(), ql.IcpResult(), _vg()
+    lib3, res, prm = ql.load_ext(), ql.IcpResult(), _vg()
     import ctypes as C
     B, G = np.ascontiguousarray(K.BEGIN.reshape(16)), np.ascontiguousarray(K.GUESS_END.reshape(16))
 
@@ -308,13 +308,11 @@ def test_cpp_voxelmap_ct_demo_prints_what_the_python_calls_return(hip, tmp_path)
     from quatro_amd import lib as ql
     from quatro_amd import synth
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-    libpath = qbuild.build_ext3(force=False, verbose=False)
-    assert os.path.dirname(qbuild.build_ext(force=False, verbose=False)) == os.path.dirname(libpath)
+    libpath = qbuild.build_ext(force=False, verbose=False)
     exe = str(tmp_path / "voxelmap_ct_demo")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(root, "include"),
                            os.path.join(root, "tests", "cpp", "voxelmap_ct_demo.cpp"), "-o", exe, "-L", os.path.dirname(libpath),
-                           "-lquatro_hip", "-lquatro_ext", "-lquatro_ext3", "-Wl,-rpath," + os.path.dirname(libpath),
-                           "-Wl,-rpath,/opt/rocm/lib"])
+                           "-lquatro_hip", "-lquatro_ext", "-Wl,-rpath," + os.path.dirname(libpath), "-Wl,-rpath,/opt/rocm/lib"])
     pts, nrm, pose = K.small_map()
     s, sn, t, _, _ = K.edge_cloud(200)
     t[:3] = [np.float32(K.T_END + 0.01), np.float32(K.T_BEGIN), np.float32(K.T_END)]

@@ -1,9 +1,8 @@
-"""The grouped place query without a GPU: the second extension library's symbol table and the header's two entry points
-against map, binding and ctypes mirror; the host-side plan of include/qtr_place_batch_math.h compiled with g++ against its
+"""The grouped place query without a GPU: the header's two entry points against the extension library's symbol table,
+binding and ctypes mirror; the host-side plan of include/qtr_place_batch_math.h compiled with g++ against its
 Python mirror (tests/place_batch_restate.py); api.find_loops / api.close_loops over a fake index."""
 import ctypes
 import os
-import re
 import subprocess
 import tempfile
 
@@ -33,24 +32,12 @@ def ref_lib():
     return lib
 
 
-def test_the_second_extension_library_exports_the_two_names_and_nothing_else(ref_lib):
-    from quatro_amd import build as qbuild
+def test_the_extension_library_exports_the_headers_two_names_and_the_mirrors_match_the_compiled_header(ref_lib):
     from quatro_amd import lib as ql
-    ext2 = qbuild.build_ext2(force=False, verbose=False)
-    hip, ext = ext_abi.libraries()
-    assert os.path.basename(ext2) == "libquatro_ext2.so" and ext2 == qbuild.EXT2_LIB
-    assert ext_abi.table(ext2) == TWO
-    assert not (ext_abi.table(hip) & TWO) and not (ext_abi.table(ext) & TWO)
-    assert set(ql.PLACE_BATCH_EXPORTS) == TWO and list(ql.EXT2_EXPORTS) == list(ql.PLACE_BATCH_EXPORTS)
-    assert not (set(ql.EXPORTS) & TWO) and not (set(ql.EXT_EXPORTS) & TWO)
-    hdr = open(os.path.join(ROOT, "include", "quatro_place_batch.h")).read()
-    declared = set(re.findall(r"^QTR_EXT2_API [^\n(]*?\b(qtr_[a-z_0-9]+)\s*\(", hdr, flags=re.M))
-    assert declared == set(re.findall(r"\b(qtr_[a-z_0-9]+)\s*\(", hdr)) == TWO
-    emap = open(os.path.join(ROOT, "quatro_amd", "csrc", "exports_ext2.map")).read()
-    assert set(re.findall(r"\b(qtr_[a-z_0-9]+)\s*;", emap)) == TWO
-    assert emap.count("*") == 1 and re.search(r"\blocal:\s*\*;", emap)  # no wildcard among the globals
-    lib2 = ql.load_ext2()
-    assert all(getattr(lib2, n).argtypes is not None for n in TWO)
+    assert ext_abi.check_header("quatro_place_batch.h") == TWO  # declared, listed, exported by libquatro_ext.so alone
+    hip, _ = ext_abi.libraries()
+    assert set(ql.PLACE_BATCH_EXPORTS) == TWO
+    assert not (ext_abi.table(hip) & TWO) and not (set(ql.EXPORTS) & TWO)
     # the ctypes mirrors against sizeof / offsetof of the compiled header
     got = np.zeros(17, np.int32)
     ref_lib.place_batch_ref_layout(got.ctypes.data)

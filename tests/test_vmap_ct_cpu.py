@@ -1,10 +1,8 @@
 """The continuous-time registration's contract (include/qtr_vmap_ct_math.h) on the host: the restated loop
 (tests/vmap_ct_ref/vmap_ct_ref.cpp over a RefMap) against an independent restatement in Python floats, the anchor — all times
-at t_end IS the rigid map registration, bit for bit —, the Jacobian's stated bound, the third library's table and layout, the
+at t_end IS the rigid map registration, bit for bit —, the Jacobian's stated bound, the header's two entry points and layout, the
 glue of quatro_amd.api, and the accuracy of the method against today's path, computed by the restatements."""
 import ctypes
-import os
-import re
 import types
 
 import numpy as np
@@ -18,7 +16,6 @@ import vmap_ct_cases as K
 import vmap_ct_restate as CT
 import vmap_restate as M
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 TWO = {"qtr_voxel_map_register_ct", "qtr_voxel_map_ct_pose_at"}
 
 
@@ -173,27 +170,12 @@ def test_the_jacobian_is_within_the_bound_the_header_states():
     assert 0.1 * w / 8 < worst <= w / 8 + w * w  # (the gap is there, and of the size the first-order term says)
 
 
-def test_the_third_extension_library_exports_the_two_names_and_nothing_else():
-    from quatro_amd import build as qbuild
+def test_the_extension_library_exports_the_headers_two_names_and_pose_at_is_the_restatement():
     from quatro_amd import lib as ql
-    ext3 = qbuild.build_ext3(force=False, verbose=False)
-    ext2 = qbuild.build_ext2(force=False, verbose=False)
-    hip, ext = ext_abi.libraries()
-    assert os.path.basename(ext3) == "libquatro_ext3.so" and ext3 == qbuild.EXT3_LIB
-    assert ext_abi.table(ext3) == TWO
-    for other in (hip, ext, ext2):
-        assert not (ext_abi.table(other) & TWO), other
-    assert set(ql.VMAP_CT_EXPORTS) == TWO and list(ql.EXT3_EXPORTS) == list(ql.VMAP_CT_EXPORTS)
-    for names in (ql.EXPORTS, ql.EXT_EXPORTS, ql.EXT2_EXPORTS):
-        assert not (set(names) & TWO)
-    hdr = open(os.path.join(ROOT, "include", "quatro_voxelmap_ct.h")).read()
-    declared = set(re.findall(r"^QTR_EXT3_API [^\n(]*?\b(qtr_[a-z_0-9]+)\s*\(", hdr, flags=re.M))
-    assert declared == set(re.findall(r"\b(qtr_[a-z_0-9]+)\s*\(", hdr)) == TWO
-    emap = open(os.path.join(ROOT, "quatro_amd", "csrc", "exports_ext3.map")).read()
-    assert set(re.findall(r"\b(qtr_[a-z_0-9]+)\s*;", emap)) == TWO
-    assert emap.count("*") == 1 and re.search(r"\blocal:\s*\*;", emap)  # no wildcard among the globals
-    lib3 = ql.load_ext3()
-    assert all(getattr(lib3, n).argtypes is not None for n in TWO)
+    assert ext_abi.check_header("quatro_voxelmap_ct.h") == TWO  # declared, listed, exported by libquatro_ext.so alone
+    hip, _ = ext_abi.libraries()
+    assert set(ql.VMAP_CT_EXPORTS) == TWO
+    assert not (ext_abi.table(hip) & TWO) and not (set(ql.EXPORTS) & TWO)
     # the ctypes mirror against sizeof / offsetof of the compiled header
     got = np.zeros(4, np.int32)
     CT.load().vmap_ct_ref_layout(got.ctypes.data)
