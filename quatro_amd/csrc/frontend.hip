@@ -327,6 +327,9 @@ __device__ __forceinline__ void d_scan_i32_copy(const int* __restrict__ in, int*
 
 // =================================================================================================
 // K1  pcl::VoxelGrid::applyFilter restated
+// Two dimension formulas, as in PCL: the truncated extents (long long)((max - min) * inv) + 1 decide pass-through (their
+// product against INT32_MAX), the floor differences floor(max * inv) - floor(min * inv) + 1 — up to one more per axis — make
+// the keys, whose int32 arithmetic may therefore wrap on a grid that was accepted (tests/voxel_cases.py, family int32_edge).
 struct VoxGrid {
   float inv;
   int minb[3], divb[3];
