@@ -4016,6 +4016,9 @@ static int clique_stage_launch(const SolverArgs& a, int G, int L, int mode, doub
       const int lds_bitmap = (q_in_lds && kc_lds + 8 + bm_bytes <= (size_t)150 * 1024) ? 1 : 0;
       const bool hcore = hcore_planned(L), hc_sweeps = kcore_sweeps();
       bool after_async = false;
+      // (the quadratic ranking of the test build has no k_rank_sort behind k_hcore_async: it knows no floor, and
+      // k_hcore_finish does what k_rank_sort's after_async part does — tests/clique_cases.py found both missing)
+      static const bool rank_quadratic = QTR_ENGINE_ENV("QTR_RANK_QUADRATIC") != nullptr;
       if (hcore && !hc_sweeps) {
         // one resident workgroup per compute unit at most (they wait for one another); a group of pairs shares the device
         int nwg = min(min(hca_max_workgroups(), HCA_MAXWG), max(1, (L + 15) / 16));
@@ -4041,7 +4044,7 @@ static int clique_stage_launch(const SolverArgs& a, int G, int L, int mode, doub
           const char* e = QTR_ENGINE_ENV("QTR_HCORE_FLOOR");
           return e && atoi(e) == 0;
         }();
-        int allow_floor = (exact_cores || no_floor || mode == QTR_INLIER_KCORE_HEU) ? 0 : 1;
+        int allow_floor = (exact_cores || no_floor || rank_quadratic || mode == QTR_INLIER_KCORE_HEU) ? 0 : 1;
         // a single pair's large graph: one more workgroup, the scout (hca_scout) — one of the resident set, so a launch that
         // would fill the device gives it one of its places
         static const bool no_scout = [] {  // (QTR_HCORE_SCOUT=0: comparison runs of the test build)
@@ -4091,6 +4094,9 @@ static int clique_stage_launch(const SolverArgs& a, int G, int L, int mode, doub
         if (!hcore_prepared) LAUNCH_SV(k_hcore_async_init, a, dim3((max(L, 4096) + 255) / 256, 1, G), dim3(256), 0, stream);
         LAUNCH_SV(k_hcore_async, a, dim3(nwg + (scout ? 1 : 0), 1, G), dim3(HCA_THREADS), fixed + (size_t)2 * pool_entries, stream,
                   pool_entries, allow_floor);
+#ifdef QTR_TEST_ENGINES
+        if (rank_quadratic) LAUNCH_SV(k_hcore_finish, a, dim3(1, 1, G), dim3(1024), 0, stream, 1);
+#endif
         after_async = true;
       }
 #ifdef QTR_TEST_ENGINES
@@ -4100,7 +4106,6 @@ static int clique_stage_launch(const SolverArgs& a, int G, int L, int mode, doub
         LAUNCH_SV(k_hcore_finish, a, dim3(1, 1, G), dim3(1024), 0, stream, 0);
       }
 #endif
-      static const bool rank_quadratic = QTR_ENGINE_ENV("QTR_RANK_QUADRATIC") != nullptr;
       const size_t kc_bytes = kc_lds + (lds_bitmap ? bm_bytes + 8 : 0);
       // the peeling workgroup rides in k_rank_sort's launch (it is the fallback behind k_hcore_async, and the core-number
       // kernel of the graphs in between); the older chains keep its own launch
